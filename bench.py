@@ -10,6 +10,14 @@ collective); per-rule pass/fail/... counts are all-reduced over RCCL once after
 the timed region (PolicyReport summary), outside the timing.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n-res R] [--mode full|counts|scopes] [--config c2|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`,
+the algorithmic roofline of the timed passes, the status counts). `--full` adds the measurements
+that take runs of their own: `single_pass_ms`, the PCIe-inclusive `e2e_kv_validate` / `e2e_stream`
+legs, the CPU baseline and the in-run PMC traffic. `--dump-outputs DIR` writes what the last timed
+step computed as DIR/<name>.npy (the inputs are a seeded synthetic stream: the same arguments give
+the same arrays).
 """
 from __future__ import annotations
 
@@ -263,6 +271,51 @@ def e2e_stream(ps, n_res: int, kind_mix: int, device: int, seed: int, chunk: int
                         "the dense status matrix, two in flight)"}
 
 
+DUMP_STATUS_BYTES = 40 << 20  # float32 status sample of --dump-outputs
+DUMP_FAIL_PATHS = 20000  # FAIL pairs of that sample whose failing path is dumped
+
+
+def dump_outputs(out_dir: str, sess, mode: str, n_scopes: int, fetch: bool) -> None:
+    """--dump-outputs: what the session's last pass computed, as a caller receives it, one .npy per
+    array (float32 / float64, well under 64 MB in all). Always `counts` [rule][8]; scopes mode:
+    `scope_counts` [scope][rule][8]; full mode (kv_session_fetch; not a parts session, which keeps no
+    host batch): `status` [rule][k], the status matrix at the resource columns `status_res` [k] (all
+    of them, or a fixed seeded sample when the matrix is larger than DUMP_STATUS_BYTES), and
+    `fail_paths` [m][3] = (rule, resource, crc32 of the failing path; -1 without one) for a seeded
+    sample of the FAIL pairs in those columns."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+    save("counts", sess.counts().astype(np.float64))
+    if mode == "scopes":
+        save("scope_counts", sess.scope_counts(n_scopes).astype(np.float64))
+    if mode != "full" or not fetch:
+        return
+    r = sess.fetch()
+    st = r.status
+    rng = np.random.default_rng(0x6B76)
+    k = min(r.n_res, max(1, DUMP_STATUS_BYTES // (4 * max(1, r.n_rules))))
+    cols = np.arange(r.n_res) if k == r.n_res else np.sort(rng.choice(r.n_res, k, replace=False))
+    sample = st[:, cols]
+    save("status", sample.astype(np.float32))
+    save("status_res", cols.astype(np.float64))
+    fails = np.argwhere(sample == 1)
+    if len(fails) > DUMP_FAIL_PATHS:
+        fails = fails[np.sort(rng.choice(len(fails), DUMP_FAIL_PATHS, replace=False))]
+    rows = np.empty((len(fails), 3), np.float64)
+    for i, (rule, c) in enumerate(fails):
+        res = int(cols[c])
+        p = r.path(int(rule), res)
+        rows[i] = (rule, res, -1 if p is None else zlib.crc32(p.encode("utf-8")))
+    save("fail_paths", rows)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -279,8 +332,16 @@ def main():
                     help="c2: Pods x 100 pattern rules; c3: mixed kinds x 1000 policies with match/exclude; "
                          "c4: anchor-heavy chart + test/policy/validate + status forms (142 rules) x Pods; "
                          "c5: background scan, chart after autogen (105 rules) x mixed kinds, counts")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive kv_validate timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: single_pass_ms, "
+                         "the PCIe-inclusive e2e legs, the CPU baseline and the PMC traffic (each can be "
+                         "switched off with its --no-* option); a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64): "
+                         "counts, and in full mode a fixed seeded sample of the status matrix and of its "
+                         "failing paths, in scopes mode scope_counts")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the PCIe-inclusive kv_validate timing")
     ap.add_argument("--stream-ingesters", type=int, default=4,
                     help="e2e_stream: chunks ingested side by side (the host threads split among them)")
     ap.add_argument("--cpu-pairs", type=float, default=6e7,
@@ -290,13 +351,15 @@ def main():
                          "gloo lets several ranks share one GPU for a rehearsal")
     ap.add_argument("--rule-filter", default="", help="diagnostics: regex over C2 rule names")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the PMC traffic measurement (two rocprofv3 --pmc child runs of this workload)")
+                    help="--full: skip the PMC traffic measurement (two rocprofv3 --pmc child runs of this workload)")
     ap.add_argument("--engine", choices=["vm", "specialized"], default="specialized",
                     help="bytecode interpreter kernel, or per-policy-set specialized kernels (hiprtc)")
     ap.add_argument("--parts-per-gpu", type=int, default=1,
                     help="in-process multi-device path only: run each device's share as this many logical "
                          "parts on device 0 (KVGPU_SHARDS_PER_DEVICE; rehearses --gpus N on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     # --gpus N without a launcher (no WORLD_SIZE): one process drives the N devices through the
@@ -401,13 +464,17 @@ def main():
         dist.barrier()
     wall = te - ts
     kernel_ms = event_ms / args.steps
+    status_written = sess.status_bytes() if args.mode == "full" else 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sess, args.mode, len(namespaces), fetch=not inproc)
     # The K timed passes re-validate the resident batch: pass i + 1's per-pass tables are built on a
     # low-priority stream beside pass i's rule kernels (DESIGN.md §4 Streams). A caller validating
     # each batch once runs one pass with its tables in order: single_pass_ms (median of 5, untimed
-    # for `value`).
-    single = sorted(sess.run(1) for _ in range(5))
-    single_ms = single[len(single) // 2]
-    status_written = sess.status_bytes() if args.mode == "full" else 0
+    # for `value`; --full).
+    single_ms = None
+    if args.full:
+        single = sorted(sess.run(1) for _ in range(5))
+        single_ms = single[len(single) // 2]
     t_max = wall
     if dist is not None:
         import torch
@@ -467,14 +534,15 @@ def main():
                    "engine": args.engine},
         "kernel_ms_per_step": kernel_ms,
         "pipelined": True,
-        "single_pass_ms": single_ms,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      "bytes_per_launch": b_alg, "bytes_per_eval": b_alg / n_pairs_rank,
-                     "output_bytes": out_bytes, "status_bytes_written": status_written // n_devs,
-                     "single_pass_frac": b_alg / (single_ms / 1e3) / 1e9 / HBM_PEAK_GBS},
+                     "output_bytes": out_bytes, "status_bytes_written": status_written // n_devs},
         "status_counts": {n: int(counts[:, i].sum()) for i, n in enumerate(batch.STATUS_NAMES)},
     }
+    if single_ms is not None:
+        out["single_pass_ms"] = single_ms
+        out["roofline"]["single_pass_frac"] = b_alg / (single_ms / 1e3) / 1e9 / HBM_PEAK_GBS
     if scopes is not None:
         out["policy_reports"] = scopes
     # which RCCL reduces the PolicyReport counts: the communicator inside libkvgpu (in-process
@@ -491,7 +559,7 @@ def main():
     out["ingest"] = {"seconds": t2 - t1, "resources_per_s": n_res_total / (t2 - t1),
                      "MB_per_s": ndjson_bytes / (t2 - t1) / 1e6,
                      "threads": int(os.environ.get("KVGPU_INGEST_THREADS", min(16, os.cpu_count() or 1)))}
-    if rank == 0 and n_gpus == 1 and args.mode == "full" and not args.no_e2e:
+    if args.full and rank == 0 and n_gpus == 1 and args.mode == "full" and not args.no_e2e:
         # PCIe-inclusive rate of the host boundary: kv_validate on a freshly ingested
         # batch = H2D upload of the projected store + one pass + D2H of statuses and error records
         sess = None
@@ -522,12 +590,12 @@ def main():
         # the same stream as a caller would push it: ingest overlapped with upload + pass + fetch
         out["e2e_stream"] = e2e_stream(ps, args.n_res, kind_mix, local, workloads.SEED + 13,
                                        max(KV_LANES_CHUNK, args.n_res // 16), args.stream_ingesters)
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         # every core this process may run on (the GPU box grants a share of the machine's cores;
         # nproc and the CPU model are recorded beside it)
         threads = host_cpu()["available"]
         out["cpu_baseline"] = cpu_baseline(pols, args.cpu_pairs, threads, kind_mix, args.config.upper())
-    if rank == 0 and n_gpus == 1 and not args.no_traffic:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_traffic:
         # measured HBM bytes of the same workload (child rocprofv3 --pmc runs), after this
         # process's device buffers are freed
         sess = None

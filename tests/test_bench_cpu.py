@@ -64,6 +64,61 @@ def test_scope_union_remap_matches_report_reindexing():
     assert np.array_equal(c[u.index("ns-a")], counts[2])
 
 
+def test_dump_outputs_writes_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float arrays of the session's last pass; a status matrix above the
+    size limit is cut to the same seeded resource columns on every run, the failing paths come from
+    those columns."""
+    import zlib
+
+    import bench
+
+    n_rules, n_res = 3, 5000
+    st = (np.random.default_rng(1).integers(0, 3, (n_rules, n_res))).astype(np.uint8)
+
+    class FakeResult:
+        status = st
+
+        def __init__(self):
+            self.n_rules, self.n_res = st.shape
+
+        def path(self, rule, res):
+            assert st[rule, res] == 1
+            return None if rule == 2 else f"/spec/{rule}/{res}/"
+
+    class FakeSession:
+        def counts(self):
+            return np.arange(n_rules * 8, dtype=np.int64).reshape(n_rules, 8)
+
+        def scope_counts(self, n):
+            return np.ones((n, n_rules, 8), np.int64)
+
+        def fetch(self):
+            return FakeResult()
+
+    monkeypatch.setattr(bench, "DUMP_STATUS_BYTES", 4 * n_rules * 1000)
+    monkeypatch.setattr(bench, "DUMP_FAIL_PATHS", 50)
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), FakeSession(), "full", 0, fetch=True)
+        outs.append({f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    a, b = outs
+    assert sorted(a) == ["counts", "fail_paths", "status", "status_res"]
+    assert all(a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["counts"], FakeSession().counts())
+    cols = a["status_res"].astype(np.int64)
+    assert len(cols) == 1000 and np.all(np.diff(cols) > 0)
+    assert np.array_equal(a["status"], st[:, cols])
+    assert a["fail_paths"].shape == (50, 3)
+    for rule, res, crc in a["fail_paths"]:
+        assert res in cols and st[int(rule), int(res)] == 1
+        assert crc == (-1 if rule == 2 else zlib.crc32(f"/spec/{int(rule)}/{int(res)}/".encode()))
+    # counts / scopes modes and a parts session (no host batch to fetch) write no status
+    bench.dump_outputs(str(tmp_path / "c"), FakeSession(), "scopes", 2, fetch=True)
+    assert sorted(os.listdir(tmp_path / "c")) == ["counts.npy", "scope_counts.npy"]
+    bench.dump_outputs(str(tmp_path / "d"), FakeSession(), "full", 0, fetch=False)
+    assert os.listdir(tmp_path / "d") == ["counts.npy"]
+
+
 def test_inprocess_bench_refuses_a_wrong_rccl_rank_count(monkeypatch):
     """bench.py --gpus N (in process) must prove that RCCL reduced over one rank per distinct
     device: a parts session whose communicator reports another count ends the run non-zero

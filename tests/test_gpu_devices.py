@@ -127,6 +127,34 @@ def test_bench_in_process_parts_match_one_gpu(cfg):
         assert four["policy_reports"] == one["policy_reports"]
 
 
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """A plain `bench.py` run times its steps only (none of the --full legs in its line) and
+    `--dump-outputs` writes the last timed step's results: the same arrays on every run, equal to
+    kv_validate on the same stream."""
+    from kyverno_amd import batch, workloads
+
+    n = 8192
+    lines = [_bench("--n-res", str(n), "--steps", "3", "--dump-outputs", str(tmp_path / d)) for d in ("a", "b")]
+    for line in lines:
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert not {"single_pass_ms", "e2e_kv_validate", "e2e_stream", "cpu_baseline"} & set(line)
+        assert line["roofline"]["traffic"] is None
+    a, b = [{f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))} for d in ("a", "b")]
+    assert sorted(a) == ["counts", "fail_paths", "status", "status_res"]
+    assert all(a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) for k in a)
+    ps = batch.PolicySet(workloads.c2_policies(), specialize=True)
+    ref = batch.validate(ps, batch.Batch(ps, batch.synth(workloads.SEED, n)))
+    assert np.array_equal(a["status_res"], np.arange(n))  # small enough to be dumped whole
+    assert np.array_equal(a["status"], ref.status)
+    assert np.array_equal(a["counts"], ref.counts)
+    assert lines[0]["status_counts"]["fail"] == int((ref.status == 1).sum())
+    import zlib
+
+    for rule, res, crc in a["fail_paths"][:500]:
+        p = ref.path(int(rule), int(res))
+        assert crc == (-1 if p is None else zlib.crc32(p.encode()))
+
+
 @pytest.mark.parametrize("parts", [2, 3])
 def test_parts_session_matches_one_batch(parts):
     """kv_session_create_parts + kv_session_attach_part: each part's shard of the stream ingested

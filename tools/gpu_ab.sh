@@ -27,8 +27,8 @@ for f in glob.glob(sys.argv[3] + "/**/*kernel_stats.csv", recursive=True):
             print("   %-28s calls=%-4s avg=%.1f us" % (r["Name"][:28], r["Calls"], float(r["AverageNs"]) / 1e3))
 PY
 done
-if [ -n "$FULL" ]; then  # the default bench line (e2e leg, in-run PMC traffic, CPU baseline)
-  timeout -k 10 600 python -u bench.py ${FULL_ARGS} > $A/full.json 2> $A/full.err \
+if [ -n "$FULL" ]; then  # the default bench with --full (e2e leg, in-run PMC traffic, CPU baseline)
+  timeout -k 10 600 python -u bench.py --full ${FULL_ARGS} > $A/full.json 2> $A/full.err \
     || { echo "full bench failed"; tail -20 $A/full.err; exit 1; }
   cat $A/full.json
 fi

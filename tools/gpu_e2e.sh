@@ -8,7 +8,7 @@ for c in ${CFGS:-c2}; do
   for spec in "$@"; do
     envs=""; [ "$spec" != "-" ] && envs=$(echo "$spec" | tr ',' ' ')
     tag=$(echo "$c.$spec" | tr -c 'A-Za-z0-9.\n' '_')
-    env $envs timeout -k 10 400 python -u bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline --no-traffic $BENCH_ARGS \
+    env $envs timeout -k 10 400 python -u bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline --no-traffic $BENCH_ARGS \
       > $O/$tag.json 2> $O/$tag.err || { echo "bench $c $spec failed"; tail -5 $O/$tag.err; exit 1; }
     python - "$O/$tag.json" "$c $spec" <<'PY'
 import json, sys
@@ -23,7 +23,7 @@ done
 if [ -n "$TRACE" ]; then
   c=$(echo ${CFGS:-c2} | cut -d' ' -f1)
   (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --hip-runtime-trace --stats -d "$R/$O/trace" \
-     -o run --output-format csv -- python -u "$R/bench.py" --config $c --steps 2 --warmup 1 --no-cpu-baseline --no-traffic \
+     -o run --output-format csv -- python -u "$R/bench.py" --full --config $c --steps 2 --warmup 1 --no-cpu-baseline --no-traffic \
      > "$R/$O/trace.json" 2> "$R/$O/trace.err") || { echo "trace failed"; tail -5 $O/trace.err; exit 1; }
   echo trace ok
 fi

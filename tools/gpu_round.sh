@@ -3,7 +3,7 @@
 # Steps run in this order, each under its own time limit, stopping at the first failure:
 #   TESTS=1        pytest -m gpu (TESTS_K: a -k expression; TESTS_ARGS: extra pytest args)
 #   SMOKE=1        __graft_entry__.smoke()
-#   BENCH=1        the default bench line (C2: e2e leg, CPU baseline, in-run PMC traffic)
+#   BENCH=1        the default bench with --full (C2: e2e leg, CPU baseline, in-run PMC traffic)
 #   PROF=1         rocprofv3 kernel stats of the default bench
 #   CONFIGS="c3 c4 c5"  one bench line per config with in-run PMC traffic + rocprofv3 kernel stats
 #   STAMPS=1       per-segment shader-clock stamps of the rule kernels' waves (STAMPS_CFG, default c2)
@@ -23,7 +23,7 @@ if [ -n "$SMOKE" ]; then
   cat "$O/smoke.log"
 fi
 if [ -n "$BENCH" ]; then
-  timeout -k 10 600 python -u bench.py $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" \
+  timeout -k 10 600 python -u bench.py --full $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" \
     || { echo "bench failed"; tail -20 "$O/bench.err"; exit 1; }
   cat "$O/bench.json"
 fi
@@ -43,11 +43,11 @@ if [ -n "$PROF" ]; then
   kstats "$O/prof"
 fi
 for c in $CONFIGS; do
-  timeout -k 10 600 python -u bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline $CFG_ARGS \
+  timeout -k 10 600 python -u bench.py --full --config $c --steps 10 --warmup 2 --no-cpu-baseline $CFG_ARGS \
     > "$O/$c.json" 2> "$O/$c.err" || { echo "bench $c failed"; tail -20 "$O/$c.err"; exit 1; }
   cat "$O/$c.json"
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$R/$O/prof_$c" -o run --output-format csv -- \
-     python -u "$R/bench.py" --config $c --no-cpu-baseline --no-traffic --steps 10 --warmup 2 $CFG_ARGS \
+     python -u "$R/bench.py" --full --config $c --no-cpu-baseline --no-traffic --steps 10 --warmup 2 $CFG_ARGS \
      > "$R/$O/${c}_prof.json" 2> "$R/$O/${c}_prof.err") || { echo "prof $c failed"; tail "$O/${c}_prof.err"; exit 1; }
   kstats "$O/prof_$c"
 done
