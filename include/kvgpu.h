@@ -84,6 +84,9 @@ int kv_policyset_info(const kv_policyset* ps, uint32_t* n_policies, uint32_t* n_
 /* specialized kernels of a KV_COMPILE_SPECIALIZE policy set (zeros otherwise) */
 int kv_policyset_jit_info(const kv_policyset* ps, uint32_t* n_kernels, double* gen_ms, double* compile_ms,
                           uint64_t* code_bytes);
+/* path columns the specialized kernels read, by cell format: wide (12 or 16 bytes a cell) and
+ * narrow (4 bytes: presence, type and a scalar's value id) */
+int kv_policyset_jit_cols(const kv_policyset* ps, uint32_t* n_wide, uint32_t* n_narrow);
 int kv_rule_info_get(const kv_policyset* ps, uint32_t rule, kv_rule_info* out);
 
 /* Ingest resources (JSON array or NDJSON of unstructured objects; numbers typed

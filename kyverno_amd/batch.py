@@ -90,7 +90,10 @@ class PolicySet:
         nk, cb = ctypes.c_uint32(), ctypes.c_uint64()
         g, c = ctypes.c_double(), ctypes.c_double()
         lib().kv_policyset_jit_info(self._h, ctypes.byref(nk), ctypes.byref(g), ctypes.byref(c), ctypes.byref(cb))
-        return {"kernels": nk.value, "gen_ms": g.value, "compile_ms": c.value, "code_bytes": cb.value}
+        cw, cn = ctypes.c_uint32(), ctypes.c_uint32()
+        lib().kv_policyset_jit_cols(self._h, ctypes.byref(cw), ctypes.byref(cn))
+        return {"kernels": nk.value, "gen_ms": g.value, "compile_ms": c.value, "code_bytes": cb.value,
+                "cols_wide": cw.value, "cols_narrow": cn.value}
 
     def policy_rules(self, policy: int) -> list[Rule]:
         return [r for r in self.rules if r.policy == policy]

@@ -973,7 +973,7 @@ DevPolicySet& dev_ps(kv_policyset* s, int device) {
 }
 
 // Path columns of the batch for the policy set's specialized kernels (kvcol.h, kvdevtypes.h):
-// family 0 at [wave group][column][lane] (wave groups padded to whole workgroups, so every lane
+// the rows of family 0, one per wave group (wave groups padded to whole workgroups, so every lane
 // of the rule kernels' grid has its cells), then each family's element rows; built once per
 // batch and device from the node rows (d->view_dev must hold the batch view).
 void build_pcol(const JitImage& J, const Batch& b, DevBatchRes* d, int device) {
@@ -986,11 +986,20 @@ void build_pcol(const JitImage& J, const Batch& b, DevBatchRes* d, int device) {
   d->perow.alloc((size_t)std::max<uint32_t>(1u, nf - 1) * (groups + 1) * sizeof(uint32_t), device);
   HIPCHK(hipMemset(d->perow.p, 0, d->perow.n));
   std::vector<ColFam> fams(nf);
+  uint32_t n_wide = 0, n_narrow = 0;
   for (uint32_t f = 0; f < nf; f++) {
     fams[f].arr_col = J.fam_arr[f];
     fams[f].ncols = J.fam_ncols[f];
+    fams[f].nw = J.fam_nw.at(f);
+    fams[f].nb = J.fam_nb.at(f);
+    fams[f].nn = J.fam_nn.at(f);
     fams[f].erow = f ? (uint32_t*)d->perow.p + (size_t)(f - 1) * (groups + 1) : nullptr;
+    n_wide += fams[f].nw;
+    n_narrow += fams[f].nn;
   }
+  // (a narrow cell holds a Val id in KV_COL_PAYLOAD bits)
+  if (n_narrow && b.vals.size() + KV_PTAB_PSEUDO >= (1ull << KV_COL_PAYLOAD))
+    throw std::runtime_error("path columns: more than 2^28 distinct values");
   d->pfam.upload(fams, device);
   const DevBatch* Bd = (const DevBatch*)d->view_dev.p;
   const ColDesc* cd = (const ColDesc*)d->pcold.p;
@@ -1000,33 +1009,33 @@ void build_pcol(const JitImage& J, const Batch& b, DevBatchRes* d, int device) {
     erow.resize((size_t)(nf - 1) * (groups + 1));
     HIPCHK(hipMemcpy(erow.data(), d->perow.p, erow.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
-  const uint64_t root_cells = (uint64_t)groups * j0 * KV_LANES;
-  uint64_t cells = root_cells;
+  auto row_words = [&](uint32_t f) { return (uint64_t)(3u * fams[f].nw + fams[f].nb + fams[f].nn) * KV_LANES; };
+  const uint64_t root_words = (uint64_t)groups * row_words(0);
+  uint64_t words = root_words;
   for (uint32_t f = 1; f < nf; f++) {
-    fams[f].off_lo = (uint32_t)cells;
-    fams[f].off_hi = (uint32_t)(cells >> 32);
-    cells += (uint64_t)erow[(size_t)(f - 1) * (groups + 1) + groups] * fams[f].ncols * KV_LANES;
+    fams[f].off_lo = (uint32_t)words;
+    fams[f].off_hi = (uint32_t)(words >> 32);
+    words += (uint64_t)erow[(size_t)(f - 1) * (groups + 1) + groups] * row_words(f);
   }
-  // (the kernels index cells with 32 bits)
-  if (cells >= (1ull << 32)) throw std::runtime_error("path columns: more than 2^32 cells");
+  // (the kernels index the pool's words with 32 bits)
+  if (words >= (1ull << 32)) throw std::runtime_error("path columns: more than 2^32 words");
   HIPCHK(hipMemcpy(d->pfam.p, fams.data(), fams.size() * sizeof(ColFam), hipMemcpyHostToDevice));
-  // two planes (kvcol.h col_put): (kt, a, c) 12 B per cell, then b 4 B per cell
-  d->pcol.alloc(cells * sizeof(Node), device);
+  d->pcol.alloc(std::max<uint64_t>(words, 1) * sizeof(uint32_t), device);
   uint32_t* pool = (uint32_t*)d->pcol.p;
-  if (cells > root_cells) {  // element rows past a lane's own elements stay zero (both planes)
-    HIPCHK(hipMemset(pool + 3 * root_cells, 0, (cells - root_cells) * 12u));
-    HIPCHK(hipMemset(pool + 3 * cells + root_cells, 0, (cells - root_cells) * 4u));
-  }
-  HIPCHK(launch_pcol_build(Bd, cd, (const ColFam*)d->pfam.p, j0, 0, j0, groups, false, pool, cells, nullptr));
-  HIPCHK(launch_pcol_build(Bd, cd, (const ColFam*)d->pfam.p, j0, j0, (uint32_t)J.cols.size() - j0, groups, true,
-                           pool, cells, nullptr));
+  // element rows past a lane's own elements stay zero
+  if (words > root_words) HIPCHK(hipMemset(pool + root_words, 0, (words - root_words) * sizeof(uint32_t)));
+  HIPCHK(launch_pcol_build(Bd, cd, (const ColFam*)d->pfam.p, 0, j0, groups, false, pool, nullptr));
+  HIPCHK(launch_pcol_build(Bd, cd, (const ColFam*)d->pfam.p, j0, (uint32_t)J.cols.size() - j0, groups, true, pool,
+                           nullptr));
   HIPCHK(hipStreamSynchronize(nullptr));
   d->view.pcol = pool;
-  d->view.pcolb = pool + 3 * cells;
   d->pcol_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (getenv("KVGPU_VERBOSE"))
-    fprintf(stderr, "[kvgpu] path columns: %zu columns in %u families, %.1f MB, built in %.2f ms\n", J.cols.size(), nf,
-            cells * sizeof(Node) / 1e6, d->pcol_ms);
+    fprintf(stderr,
+            "[kvgpu] path columns: %u wide + %u narrow columns in %u families, %llu bytes (%.1f per resource), built in "
+            "%.2f ms\n",
+            n_wide, n_narrow, nf, (unsigned long long)(words * sizeof(uint32_t)),
+            b.res.empty() ? 0.0 : (double)(words * sizeof(uint32_t)) / (double)b.res.size(), d->pcol_ms);
 }
 
 std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int device) {
@@ -2412,6 +2421,16 @@ int kv_policyset_jit_info(const kv_policyset* ps, uint32_t* n_kernels, double* g
   if (gen_ms) *gen_ms = j ? j->gen_ms : 0;
   if (compile_ms) *compile_ms = j ? j->compile_ms : 0;
   if (code_bytes) *code_bytes = j ? kvh::code_bytes(*j) : 0;
+  return 0;
+}
+
+int kv_policyset_jit_cols(const kv_policyset* ps, uint32_t* n_wide, uint32_t* n_narrow) {
+  if (!ps) return KV_E_INVALID;
+  uint32_t w = 0, n = 0;
+  if (const JitImage* j = ps->jit.get())
+    for (const ColDesc& c : j->cols) (c.fmt == KV_COLF_NARROW ? n : w)++;
+  if (n_wide) *n_wide = w;
+  if (n_narrow) *n_narrow = n;
   return 0;
 }
 

@@ -8,7 +8,8 @@
 // key, a non-map parent, a slot past the map's slots); the present cells carry
 // KV_COL_PRESENT in kt (their key is dropped: the walk never reads a hoisted node's key) and
 // in c the node's own index when it is a map (the cursor of a wildcard-key lookup) or the
-// cell offset of its element rows when it holds a family's array.
+// word offset of its element rows when it holds a family's array. A narrow column keeps one
+// word of it (kvdevfn.h kv_narrow_cell).
 #pragma once
 
 // the node one step below n (held in cell *idx, ABSENT: none)
@@ -61,17 +62,27 @@ KV_FN Node col_cell(const Node& n, uint32_t idx, uint32_t arr_c) {
 }
 
 KV_FN uint64_t col_fam_off(const ColFam& F) { return (uint64_t)F.off_lo | (uint64_t)F.off_hi << 32; }
+// words of one row of family F: [wide (kt, a, c) x nw x 64][b x nb x 64][narrow x nn x 64]
+KV_FN uint32_t col_row_words(const ColFam& F) { return (3u * F.nw + F.nb + F.nn) * KV_LANES; }
 
-// cell i of a pool of `cells` cells in two planes (DevBatch::pcol): (kt, a, c) at word 3i, b at
-// word 3 cells + i
-KV_FN void col_put(uint32_t* __restrict__ pool, uint64_t cells, uint64_t i, const Node& n) {
-  pool[3 * i] = n.kt;
-  pool[3 * i + 1] = n.a;
-  pool[3 * i + 2] = n.c;
-  pool[3 * cells + i] = n.b;
+// lane `lane`'s cell of column d in the row of family F that starts at word `row` of the pool
+// (idx: the node's index)
+KV_FN void col_put(uint32_t* __restrict__ pool, uint64_t row, const ColFam& F, const ColDesc& d, uint32_t lane,
+                   const Node& n, uint32_t idx) {
+  if (d.fmt == KV_COLF_NARROW) {
+    pool[row + (size_t)(3u * F.nw + F.nb + d.pos) * KV_LANES + lane] = kv_narrow_cell(n.kt, n.a, idx);
+    return;
+  }
+  uint32_t* __restrict__ w = pool + row + (size_t)d.pos * (3u * KV_LANES) + 3u * lane;
+  w[0] = n.kt;
+  w[1] = n.a;
+  w[2] = n.c;
+  if (d.fmt == KV_COLF_WIDEB) pool[row + (size_t)(3u * F.nw + d.bpos) * KV_LANES + lane] = n.b;
 }
-KV_FN Node col_get(const uint32_t* __restrict__ pool, uint64_t cells, uint64_t i) {
-  return Node{pool[3 * i], pool[3 * i + 1], pool[3 * cells + i], pool[3 * i + 2]};
+// a wide cell with its b (a family array's)
+KV_FN Node col_get(const uint32_t* __restrict__ pool, uint64_t row, const ColFam& F, const ColDesc& d, uint32_t lane) {
+  const uint32_t* __restrict__ w = pool + row + (size_t)d.pos * (3u * KV_LANES) + 3u * lane;
+  return Node{w[0], w[1], pool[row + (size_t)(3u * F.nw + d.bpos) * KV_LANES + lane], w[2]};
 }
 
 // element rows lane r needs in family f (its array's element count; 0 without an array)
@@ -83,34 +94,35 @@ KV_FN uint32_t col_rows(const DevBatch& B, const ColDesc* cols, const ColFam* fa
 }
 
 // cell of family-0 column `c` for lane r (r >= n_res: the zero cell), written into the pool
-KV_FN void col_build_root(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t j0, uint32_t c,
-                          uint32_t r, uint32_t* __restrict__ pool, uint64_t cells) {
+KV_FN void col_build_root(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t c, uint32_t r,
+                          uint32_t* __restrict__ pool) {
   const ColDesc& d = cols[c];
   Node cell{0u, 0u, 0u, 0u};
+  uint32_t idx = ABSENT;
   if (r < B.n_res) {
-    uint32_t idx;
     const Node n = col_walk(B.nodes, ni(B.res[r].root), d, &idx);
     uint32_t arr_c = 0u;
-    if (d.arr_fam) {  // a family array: the offset of this wave group's element rows
+    if (d.arr_fam) {  // a family array: the word offset of this wave group's element rows
       const ColFam& F = fams[d.arr_fam];
-      arr_c = (uint32_t)(col_fam_off(F) + (uint64_t)F.erow[r >> 6] * F.ncols * KV_LANES);
+      arr_c = (uint32_t)(col_fam_off(F) + (uint64_t)F.erow[r >> 6] * col_row_words(F));
     }
     cell = col_cell(n, idx, arr_c);
   }
-  col_put(pool, cells, ((size_t)(r >> 6) * j0 + d.j) * KV_LANES + (r & (KV_LANES - 1)), cell);
+  col_put(pool, (uint64_t)(r >> 6) * col_row_words(fams[0]), fams[0], d, r & (KV_LANES - 1), cell, idx);
 }
 
-// cells of element column `c` (family f > 0) for every element of lane r's family array
-KV_FN void col_build_elem(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t j0, uint32_t c,
-                          uint32_t r, uint32_t* __restrict__ pool, uint64_t cells) {
+// cells of element column `c` (family f > 0) for every element of lane r's family array (whose
+// cell, a wide one with its b, must be built)
+KV_FN void col_build_elem(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t c, uint32_t r,
+                          uint32_t* __restrict__ pool) {
   const ColDesc& d = cols[c];
   const ColFam& F = fams[d.fam];
   const uint32_t lane = r & (KV_LANES - 1);
-  const Node a = col_get(pool, cells, ((size_t)(r >> 6) * j0 + F.arr_col) * KV_LANES + lane);
+  const Node a = col_get(pool, (uint64_t)(r >> 6) * col_row_words(fams[0]), fams[0], cols[F.arr_col], lane);
   if (node_type(a.kt) != NT_ARR || a.kt == 0u) return;
   for (uint32_t i = 0; i < a.b; i++) {
     uint32_t idx;
     const Node n = col_walk(B.nodes, ni(a.a + i), d, &idx);
-    col_put(pool, cells, (size_t)a.c + ((size_t)i * F.ncols + d.j) * KV_LANES + lane, col_cell(n, idx, 0u));
+    col_put(pool, (uint64_t)a.c + (uint64_t)i * col_row_words(F), F, d, lane, col_cell(n, idx, 0u), idx);
   }
 }

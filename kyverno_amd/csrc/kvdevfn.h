@@ -75,20 +75,45 @@ __device__ __forceinline__ Node kv_ldn(const Node* p, size_t i) {
 #endif
 }
 
-// path-column cell i (DevBatch::pcol / pcolb planes): its (kt, a, c) words as one 12-byte
-// global-address-space load and its b word (an array's element count) as a 4-byte one, which
-// only array cells need (a caller that never reads .b leaves it dead)
-__device__ __forceinline__ Node kv_ldc(const uint32_t* pa, const uint32_t* pb, size_t i) {
+// Path-column cells (DevBatch::pcol, kvdevtypes.h ColDesc; word offsets into the pool).
+// A wide cell: its (kt, a, c) words at word i as one 12-byte global-address-space load (b = 0),
+// and with its b word (an array's element count) at word ib as a 4-byte one (a caller that
+// never reads .b leaves it dead).
+__device__ __forceinline__ Node kv_ldw(const uint32_t* p, uint32_t i) {
 #if defined(__HIP_DEVICE_COMPILE__)
   // (a 12-byte cell is 4-byte aligned: the type says so, gfx950 loads it as one dwordx3)
   typedef uint32_t u32x3_ __attribute__((ext_vector_type(3), aligned(4)));
-  const u32x3_ x = *(const __attribute__((address_space(1))) u32x3_*)((const __attribute__((address_space(1))) char*)pa + 12u * i);
-  const uint32_t y = ((const __attribute__((address_space(1))) uint32_t*)pb)[i];
-  return Node{x.x, x.y, y, x.z};
+  const u32x3_ x = *(const __attribute__((address_space(1))) u32x3_*)((const __attribute__((address_space(1))) uint32_t*)p + i);
+  return Node{x.x, x.y, 0u, x.z};
 #else
-  return Node{pa[3 * i], pa[3 * i + 1], pb[i], pa[3 * i + 2]};
+  return Node{p[i], p[i + 1], 0u, p[i + 2]};
 #endif
 }
+__device__ __forceinline__ Node kv_ldwb(const uint32_t* p, uint32_t i, uint32_t ib) {
+  Node n = kv_ldw(p, i);
+  n.b = kv_gld(p, ib);
+  return n;
+}
+// A narrow cell (one word: 0 absent, else (8 | type) << 28 | payload: the Val id of a scalar,
+// the node's row - its index / 64 - for an array, 0 for null / map) as the node its consumers
+// see: {type | KV_COL_PRESENT, payload, 0, 0}, all zero when absent
+KV_HD inline uint32_t kv_narrow_cell(uint32_t kt, uint32_t a, uint32_t idx) {
+  if (kt == 0u) return 0u;
+  const uint32_t t = node_type(kt);
+  return (8u | t) << KV_COL_PAYLOAD | (t - 1u < 4u ? a : t == NT_ARR ? idx / KV_LANES : 0u);
+}
+KV_HD inline Node kv_narrow_node(uint32_t w) {
+  return Node{((w >> KV_COL_PAYLOAD) & 7u) | ((w >> (KV_COL_PAYLOAD - 1u)) & KV_COL_PRESENT),
+              w & ((1u << KV_COL_PAYLOAD) - 1u), 0u, 0u};
+}
+__device__ __forceinline__ Node kv_ldn(const uint32_t* p, uint32_t i) { return kv_narrow_node(kv_gld(p, i)); }
+// The node index a narrow map cell stands for: none of its consumers reads one (kvjit.cpp
+// col_plan), so the host emulator hands out a poison index that faults where one did
+#ifdef KVEMU
+#define KV_NARROW_IDX 0x7FFFFFF0u
+#else
+#define KV_NARROW_IDX 0u
+#endif
 
 // node index of this lane's cell in a row (wave-group layout, kv_layout.h)
 __device__ __forceinline__ uint32_t ni(uint32_t row) { return row * KV_LANES + (threadIdx.x & (KV_LANES - 1)); }
@@ -749,6 +774,23 @@ __device__ __forceinline__ uint32_t kv_leaf_word(const DevPS& P, const Node* __r
   uint32_t x = 0xFFFFFFFFu;
   for (uint32_t k = 0; k < n.b; k++) {
     const Node e = N[ni(n.a + k)];
+    x &= kv_gld(P.ptab, (size_t)w * P.n_vals + kv_ptab_col(P, node_type(e.kt), e.a));
+  }
+  return x;
+}
+
+// table word `w` of the leaf predicates on the node of a narrow cell n. An array at a leaf
+// position (rare, divergent) needs its first element and its count, which the cell does not
+// hold: its payload is the array node's row (a lane's nodes all lie in the lane's column of
+// the node rows, so row x 64 + lane is the node), read here.
+__device__ __forceinline__ uint32_t kv_leaf_word_n(const DevPS& P, const Node* __restrict__ N, const Node& n, uint32_t w) {
+  const uint32_t t = node_type(n.kt);
+  if (t != NT_ARR) return kv_leaf_word(P, N, n, w);
+  const uint32_t ai = ni(n.a);
+  const uint32_t first = kv_gld(&N[ai].a, 0), count = kv_gld(&N[ai].b, 0);
+  uint32_t x = 0xFFFFFFFFu;
+  for (uint32_t k = 0; k < count; k++) {
+    const Node e = N[ni(first + k)];
     x &= kv_gld(P.ptab, (size_t)w * P.n_vals + kv_ptab_col(P, node_type(e.kt), e.a));
   }
   return x;

@@ -131,40 +131,52 @@ struct DevBatch {
   const DevPS* dps;
   const uint32_t* dleaf;
   const uint8_t* dyn_st;
-  // path columns of the specialized kernels (kvcol.h; null without them), in two planes: the
-  // (kt, a, c) words of every cell, then its b words (pcolb = pcol + 3 x cells), so a lookup
-  // of a map or a scalar (everything but an array's element count) loads 12 of its 16 bytes
+  // path columns of the specialized kernels (kvcol.h; null without them): one pool of 32-bit
+  // words, every row of a family laid out by cell format (below), so a lookup loads only the
+  // words its consumers read (4 bytes for a narrow cell, 12 or 16 for a wide one)
   const uint32_t* pcol;
-  const uint32_t* pcolb;
 };
 
 // ------------------------------------------------------------------ path columns
 // The specialized kernels read every lookup whose path from the resource root (or from the
 // element of a fused array loop) is static from a column of the batch's nodes at that path,
-// one coalesced 16 B load, instead of chasing the path through the node rows (kvjit.cpp
-// hoist). Columns come in families: family 0 has one column per root path, laid out
-// [wave group][column][lane]; family f > 0 belongs to one array path (its "family array", a
-// column of family 0) and holds one column per path relative to that array's elements, laid
-// out [element row][column][lane] with the element rows of each wave group together
-// (element i of a lane's array: row E + i, E = the family array cell's `c`). Cell of a present
-// node: {type | KV_COL_PRESENT, a, b, c'} with c' = the node's own index for a map, the cell
-// offset of its element rows for a family array, the node's c otherwise; absent: all zero.
+// one coalesced load, instead of chasing the path through the node rows (kvjit.cpp hoist).
+// Columns come in families: family 0 has one column per root path, one row per wave group;
+// family f > 0 belongs to one array path (its "family array", a column of family 0) and holds
+// one column per path relative to that array's elements, one row per element with the element
+// rows of each wave group together (element i of a lane's array: the row at word E + i x the
+// family's row words, E = the family array cell's `c`).
+// A column's cell format is chosen by the generator from what the kernels read of it (kvjit.cpp
+// col_plan): a *narrow* cell is one word, 0 for an absent node, else (8 | type) << 28 | the
+// Val id of a scalar (0 for null / map / array) - presence, type and value are all its
+// consumers read; a *wide* cell is the present node as {type | KV_COL_PRESENT, a, c'} with c' =
+// the node's own index for a map, the word offset of its element rows for a family array, the
+// node's c otherwise (absent: all zero), and its b in a plane of its own when a consumer reads
+// it. A row of a family with nw wide columns, nb of them with a b plane, and nn narrow ones:
+//   [wide (kt, a, c) x nw x 64 lanes][b x nb x 64][narrow x nn x 64]     (32-bit words)
 // Built once per batch and device (kvcol.h, kv_pcol_* in kvkernel.hip).
 constexpr uint32_t KV_COL_MAXD = 12;            // steps of a column path
 constexpr uint32_t KV_COL_SCAN = 0x80000000u;   // step: key id of a keep-all map (else a slot)
 constexpr uint32_t KV_COL_PRESENT = 16u;        // kt of a present cell: type | KV_COL_PRESENT
+constexpr uint32_t KV_COL_PAYLOAD = 28u;        // payload bits of a narrow cell (Val ids below 2^28)
+enum ColFmt : uint32_t { KV_COLF_WIDE = 0, KV_COLF_WIDEB = 1, KV_COLF_NARROW = 2 };
 struct ColDesc {
   uint32_t fam;      // 0: a root path, f > 0: a path relative to the elements of family f
-  uint32_t j;        // column within its family
+  uint32_t j;        // column within its family (order of first use)
   uint32_t nsteps;   // path length
   uint32_t arr_fam;  // family columns 0: the family whose array this column holds (0: none)
+  uint32_t fmt;      // ColFmt
+  uint32_t pos;      // position among the family's wide (or narrow) columns
+  uint32_t bpos;     // KV_COLF_WIDEB: position in the b plane
   uint32_t steps[KV_COL_MAXD];
 };
-// per family: its array's column in family 0 (family 0: unused), its columns; set per batch:
-// the first cell of its element rows in the pool, and (device pointer) the exclusive prefix of
-// element rows per wave group (n_groups + 1 entries: the last one is the family's row count)
+// per family: its array's column in family 0 (family 0: unused), its columns by format; set per
+// batch: the first word of its element rows in the pool, and (device pointer) the exclusive
+// prefix of element rows per wave group (n_groups + 1 entries: the last one is the family's row
+// count)
 struct ColFam {
   uint32_t arr_col, ncols;
+  uint32_t nw, nb, nn;
   uint32_t off_lo, off_hi;
   uint32_t* erow;
 };

@@ -99,8 +99,9 @@ struct Gen {
   // or the loop element: one independent coalesced load per lookup instead of a chain of
   // dependent ones. Family 0 holds root paths; family f > 0 the paths relative to the elements
   // of one array path (a column of family 0). Columns are numbered in order of first use; the
-  // column count of each family is a macro (KVC_J<f>) defined at the head of every kernel
-  // program once the whole image is generated.
+  // kernels read column j of family f through macros (KVC_LD_<f>_<j> and its kin, col_plan)
+  // defined at the head of every kernel program once the whole image is generated and the
+  // cell format of every column is known.
   // Site records of rule groups (kvdevtypes.h GSiteDesc): per group of 2+ members its descriptor
   // (n, gpre, moff, 0) in gs_desc and its members' (rule, pattern-node shift) in gs_mem, numbered
   // in generation order over the image; k_gs0 / k_gsn: the first group and the groups of the kernel
@@ -111,7 +112,24 @@ struct Gen {
     std::string arr;                          // family array expr (family 0: "")
     std::map<std::string, uint32_t> idx;      // relative expr -> column
     std::vector<std::vector<uint32_t>> steps; // per column: its path steps
+    std::vector<uint32_t> use;                // per column: what the kernels read of it (ColUse)
   };
+  // Cell format of a column (kvdevtypes.h ColFmt): narrow unless a consumer, marked where it is
+  // emitted, reads more of a cell than its presence, its type and a scalar's Val id. CU_WIDE: a
+  // field of the node (.a / .b / .c) or a map's own node index is read; CU_B: the node's b is
+  // (an array's element count); CU_LEAF: a leaf predicate reads it (its array case needs a and b
+  // when the cell is wide, and reads the array's node when it is narrow: kv_leaf_word_n). The uses of every
+  // rule of the policy set decide, whatever the kernel plan; KVGPU_JIT_NARROW=0 makes every
+  // column wide (A/B runs; read here, so part of the program text and of the cache keys).
+  enum ColUse : uint32_t { CU_WIDE = 1u, CU_B = 2u, CU_LEAF = 4u };
+  const bool narrow_on = !(getenv("KVGPU_JIT_NARROW") && getenv("KVGPU_JIT_NARROW")[0] == '0');
+  std::map<std::string, uint32_t> use_seed;  // uses known before generation (JitImage::col_use)
+  void col_mark(int fam, uint32_t j, uint32_t use) {
+    if (fam >= 0 && j != kNoCol) fams.at((size_t)fam).use.at(j) |= use;
+  }
+  static std::string col_macro(const char* what, uint32_t f, uint32_t j) {
+    return std::string("KVC_") + what + "_" + std::to_string(f) + "_" + std::to_string(j);
+  }
   std::vector<Fam> fams;
   std::map<std::string, uint32_t> fam_of;  // family array expr -> family
   static constexpr uint32_t kNoCol = 0xFFFFFFFFu;
@@ -140,6 +158,7 @@ struct Gen {
     const uint32_t j = (uint32_t)F.steps.size();
     F.idx.emplace(rel, j);
     F.steps.push_back(st);
+    F.use.push_back(0u);
     return j;
   }
   // family of the elements of array expr `arr` (a root path); its column 0 is the element itself
@@ -154,24 +173,73 @@ struct Gen {
     fam_of.emplace(arr, f);
     return f;
   }
-  // the plan (JitImage::cols / fam_*) and the macro block of the kernel programs
+  // the plan (JitImage::cols / fam_*) and the macro block of the kernel programs: per family
+  // the words of a row (KVC_W<f>), per column its load from the row at word `b` (KVC_LD), the
+  // node index of a map cell (KVC_IX) and the table word of a leaf on it (KVC_LW)
   void col_plan(JitImage* out, std::string* defs) const {
     out->cols.clear();
     out->fam_arr.clear();
     out->fam_ncols.clear();
+    out->fam_nw.clear();
+    out->fam_nb.clear();
+    out->fam_nn.clear();
+    out->col_use.clear();
     std::ostringstream d;
     for (uint32_t f = 0; f < fams.size(); f++) {
       const Fam& F = fams[f];
       out->fam_arr.push_back(f ? fams[0].idx.at(F.arr) : 0u);  // (family 0 columns come first)
       out->fam_ncols.push_back((uint32_t)F.steps.size());
-      d << "#define KVC_J" << f << " " << F.steps.size() << "u\n";
+      std::vector<uint32_t> use(F.steps.size(), 0u);
+      for (const auto& kv : F.idx) {
+        const std::string key = F.arr + "|" + kv.first;
+        uint32_t u = F.use[kv.second];
+        auto it = use_seed.find(key);
+        if (it != use_seed.end()) u |= it->second;
+        if (f == 0 && fam_of.count(kv.first)) u |= CU_WIDE | CU_B;  // a family array: a, b, c
+        use[kv.second] = u;
+        out->col_use[key] = u;
+      }
+      uint32_t nw = 0, nb = 0, nn = 0;
+      const size_t c0 = out->cols.size();
       for (uint32_t j = 0; j < F.steps.size(); j++) {
         ColDesc c{};
         c.fam = f;
         c.j = j;
         c.nsteps = (uint32_t)F.steps[j].size();
         for (uint32_t s = 0; s < c.nsteps; s++) c.steps[s] = F.steps[j][s];
+        if (narrow_on && !(use[j] & CU_WIDE)) {
+          c.fmt = KV_COLF_NARROW;
+          c.pos = nn++;
+        } else {
+          c.pos = nw++;
+          c.fmt = KV_COLF_WIDE;
+          if (use[j] & (CU_B | CU_LEAF)) {
+            c.fmt = KV_COLF_WIDEB;
+            c.bpos = nb++;
+          }
+        }
         out->cols.push_back(c);
+      }
+      out->fam_nw.push_back(nw);
+      out->fam_nb.push_back(nb);
+      out->fam_nn.push_back(nn);
+      d << "#define KVC_W" << f << " " << (3u * nw + nb + nn) * KV_LANES << "u\n";
+      for (uint32_t j = 0; j < F.steps.size(); j++) {
+        const ColDesc& c = out->cols[c0 + j];
+        d << "#define " << col_macro("LD", f, j) << "(b) ";
+        if (c.fmt == KV_COLF_NARROW) {
+          d << "kv_ldn(PC, (b) + " << u32((3u * nw + nb + c.pos) * KV_LANES) << " + ln_)\n"
+            << "#define " << col_macro("IX", f, j) << "(n) (node_type((n).kt) == NT_MAP ? KV_NARROW_IDX : 0u)\n"
+            << "#define " << col_macro("LW", f, j) << "(n, w) kv_leaf_word_n(P, N, n, w)\n";
+        } else {
+          if (c.fmt == KV_COLF_WIDEB)
+            d << "kv_ldwb(PC, (b) + " << u32(c.pos * 3u * KV_LANES) << " + 3u * ln_, (b) + "
+              << u32((3u * nw + c.bpos) * KV_LANES) << " + ln_)\n";
+          else
+            d << "kv_ldw(PC, (b) + " << u32(c.pos * 3u * KV_LANES) << " + 3u * ln_)\n";
+          d << "#define " << col_macro("IX", f, j) << "(n) (node_type((n).kt) == NT_MAP ? (n).c : 0u)\n"
+            << "#define " << col_macro("LW", f, j) << "(n, w) kv_leaf_word(P, N, n, w)\n";
+        }
       }
     }
     for (uint32_t f = 1; f < fams.size(); f++) out->cols.at(out->fam_arr[f]).arr_fam = f;
@@ -894,7 +962,13 @@ struct Gen {
   // node << 8), loop indices of the raise (ei0..), anchor bitsets when used.
   static constexpr uint32_t FIN = 0x7F000000u, ACT = 0x80000000u;
 
-  struct HVar { std::string idx, node; };  // hoisted cursor: node index var + Node var
+  // hoisted cursor: node index var + Node var, and the path column the node is read from
+  // (fam -1: none). The index var of a column's node is a node index for a map only.
+  struct HVar {
+    std::string idx, node;
+    int fam = -1;
+    uint32_t j = kNoCol;
+  };
   struct HoistTable {
     std::string prefix;
     std::map<std::string, HVar> vars;
@@ -903,7 +977,7 @@ struct Gen {
     size_t flushed = 0;
     uint32_t n = 0;
     // path columns: the family its lookups read (-1: none, walk the node rows), the root token
-    // of its exprs (an element family) and the cell-offset expression of its lane's column 0
+    // of its exprs (an element family) and the word offset of its lane's row in the pool
     int fam = -1;
     std::string troot, cell0;
     std::string flush() {
@@ -918,6 +992,9 @@ struct Gen {
     std::vector<std::pair<uint32_t, uint32_t>> loops;  // stage loops (LOOP_BEGIN pc, LOOP_END pc)
     std::vector<std::string> expr;                      // symbolic cursor per depth ("" = unknown)
     std::vector<HVar> hv;                               // hoisted vars per depth (when expr known)
+    // per depth: the columns whose index var was assigned to the rule's cursor c<d> (a use of the
+    // cursor as a node index makes them all wide)
+    std::vector<std::vector<std::pair<int, uint32_t>>> csrc;
     std::set<uint32_t> resume;                          // resume targets of later segments
     // targets past the segment being emitted, reached without / with a pending error
     std::set<uint32_t> seg_jumps, seg_err_jumps;
@@ -957,13 +1034,16 @@ struct Gen {
     if (j != kNoCol) {
       // the node from its path column (absent: the zero cell); the index only where the
       // lookup's presence (or a map's own index: wildcard keys) is asked for
-      c << "  const Node " << h.node << " = kv_ldc(PC, PCB, " << T.cell0 << " + " << u32(j * KV_LANES) << ");\n"
-        << "  const uint32_t " << h.idx << " = " << h.node << ".kt == 0u ? ABSENT : node_type(" << h.node
-        << ".kt) == NT_MAP ? " << h.node << ".c : 0u;\n";
+      h.fam = T.fam;
+      h.j = j;
+      c << "  const Node " << h.node << " = " << col_macro("LD", (uint32_t)T.fam, j) << "(" << T.cell0 << ");\n"
+        << "  const uint32_t " << h.idx << " = " << h.node << ".kt == 0u ? ABSENT : "
+        << col_macro("IX", (uint32_t)T.fam, j) << "(" << h.node << ");\n";
       T.code.push_back(c.str());
       T.vars.emplace(ex, h);
       return h;
     }
+    col_mark(p.fam, p.j, CU_WIDE | CU_B);  // the walk below reads the parent's a and b
     c << "  uint32_t " << h.idx << " = ABSENT; Node " << h.node << "{0u, 0u, 0u, 0u};\n";
     if (scan) {
       c << "  if (node_type(" << p.node << ".kt) == NT_MAP) for (uint32_t q_ = 0u; q_ < " << p.node << ".b; q_++) { "
@@ -1069,8 +1149,18 @@ struct Gen {
       const std::string& ex = g.expr[d];
       return ex[0] == 'R' || (R.T && ex.compare(0, R.troot.size(), R.troot) == 0);
     };
-    auto NODE = [&](uint32_t d) -> std::string {
-      if (known(d)) return g.hv[d].node;
+    // the cursor c<d> read as a node index: the columns it may come from hold one (wide)
+    auto IDX = [&](uint32_t d) {
+      if (d < g.csrc.size())
+        for (const auto& cj : g.csrc[d]) col_mark(cj.first, cj.second, CU_WIDE);
+    };
+    // the node at depth d; `use`: what is read of it beyond its type (ColUse)
+    auto NODE = [&](uint32_t d, uint32_t use = 0u) -> std::string {
+      if (known(d)) {
+        col_mark(g.hv[d].fam, g.hv[d].j, use);
+        return g.hv[d].node;
+      }
+      IDX(d);
       return "N[" + C(d) + "]";
     };
     auto table_for = [&](uint32_t d) -> HoistTable* {
@@ -1092,10 +1182,12 @@ struct Gen {
           set_unknown(d + 1);
           g.expr[d + 1] = g.expr[d] + (laux ? "/k" : "/s") + std::to_string(a);
           g.hv[d + 1] = h;
+          if (h.fam >= 0) g.csrc.at(d + 1).push_back({h.fam, h.j});
         }
         return h.idx;
       }
       if (assign) set_unknown(d + 1);
+      IDX(d);
       return "lookup_op(N, " + C(d) + ", " + u32(a) + ", " + u32(laux) + ")";
     };
     const std::string ek = "ek" + s;
@@ -1117,6 +1209,7 @@ struct Gen {
           if (known(d)) {
             w << "  if (node_type(" << NODE(d) << ".kt) != " << t << ") ";
           } else {
+            IDX(d);
             w << "  if (" << cd << " == ABSENT || node_type(N[" << cd << "].kt) != " << t << ") ";
           }
           w << raise(op == OP_MAPCHK ? E_TYPE_MAP : E_TYPE_ARR, in.a, in.c) << "\n";
@@ -1151,6 +1244,7 @@ struct Gen {
         case OP_KEYGLOB:
           if (G) throw std::runtime_error("kvjit: KEYGLOB in a rule group");
           set_unknown(d + 1);
+          IDX(d);
           w << "  { uint32_t nd_; if (!keyglob_op(P, B, N, " << cd << ", " << u32(in.op) << ", " << u32(in.a) << ", "
             << u32(in.c) << ", &nd_, &kn" << s << ")) " << jump(in.b) << " " << cn << " = nd_; }\n";
           break;
@@ -1178,6 +1272,7 @@ struct Gen {
           if (known(d + 1)) {
             w << "  if (node_type(" << NODE(d + 1) << ".kt) == NT_NULL) ";
           } else {
+            IDX(d + 1);
             w << "  if (" << cn << " == ABSENT || node_type(N[" << cn << "].kt) == NT_NULL) ";
           }
           w << raise(E_STAR, in.b, in.c) << "\n";
@@ -1191,11 +1286,17 @@ struct Gen {
           HoistTable* T = known(d) ? table_for(d) : nullptr;
           std::string wx;
           if (T) {
-            const std::string hn = g.hv[d].node;
+            const HVar& hvd = g.hv[d];
+            const std::string hn = hvd.node;
             wx = hn + "_w" + std::to_string(word);
+            col_mark(hvd.fam, hvd.j, CU_LEAF);
             if (T->words.insert(wx).second)
-              T->code.push_back("  const uint32_t " + wx + " = kv_leaf_word(P, N, " + hn + ", " + u32(word) + ");\n");
+              T->code.push_back("  const uint32_t " + wx + " = " +
+                                (hvd.fam >= 0 ? col_macro("LW", (uint32_t)hvd.fam, hvd.j) + "(" + hn + ", "
+                                              : "kv_leaf_word(P, N, " + hn + ", ") +
+                                u32(word) + ");\n");
           } else {
+            IDX(d);
             wx = "kv_leaf_word(P, N, (" + cd + " != ABSENT ? N[" + cd + "] : Node{0u, 0u, 0u, 0u}), " + u32(word) + ")";
           }
           if (G) {
@@ -1214,8 +1315,11 @@ struct Gen {
         }
         case OP_VLEAF:  // pattern variables: the resource's substituted value (kvvars.cpp)
           if (G) throw std::runtime_error("kvjit: VLEAF in a rule group");
-          if (known(d)) w << "  { const Node vn_ = " << NODE(d) << ";\n";
-          else w << "  { Node vn_{0u, 0u, 0u, 0u}; if (" << cd << " != ABSENT) vn_ = N[" << cd << "];\n";
+          if (known(d)) w << "  { const Node vn_ = " << NODE(d, CU_WIDE | CU_B) << ";\n";
+          else {
+            IDX(d);
+            w << "  { Node vn_{0u, 0u, 0u, 0u}; if (" << cd << " != ABSENT) vn_ = N[" << cd << "];\n";
+          }
           dleaf_fn();
           w << "    if (!g_dleaf_0(B, N, B.dleaf[(size_t)" << u32(in.a) << " * n_res + r], vn_)) "
             << raise(E_VALUE, in.b, in.c) << " }\n";
@@ -1227,17 +1331,18 @@ struct Gen {
           if (known(d)) {
             w << "  if (node_type(" << NODE(d) << ".kt) != NT_ARR) ";
           } else {
+            IDX(d);
             w << "  if (" << cd << " == ABSENT || node_type(N[" << cd << "].kt) != NT_ARR) ";
           }
           w << raise(E_EXIST_RESTYPE, in.a, in.c) << "\n";
           break;
         case OP_LENCHK:
-          w << "  if (" << NODE(d) << ".b < " << u32(in.a) << ") " << raise(E_LEN, in.b, in.c) << "\n";
+          w << "  if (" << NODE(d, CU_WIDE | CU_B) << ".b < " << u32(in.a) << ") " << raise(E_LEN, in.b, in.c) << "\n";
           if (known(d)) {
           }
           break;
         case OP_INDEX:
-          w << "  " << cn << " = ni(" << NODE(d) << ".a + " << u32(in.a) << ");\n";
+          w << "  " << cn << " = ni(" << NODE(d, CU_WIDE) << ".a + " << u32(in.a) << ");\n";
           if (known(d)) {
           }
           set_unknown(d + 1);
@@ -1252,7 +1357,7 @@ struct Gen {
         case OP_EXIST_BEGIN:
           if (G && op == OP_EXIST_BEGIN) throw std::runtime_error("kvjit: EXIST in a rule group");
           set_unknown(d + 1);
-          w << "  { const Node an_ = " << NODE(d) << "; lf" << L_lv << s << " = an_.a; ll" << L_lv << s << " = an_.b; li"
+          w << "  { const Node an_ = " << NODE(d, CU_WIDE | CU_B) << "; lf" << L_lv << s << " = an_.a; ll" << L_lv << s << " = an_.b; li"
             << L_lv << s << " = 0u;\n    if (an_.b == 0u) ";
           if (op == OP_LOOP_BEGIN) w << jump(in.a + 1);
           else w << raise(E_EXIST_FAIL, in.b, in.c);
@@ -1334,8 +1439,9 @@ struct Gen {
     }
     g.expr.assign(g.maxd + 1, "");
     g.hv.assign(g.maxd + 1, HVar{});
+    g.csrc.assign(g.maxd + 2, {});
     g.expr[0] = "R";
-    g.hv[0] = HVar{"root", "rootn"};
+    g.hv[0] = HVar{"root", "rootn", 0, 0u};
     return g;
   }
 
@@ -1539,7 +1645,7 @@ struct Gen {
     HoistTable global;
     global.prefix = "g";
     global.fam = 0;
-    global.cell0 = "gc_";
+    global.cell0 = "gw_";
     gT = &global;
     size_t K = 0;
     for (uint32_t q = 0; q < nr; q++) {
@@ -1823,6 +1929,11 @@ struct Gen {
         const RGen& g0 = *grp[0];
         const uint32_t d0 = (ps.prog[g0.loops[k].first].op >> 8) & 0xFF;
         const std::string arr_node = key[0] == 'U' ? "N[c" + std::to_string(d0) + g0.s + "]" : g0.hv[d0].node;
+        if (key[0] == 'U') {
+          for (const auto& cj : g0.csrc.at(d0)) col_mark(cj.first, cj.second, CU_WIDE);
+        } else {
+          col_mark(g0.hv[d0].fam, g0.hv[d0].j, CU_WIDE | CU_B);  // an_.a / .b / .c below
+        }
         HoistTable T;
         T.prefix = "l" + tag + "_";
         const std::string troot = "E" + tag;
@@ -1841,7 +1952,7 @@ struct Gen {
           const uint32_t lb = g.loops[k].first, le = g.loops[k].second;
           const uint32_t d = (ps.prog[lb].op >> 8) & 0xFF;
           g.expr[d + 1] = troot;
-          g.hv[d + 1] = HVar{"el" + tag, "eln" + tag};
+          g.hv[d + 1] = HVar{"el" + tag, "eln" + tag, fam != kNoCol ? (int)fam : -1, fam != kNoCol ? 0u : kNoCol};
           Region R;
           R.kind = 1;
           R.rb = lb + 1;
@@ -1896,8 +2007,8 @@ struct Gen {
         body << "    for (uint32_t fli" << tag << " = 0u; fli" << tag << " < fn" << tag << "; fli" << tag << "++) {\n"
              << "      const uint32_t el" << tag << " = ni(ff" << tag << " + fli" << tag << ");\n";
         if (fam != kNoCol)  // the element's column-0 cell: element row fe + i of its family
-          body << "      const uint32_t ec" << tag << " = fe" << tag << " + fli" << tag << " * (KVC_J" << fam
-               << " * " << u32(KV_LANES) << ") + ln_;\n      const Node eln" << tag << " = kv_ldc(PC, PCB, ec" << tag << ");\n";
+          body << "      const uint32_t ec" << tag << " = fe" << tag << " + fli" << tag << " * KVC_W" << fam
+               << ";\n      const Node eln" << tag << " = " << col_macro("LD", fam, 0) << "(ec" << tag << ");\n";
         else
           body << "      const Node eln" << tag << " = N[el" << tag << "];\n";
         body << T.flush() << bodies.str() << "    }\n";
@@ -2019,9 +2130,9 @@ struct Gen {
       << "  if (valid) { root = ni(kv_gld(&R->root, 0)); rkind = kv_gld(&R->kind, 0); rflags = kv_gld(&R->flags, 0); rtup = kv_gld(&R->tup, 0); }\n"
       << "  Node rootn{0u, 0u, 0u, 0u};\n";
     // path columns (kvdevtypes.h): cell offset of this lane's family-0 columns; column 0 = the root
-    o << "  const uint32_t* __restrict__ PC = B.pcol;\n  const uint32_t* __restrict__ PCB = B.pcolb;\n"
-        << "  const uint32_t ln_ = threadIdx.x & " << u32(KV_LANES - 1) << ", gc_ = (r >> 6) * (KVC_J0 * " << u32(KV_LANES)
-        << ") + ln_;\n  if (valid) rootn = kv_ldc(PC, PCB, gc_);\n";
+    o << "  const uint32_t* __restrict__ PC = B.pcol;\n"
+        << "  const uint32_t ln_ = threadIdx.x & " << u32(KV_LANES - 1) << ", gw_ = (r >> 6) * KVC_W0;\n"
+        << "  if (valid) rootn = " << col_macro("LD", 0, 0) << "(gw_);\n";
     o
       << "  const uint32_t* __restrict__ mtr_ = P.mtup + rtup;\n  const uint32_t ntup_ = B.n_tup;\n"
       << "  uint8_t* s_w = (uint8_t*)s_stw;\n"
@@ -2278,6 +2389,7 @@ uint32_t jit_chunk_rules() {
 void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
   auto t0 = std::chrono::steady_clock::now();
   Gen g(ps);
+  g.use_seed = out->col_use;
   // KVGPU_JIT_DIAG=A,B: diagnostics-only kernel variants (#define KV_DIAG_A ... ahead of the
   // prelude; their results are wrong)
   std::string diag;
@@ -2365,7 +2477,7 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
   out->gs_desc = g.gs_desc;
   out->gs_mem = g.gs_mem;
   out->gs_members = g.gs_members;
-  std::string cdefs;  // the column count of every path-column family (KVC_J<f>)
+  std::string cdefs;  // the row words of every path-column family and the macros of every column
   g.col_plan(out, &cdefs);
 
   out->memo_preds.clear();
@@ -2776,6 +2888,7 @@ void jit_refine_blocks(const PolicySet& ps, uint32_t chunk_rules, JitImage* img)
   for (int round = 0; round < 12; round++) {
     JitImage probe;
     probe.probe = true;
+    probe.col_use = img->col_use;
     std::vector<std::pair<size_t, size_t>> at;  // (kernel, block) of each probe
     for (size_t k = 0; k < img->plan.size(); k++) {
       const JitKernelPlan& kp = img->plan[k];

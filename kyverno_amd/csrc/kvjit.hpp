@@ -5,6 +5,7 @@
 // and compiled for gfx950 with hiprtc when the policy set is compiled.
 #pragma once
 #include <cstdint>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -60,6 +61,13 @@ struct JitImage {
   // column; per family its array's column in family 0 and its column count
   std::vector<kv::ColDesc> cols;
   std::vector<uint32_t> fam_arr, fam_ncols;
+  // per family its wide columns, those of them with a b plane, and its narrow columns (cell
+  // formats: kvdevtypes.h ColFmt; KVGPU_JIT_NARROW=0 at generation: every column wide)
+  std::vector<uint32_t> fam_nw, fam_nb, fam_nn;
+  // what the kernels read of each column ("<family array path>|<relative path>" -> use bits,
+  // kvjit.cpp Gen::ColUse): the formats follow from the uses of every rule of the policy set, so
+  // an image that generates only some rules (a block probe) is seeded with the whole image's
+  std::map<std::string, uint32_t> col_use;
   bool probe = false;      // a block-probe image (jit_refine_blocks): rule kernels only
   double gen_ms = 0, compile_ms = 0;
   // Output-mode variants (jit_compile_variants): the final plan's rule kernels compiled once more

@@ -40,7 +40,9 @@ extern "C" void kvemu_mtab(const DevPS* P, const DevBatch* B, uint32_t words, ui
                            uint32_t* an, uint32_t* sl);
 
 std::vector<uint32_t> kvemu_pcol(const DevBatch* B, const std::vector<ColDesc>& cols, const std::vector<uint32_t>& fam_arr,
-                             const std::vector<uint32_t>& fam_ncols, std::vector<uint32_t>* erow);
+                                 const std::vector<uint32_t>& fam_ncols, const std::vector<uint32_t>& fam_nw,
+                                 const std::vector<uint32_t>& fam_nb, const std::vector<uint32_t>& fam_nn,
+                                 std::vector<uint32_t>* erow);
 typedef void (*ptab_fn)(const DevPS*, const Val*, const uint8_t*, uint32_t, uint32_t*);
 extern "C" void kvemu_mfac(const DevPS* P, const DevBatch* B, uint32_t* mtup);
 typedef void (*chunk_fn)(const DevPS*, const DevBatch*, const Node*, const Val*, const uint8_t*, DevOut, uint32_t);
@@ -221,11 +223,11 @@ int main(int argc, char** argv) {
     B.dyn_st = dyn.dyn_st.data();
     // path columns of the image (as dev_batch: built once per batch)
     std::vector<uint32_t> pcol_erow;
-    std::vector<uint32_t> pcol;  // two planes (kvcol.h col_put)
+    std::vector<uint32_t> pcol;  // rows by cell format (kvcol.h col_put)
     if (!img.cols.empty() && B.n_res) {
-      pcol = kvemu_pcol(&B, img.cols, img.fam_arr, img.fam_ncols, &pcol_erow);
+      if (NV + KV_PTAB_PSEUDO >= (1ull << KV_COL_PAYLOAD)) throw std::runtime_error("kvemu: more than 2^28 distinct values");
+      pcol = kvemu_pcol(&B, img.cols, img.fam_arr, img.fam_ncols, img.fam_nw, img.fam_nb, img.fam_nn, &pcol_erow);
       B.pcol = pcol.data();
-      B.pcolb = pcol.data() + pcol.size() / 4 * 3;
     }
     // match tables (as kv_session: one allocation, three [word][entity] tables)
     P.mt_ns_words = (ps.n_nss_bits + 31) / 32;

@@ -29,7 +29,9 @@ extern "C" void kvemu_mfac(const DevPS* P, const DevBatch* B, uint32_t* mtup) {
 // the element rows of every wave group and family (max over the group's lanes, exclusive
 // prefix), the families' offsets, then the element columns; returns the pool
 std::vector<uint32_t> kvemu_pcol(const DevBatch* B, const std::vector<ColDesc>& cols, const std::vector<uint32_t>& fam_arr,
-                             const std::vector<uint32_t>& fam_ncols, std::vector<uint32_t>* erow) {
+                                 const std::vector<uint32_t>& fam_ncols, const std::vector<uint32_t>& fam_nw,
+                                 const std::vector<uint32_t>& fam_nb, const std::vector<uint32_t>& fam_nn,
+                                 std::vector<uint32_t>* erow) {
   const uint32_t nf = (uint32_t)fam_ncols.size(), j0 = fam_ncols.at(0);
   const uint32_t groups = (uint32_t)((B->n_res + KV_WG - 1) / KV_WG * (KV_WG / KV_LANES));
   erow->assign((size_t)std::max<uint32_t>(1u, nf - 1) * (groups + 1), 0u);
@@ -37,6 +39,9 @@ std::vector<uint32_t> kvemu_pcol(const DevBatch* B, const std::vector<ColDesc>& 
   for (uint32_t f = 0; f < nf; f++) {
     fams[f].arr_col = fam_arr[f];
     fams[f].ncols = fam_ncols[f];
+    fams[f].nw = fam_nw.at(f);
+    fams[f].nb = fam_nb.at(f);
+    fams[f].nn = fam_nn.at(f);
     fams[f].erow = f ? erow->data() + (size_t)(f - 1) * (groups + 1) : nullptr;
   }
   for (uint32_t f = 1; f < nf; f++) {
@@ -52,21 +57,20 @@ std::vector<uint32_t> kvemu_pcol(const DevBatch* B, const std::vector<ColDesc>& 
       run += c;
     }
   }
-  uint64_t cells = (uint64_t)groups * j0 * KV_LANES;
+  uint64_t words = (uint64_t)groups * col_row_words(fams[0]);
   for (uint32_t f = 1; f < nf; f++) {
-    fams[f].off_lo = (uint32_t)cells;
-    fams[f].off_hi = (uint32_t)(cells >> 32);
-    cells += (uint64_t)fams[f].erow[groups] * fams[f].ncols * KV_LANES;
+    fams[f].off_lo = (uint32_t)words;
+    fams[f].off_hi = (uint32_t)(words >> 32);
+    words += (uint64_t)fams[f].erow[groups] * col_row_words(fams[f]);
   }
-  if (cells >= (1ull << 32)) throw std::runtime_error("kvemu: more than 2^32 column cells");
-  // two planes: (kt, a, c) 12 B per cell, then b 4 B per cell
-  const uint64_t nc = std::max<uint64_t>(cells, 1);
-  std::vector<uint32_t> pool(4 * nc, 0u);
+  if (words >= (1ull << 32)) throw std::runtime_error("kvemu: more than 2^32 column words");
+  // (exactly the pool's words: a read past a row's end is out of bounds)
+  std::vector<uint32_t> pool(std::max<uint64_t>(words, 1), 0u);
   for (uint32_t c = 0; c < cols.size(); c++)
     for (uint32_t r = 0; r < groups * KV_LANES; r++) {
       threadIdx.x = r % KV_WG;
-      if (c < j0) col_build_root(*B, cols.data(), fams.data(), j0, c, r, pool.data(), nc);
-      else col_build_elem(*B, cols.data(), fams.data(), j0, c, r, pool.data(), nc);
+      if (c < j0) col_build_root(*B, cols.data(), fams.data(), c, r, pool.data());
+      else col_build_elem(*B, cols.data(), fams.data(), c, r, pool.data());
     }
   return pool;
 }
