@@ -87,6 +87,14 @@ int kv_policyset_jit_info(const kv_policyset* ps, uint32_t* n_kernels, double* g
 /* path columns the specialized kernels read, by cell format: wide (12 or 16 bytes a cell) and
  * narrow (4 bytes: presence, type and a scalar's value id) */
 int kv_policyset_jit_cols(const kv_policyset* ps, uint32_t* n_wide, uint32_t* n_narrow);
+/* rule preconditions evaluated on the device: interned condition sets, conditions with a
+ * variable operand, and distinct condition strings of the policy set (any may be NULL) */
+int kv_policyset_cond_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings);
+/* Evaluates one already-substituted condition {"key":..., "operator":..., "value":...} as
+ * variables.Evaluate does (pkg/engine/variables/evaluate.go:11-18, operator/*.go), numbers as
+ * float64: *result = 0 or 1. KV_E_RANGE when an operand is outside the device scope (a map, a
+ * list key, the deprecated Duration* operators), KV_E_PARSE for bad JSON. Needs no GPU. */
+int kv_condition_eval(const char* condition_json, size_t len, int* result);
 int kv_rule_info_get(const kv_policyset* ps, uint32_t rule, kv_rule_info* out);
 
 /* Ingest resources (JSON array or NDJSON of unstructured objects; numbers typed
@@ -144,7 +152,9 @@ int kv_device_pool_limit(uint64_t bytes);
 int kv_device_trim(int device);
 /* phase i of the kv_validate that produced r: its name ("upload", "setup", "pass", "host_alloc",
  * "status_d2h", "records_count", "records_scatter_d2h", ...) and wall-clock milliseconds;
- * KV_E_RANGE past the last phase. Diagnostics of the host boundary (no reference counterpart). */
+ * KV_E_RANGE past the last phase. Diagnostics of the host boundary (no reference counterpart).
+ * "precond" (policy sets with device-evaluated preconditions): the HIP-event time of the
+ * precondition gate's kernel, which runs once per batch when the batch is uploaded. */
 int kv_result_phase(const kv_result* r, uint32_t i, const char** name, double* ms);
 /* counts[(scope * n_rules + rule) * 8 + status] (KV_MODE_SCOPES) */
 int kv_result_scope_counts(const kv_result* r, const int64_t** counts, uint32_t* n_scopes);
@@ -169,6 +179,12 @@ int kv_result_error_message(const kv_result* r, uint32_t rule, uint64_t res, con
  * 181-189, the reference's processValidationRule -> substitutePatterns) and returns its
  * length; 0 when the pair's status has another cause. */
 int kv_result_subst_error(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
+
+/* Preconditions: when rule `rule` is SKIP on `res` because its preconditions do not hold
+ * (pkg/engine/validation.go:175-184), writes the RuleResponse message "preconditions not met"
+ * and returns its length; 0 when the status has another cause (a conditional-anchor SKIP of the
+ * pattern). Negative codes as kv_result_subst_error. */
+int kv_result_precond_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
 double kv_result_kernel_ms(const kv_result* r);
 
 /* Bulk export of the failing pairs (KV_MODE_ERRORS): every FAIL / ERROR / SKIP pair,

@@ -4,8 +4,14 @@ evaluate every (resource, rule) pair on a MI355X.
 This is the batch form of ``engine.Validate`` (reference
 ``pkg/engine/validation.go:26``): statuses use ``response.RuleStatus`` codes
 (``pkg/engine/response/status.go:14-28``) plus ``NOMATCH`` (no RuleResponse)
-and ``CPU`` (the pair needs the reference CPU engine: context, preconditions,
-deny, foreach or ``{{ }}`` variables).
+and ``CPU`` (the pair needs the reference CPU engine: context, deny, foreach,
+``{{ }}`` variables other than ``request.object`` paths, or preconditions outside
+the device forms). Preconditions that are an ``any`` / ``all`` (or old list) of
+Equal(s), NotEqual(s), the In family and the four numeric comparisons, each with
+``request.object`` variables on one side and a constant scalar or list on the other,
+are evaluated on the device (``kv_precond_kernel``): a pair whose preconditions do
+not hold is ``SKIP`` (``Result.precond_message``), one they cannot decide there (a
+map or array operand) is ``CPU``.
 """
 from __future__ import annotations
 
@@ -24,6 +30,18 @@ STATUS_NAMES = ["pass", "fail", "warn", "error", "skip", "nomatch", "cpu"]
 MODE_STATUS, MODE_ERRORS, MODE_COUNTS, MODE_SCOPES = 1, 2, 4, 8
 COMPILE_SPECIALIZE = 1
 ROUTE_GPU, ROUTE_CPU, ROUTE_NORESPONSE, ROUTE_CONSTANT = range(4)
+
+
+def condition_eval(condition: dict) -> bool:
+    """``variables.Evaluate`` of one already-substituted condition ``{"key", "operator", "value"}``
+    (numbers as float64) by the library's host evaluator (``kv_condition_eval``; no GPU). Raises
+    ``ValueError`` for operands outside the device scope (a map, a list key, Duration* operators)."""
+    raw = json.dumps(condition, ensure_ascii=False).encode("utf-8")
+    out = ctypes.c_int()
+    rc = lib().kv_condition_eval(raw, len(raw), ctypes.byref(out))
+    if rc != 0:
+        raise ValueError(f"kv_condition_eval: code {rc}")
+    return bool(out.value)
 
 
 def _dumps(x) -> bytes:
@@ -94,6 +112,14 @@ class PolicySet:
         lib().kv_policyset_jit_cols(self._h, ctypes.byref(cw), ctypes.byref(cn))
         return {"kernels": nk.value, "gen_ms": g.value, "compile_ms": c.value, "code_bytes": cb.value,
                 "cols_wide": cw.value, "cols_narrow": cn.value}
+
+    @property
+    def precondition_info(self) -> dict:
+        """Preconditions evaluated on the device: interned condition sets, conditions with a
+        variable operand and distinct condition strings (``kv_policyset_cond_sets``)."""
+        s, c, k = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        lib().kv_policyset_cond_sets(self._h, ctypes.byref(s), ctypes.byref(c), ctypes.byref(k))
+        return {"sets": s.value, "conditions": c.value, "strings": k.value}
 
     def policy_rules(self, policy: int) -> list[Rule]:
         return [r for r in self.rules if r.policy == policy]
@@ -226,6 +252,13 @@ class Result:
         if n < 0:
             return None
         return buf.value.decode("utf-8")
+
+    def precond_message(self, rule: int, res: int) -> str | None:
+        """"preconditions not met" for a SKIP pair decided by the rule's preconditions
+        (``kv_result_precond_message``), else None (a conditional-anchor SKIP of the pattern)."""
+        buf = ctypes.create_string_buffer(64)
+        n = lib().kv_result_precond_message(self._h, rule, res, buf, 64)
+        return buf.raw[:n].decode("utf-8") if n > 0 else None
 
     def subst_error(self, rule: int, res: int) -> str | None:
         """The RuleResponse message of an ERROR pair caused by the pattern's variables failing to

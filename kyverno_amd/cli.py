@@ -18,8 +18,10 @@ Evaluation runs on the GPU through the C ABI (``kyverno_amd.batch``): one
 ``kv_validate`` over the whole (rule × resource) cross product instead of the
 reference's per-pair ``engine.Validate`` loop (apply_command.go:270-310). Rules
 the device does not evaluate (variables other than ``request.object`` paths,
-context, preconditions, deny, foreach — ``KV_ROUTE_CPU``) are reported as routed to the reference engine and
-not counted; a Go host runs them through ``engine.Validate``.
+context, deny, foreach, preconditions outside the device forms — ``KV_ROUTE_CPU``) are reported as
+routed to the reference engine and not counted; preconditions of the device forms (any / all of
+Equals, In, GreaterThan ... conditions on ``request.object`` paths) are evaluated with the rule: a
+pair whose preconditions do not hold is `skip`, "preconditions not met"; a Go host runs them through ``engine.Validate``.
 
     python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N]
     python -m kyverno_amd test test/cli/test/simple
@@ -100,6 +102,7 @@ class Evaluation:
     paths: dict = field(default_factory=dict)   # (rule, res) -> failing path (FAIL pairs)
     errors: dict = field(default_factory=dict)  # (rule, res) -> err.Error() of ERROR / SKIP pairs
     subst: dict = field(default_factory=dict)   # (rule, res) -> message of a pattern-variable substitution ERROR
+    precond: dict = field(default_factory=dict)  # (rule, res) -> message of a SKIP decided by the preconditions
     anypattern: dict = field(default_factory=dict)  # (rule, res) -> [(status, path)] per pattern
     warnings: list = field(default_factory=list)    # host-side limits met while rendering messages
 
@@ -130,14 +133,19 @@ def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messa
 
 
 def collect_errors(ev: Evaluation, ps, r, resources: list) -> None:
-    """Messages of the ERROR / SKIP pairs: pattern-variable substitution errors (whole message),
-    else the pattern error's err.Error() (pattern rules; anyPattern rules render per pattern)."""
+    """Messages of the ERROR / SKIP pairs: pattern-variable substitution errors and preconditions
+    that do not hold (whole message), else the pattern error's err.Error() (pattern rules; anyPattern rules render per pattern)."""
     for ri, res in zip(*np.nonzero((r.status == ERROR) | (r.status == SKIP))):
         key = (int(ri), int(res))
         if r.status[ri, res] == ERROR:
             m = r.subst_error(*key)
             if m is not None:
                 ev.subst[key] = m
+                continue
+        else:
+            m = r.precond_message(*key)
+            if m is not None:
+                ev.precond[key] = m
                 continue
         if not ps.rules[ri].any_pattern:
             m = r.error_message(int(ri), int(res), resources[int(res)])
@@ -214,6 +222,8 @@ def rule_message(ev: Evaluation, rule, res: int) -> str:
     st = int(ev.status[rule.index, res])
     if st == ERROR and (rule.index, res) in ev.subst:  # ruleError("variable substitution failed", err)
         return ev.subst[(rule.index, res)]
+    if st == SKIP and (rule.index, res) in ev.precond:  # "preconditions not met" (validation.go:183-184)
+        return ev.precond[(rule.index, res)]
     if rule.any_pattern:
         outs = ev.anypattern.get((rule.index, res), [])
         if st == PASS:

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/kvgpu.h"
+#include "kvcond.h"
 #include "kvdev.h"
 #include "kvinternal.hpp"
 #include "kvjit.hpp"
@@ -394,6 +395,10 @@ struct DevBatchRes {
   // families and their per-group element-row prefixes; build time and pool size
   DevBuf pcol, pcold, pfam, perow;
   double pcol_ms = 0;
+  // preconditions (kvcond.h): the gate's tables and the plane kv_precond_kernel wrote; its
+  // HIP-event time
+  DevBuf presets, preents, preoutc, pretruth, preunk, prest;
+  double pre_ms = 0;
   DevBatch view{};
 };
 
@@ -418,6 +423,12 @@ struct kv_batch {
   const DynHost& dyn_host(const PolicySet& ps) {
     std::call_once(dyn_once, [&]() { build_dyn(ps, b, &dyn); });
     return dyn;
+  }
+  std::once_flag pre_once;
+  PreHost pre;  // precondition tables (build_pre), on first use by the host accessors
+  const PreHost& pre_host(const PolicySet& ps) {
+    std::call_once(pre_once, [&]() { build_pre(ps, b, &pre); });
+    return pre;
   }
   // caller index -> store index (the inverse of Batch::order), on first use; null: identity
   std::once_flag inv_once;
@@ -1125,8 +1136,49 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     v.dleaf = (const uint32_t*)d->dleaf.p;
     v.dyn_st = (const uint8_t*)d->dynst.p;
   }
+  // preconditions: the gate's tables go on the upload stream (no blocking copy; `pre` lives until
+  // the stream is drained below), the kernel behind them
+  PreHost pre;
+  const uint32_t n_sets = (uint32_t)ps.csets.size();
+  if (n_sets && !b.res.empty()) {
+    build_pre(ps, b, &pre);
+    auto up = [&](DevBuf& buf, const std::vector<uint32_t>& src) {
+      buf.alloc(std::max<size_t>(src.size() * sizeof(uint32_t), 16), device);
+      if (!src.empty())
+        HIPCHK(hipMemcpyAsync(buf.p, src.data(), src.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us));
+    };
+    up(d->presets, pre.sets);
+    up(d->preents, pre.ents);
+    up(d->preoutc, pre.outc);
+    up(d->pretruth, pre.truth);
+    up(d->preunk, pre.unk);
+    d->prest.alloc((size_t)n_sets * b.res.size(), device);
+    v.pre_sets = (const uint32_t*)d->presets.p;
+    v.pre_ents = (const uint32_t*)d->preents.p;
+    v.pre_outc = (const uint32_t*)d->preoutc.p;
+    v.pre_truth = (const uint32_t*)d->pretruth.p;
+    v.pre_unk = (const uint32_t*)d->preunk.p;
+    v.pre_words = pre.words;
+    v.n_pre_sets = n_sets;
+    v.pre_st = (const uint8_t*)d->prest.p;
+  }
   d->view_dev.upload_raw(&d->view, sizeof(DevBatch), device);
+  hipEvent_t pe0 = nullptr, pe1 = nullptr;
+  if (v.pre_st) {
+    HIPCHK(hipEventCreate(&pe0));
+    HIPCHK(hipEventCreate(&pe1));
+    HIPCHK(hipEventRecord(pe0, us));
+    HIPCHK(launch_precond((const DevBatch*)d->view_dev.p, v.n_res, n_sets, (uint8_t*)d->prest.p, us));
+    HIPCHK(hipEventRecord(pe1, us));
+  }
   HIPCHK(hipStreamSynchronize(us));
+  if (pe0) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, pe0, pe1));
+    d->pre_ms = ms;
+    (void)hipEventDestroy(pe0);
+    (void)hipEventDestroy(pe1);
+  }
   StreamPool::get().give(device, hipStreamNonBlocking, us);
   pc.release();
   rm.release();
@@ -2310,6 +2362,9 @@ void run(kv_policyset* ps, kv_batch* bt, const char* ctx_json, const std::vector
     auto d = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const double up = s.parts.empty() ? 0.0 : s.parts[0]->upload_ms;
     out->phases = {{"upload", up}, {"setup", d(t0, t1) - up}, {"pass", d(t1, t2)}};
+    // the precondition gate's kernel (HIP events; it ran when the batch was first uploaded)
+    if (!ps->ps.csets.empty() && !s.parts.empty() && s.parts[0]->batch_ref)
+      out->phases.push_back({"precond", s.parts[0]->batch_ref->pre_ms});
     s.fetch(out, t);
   }
   if (getenv("KVGPU_VERBOSE")) {  // host-boundary breakdown
@@ -2721,6 +2776,66 @@ int kv_result_subst_error(const kv_result* r, uint32_t rule, uint64_t res, char*
   }
 }
 
+int kv_result_precond_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
+  if (!r) return KV_E_INVALID;
+  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
+  if (!r->has_status()) return KV_E_INVALID;  // counts-only result: no statuses were fetched
+  const uint64_t s = r->store_of(res);          // (the batch's tables are in store order)
+  res = r->sidx(res);
+  try {
+    const RuleRec& rr = r->ps->ps.rules[rule];
+    if (!rr.pre || const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res] != ST_SKIP) return 0;
+    const ResultPart* p = r->part_of(s);
+    if (!p) return 0;
+    kv_batch* kb = p->shard ? p->shard.get() : const_cast<kv_batch*>(r->b);
+    const PreHost& h = kb->pre_host(r->ps->ps);
+    // the pair recomputed from the batch's tables: a SKIP of the pattern's condition anchors has
+    // another cause
+    if (pre_status_host(h, rr.pre - 1, kb->b.res.size(), s - p->lo) != ST_SKIP) return 0;
+    // ruleResponse(rule, Validation, "preconditions not met", RuleStatusSkip) (validation.go:183-184)
+    static const std::string m = "preconditions not met";
+    if (buf && cap) {
+      size_t n = std::min(cap - 1, m.size());
+      memcpy(buf, m.data(), n);
+      buf[n] = 0;
+    }
+    return (int)m.size();
+  } catch (const std::exception&) {
+    return KV_E_INVALID;
+  }
+}
+
+int kv_condition_eval(const char* condition_json, size_t len, int* result) {
+  if (!condition_json || !result) return KV_E_INVALID;
+  try {
+    JDoc d;
+    parse_json(condition_json, len, NUM_FLOAT, &d);
+    if (d.at(d.root).t != J_MAP) return KV_E_PARSE;
+    const int64_t kn = d.get(d.root, "key"), on = d.get(d.root, "operator"), vn = d.get(d.root, "value");
+    std::string op;
+    if (on >= 0) {
+      if (d.at((uint32_t)on).t != J_STR) return KV_E_PARSE;  // (json: cannot unmarshal into ConditionOperator)
+      op = std::string(d.sval(d.at((uint32_t)on)));
+    }
+    const PV key = kn >= 0 ? to_pv(d, (uint32_t)kn) : PV{}, value = vn >= 0 ? to_pv(d, (uint32_t)vn) : PV{};
+    bool range = false;
+    const bool v = cond_eval(cond_op(op), key, value, &range);
+    if (range) return KV_E_RANGE;
+    *result = v ? 1 : 0;
+    return 0;
+  } catch (const std::exception&) {
+    return KV_E_PARSE;
+  }
+}
+
+int kv_policyset_cond_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings) {
+  if (!ps) return KV_E_INVALID;
+  if (sets) *sets = (uint32_t)ps->ps.csets.size();
+  if (conditions) *conditions = (uint32_t)ps->ps.conds.size();
+  if (strings) *strings = (uint32_t)ps->ps.ckeys.size();
+  return 0;
+}
+
 double kv_result_kernel_ms(const kv_result* r) { return r ? r->kernel_ms : -1.0; }
 
 int kv_result_failures(const kv_result* cr, uint64_t* n, const uint32_t** rule, const uint64_t** res,
@@ -2789,7 +2904,9 @@ int kv_result_failures(const kv_result* cr, uint64_t* n, const uint32_t** rule, 
         std::vector<std::thread> th;
         for (unsigned t = 0; t < T; t++)
           th.emplace_back([&, t]() {
-            std::vector<uint32_t> slot;  // caller index -> path id + 1 (0: no pair)
+            // caller index -> path id + 1 (0: no pair; 64-bit: KV_PATH_NONE + 1 of an ERROR / SKIP
+            // pair must not wrap to "no pair")
+            std::vector<uint64_t> slot;
             for (uint32_t rl = t; rl < r->n_rules; rl += T) {
               if (rb[rl] == rb[rl + 1]) continue;
               if ((rb[rl + 1] - rb[rl]) * 16u < r->n_res) {
@@ -2803,14 +2920,14 @@ int kv_result_failures(const kv_result* cr, uint64_t* n, const uint32_t** rule, 
                 }
                 continue;
               }
-              if (slot.empty()) slot.assign(r->n_res, 0u);
-              for (size_t i = rb[rl]; i < rb[rl + 1]; i++) slot[r->f_res[i]] = r->f_path[i] + 1u;
+              if (slot.empty()) slot.assign(r->n_res, 0ull);
+              for (size_t i = rb[rl]; i < rb[rl + 1]; i++) slot[r->f_res[i]] = (uint64_t)r->f_path[i] + 1ull;
               size_t o = rb[rl];
               for (uint64_t j = 0; j < r->n_res && o < rb[rl + 1]; j++)
                 if (slot[j]) {
                   fs[o] = j;
-                  fp[o++] = slot[j] - 1u;
-                  slot[j] = 0u;
+                  fp[o++] = (uint32_t)(slot[j] - 1ull);
+                  slot[j] = 0ull;
                 }
             }
           });

@@ -21,6 +21,7 @@
 #include <set>
 #include <stdexcept>
 
+#include "kvcond.h"
 #include "kvinternal.hpp"
 
 namespace kvh {
@@ -1468,11 +1469,17 @@ void compile_policies(const char* json, size_t len, PolicySet* ps) {
         int64_t ctx = d.get(rn, "context"), pre = d.get(rn, "preconditions");
         bool ctxP = ctx >= 0 && d.at((uint32_t)ctx).t == J_ARR && d.at((uint32_t)ctx).count > 0;
         bool preP = pre >= 0 && d.at((uint32_t)pre).t != J_NULL;
+        uint32_t pre_set = 0;
         rr.route = 0;
         if (!has_validate) { rr.route = 2; rh.route_reason = "no validate"; }
         else if (feP) { rr.route = 1; rh.route_reason = "foreach"; }
         else if (ctxP) { rr.route = 1; rh.route_reason = "context"; }
-        else if (preP) { rr.route = 1; rh.route_reason = "preconditions"; }
+        // preconditions: evaluated on the device where the block and the rule's pattern are in
+        // scope (kvcond.h); everything else keeps the CPU route and its reason
+        else if (preP && ((!patP && !anyP) || (pre_set = compile_preconditions(*ps, d, (uint32_t)pre)) == 0)) {
+          rr.route = 1;
+          rh.route_reason = "preconditions";
+        }
         else if (!patP && !anyP) {
           if (denyP) { rr.route = 1; rh.route_reason = "deny"; }
           else { rr.route = 2; rh.route_reason = "no pattern"; }  // validate() returns nil
@@ -1527,6 +1534,16 @@ void compile_policies(const char* json, size_t len, PolicySet* ps) {
               }
             }
           }
+        }
+        if (preP && pre_set != 0 && rr.route != 0) {
+          // (a pattern that is routed itself, or compiles to a constant status: SKIP-or-constant
+          // is not a form the kernels have)
+          rr.route = 1;
+          rr.const_status = 0;
+          rh.route_reason = "preconditions";
+          rh.const_message.clear();
+        } else if (preP && pre_set != 0xFFFFFFFFu) {
+          rr.pre = pre_set;
         }
         ps->rules.push_back(rr);
         ps->rhost.push_back(rh);

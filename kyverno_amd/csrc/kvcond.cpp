@@ -1,0 +1,576 @@
+// Rule preconditions: Go-exact condition evaluator, compile-time interning, per-batch truth
+// tables (kvcond.h).
+#include "kvcond.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "kvpre.h"
+
+namespace kvh {
+
+using namespace kv;
+
+namespace {
+
+std::string lower(std::string s) {
+  for (char& c : s)
+    if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
+  return s;
+}
+
+// float64 -> int64 conversion of amd64 (CVTTSD2SQ): out of range and NaN give the minimum
+int64_t go_f2i(double f) {
+  if (!(f >= -9223372036854775808.0 && f < 9223372036854775808.0)) return INT64_MIN;
+  return (int64_t)f;
+}
+
+// Duration.Seconds() (time.go): sec + nsec / 1e9
+double dur_seconds(int64_t d) {
+  const int64_t sec = d / 1000000000ll, nsec = d % 1000000000ll;
+  return (double)sec + (double)nsec / 1e9;
+}
+
+// parseDuration (operator.go:80-139): at least one operand is a duration string other than "0";
+// the other one is then a duration string or a number of seconds
+bool parse_durations(const PV& key, const PV& value, double* ks, double* vs) {
+  int64_t kd = 0, vd = 0;
+  const bool kok = key.t == J_STR && key.s != "0" && go_parse_duration(key.s, &kd);
+  const bool vok = value.t == J_STR && value.s != "0" && go_parse_duration(value.s, &vd);
+  if (!kok && !vok) return false;
+  if (!kok) {
+    if (key.t != J_FLOAT) return false;
+    kd = (int64_t)((uint64_t)go_f2i(key.f) * 1000000000ull);  // time.Duration(f) * time.Second (wraps)
+  }
+  if (!vok) {
+    if (value.t != J_FLOAT) return false;
+    vd = (int64_t)((uint64_t)go_f2i(value.f) * 1000000000ull);
+  }
+  *ks = dur_seconds(kd);
+  *vs = dur_seconds(vd);
+  return true;
+}
+
+// Quantity.Cmp of two parsed quantities (the canonical form of gocompat.cpp)
+int qcanon_cmp(const QCanon& a, const QCanon& b) {
+  const int sa = a.zero ? 0 : (a.neg ? -1 : 1), sb = b.zero ? 0 : (b.neg ? -1 : 1);
+  if (sa != sb) return sa < sb ? -1 : 1;
+  if (sa == 0) return 0;
+  int m = 0;
+  if (a.exp != b.exp) m = a.exp < b.exp ? -1 : 1;
+  else if (a.hi != b.hi) m = a.hi < b.hi ? -1 : 1;
+  else if (a.lo != b.lo) m = a.lo < b.lo ? -1 : 1;
+  return sa > 0 ? m : -m;
+}
+
+// compareByCondition (numeric.go:30-52)
+bool cmp_by(uint32_t op, double k, double v) {
+  switch (op) {
+    case CD_GE: return k >= v;
+    case CD_GT: return k > v;
+    case CD_LE: return k <= v;
+    case CD_LT: return k < v;
+    default: return false;
+  }
+}
+
+// EqualHandler / NotEqualHandler (equal.go, notequal.go): `ne` selects the NotEqual results
+bool eval_equal(const PV& key, const PV& value, bool ne) {
+  switch (key.t) {
+    case J_BOOL:  // validateValueWithBoolPattern
+      if (value.t != J_BOOL) return ne;
+      return (key.b == value.b) != ne;
+    case J_FLOAT:  // validateValueWithFloatPattern (a decoded number is never int / int64)
+      if (value.t == J_FLOAT) return (value.f == key.f) != ne;
+      if (value.t == J_STR) {
+        double f;
+        if (!go_parse_float(value.s, &f)) return ne;
+        return (f == key.f) != ne;
+      }
+      return ne;
+    case J_STR: {  // validateValueWithStringPattern: duration, quantity, wildcard
+      double ks, vs;
+      if (parse_durations(key, value, &ks, &vs)) return (ks == vs) != ne;
+      const QCanon qk = parse_quantity(key.s);
+      if (qk.valid && value.t == J_STR) {
+        const QCanon qv = parse_quantity(value.s);
+        if (!qv.valid) return false;  // (both handlers: "parse error", false)
+        return (qcanon_cmp(qk, qv) == 0) != ne;
+      }
+      if (value.t == J_STR) return wildcard_match_host(value.s, key.s) != ne;
+      return ne;
+    }
+    default:  // nil: "Unsupported type", false in both handlers
+      return false;
+  }
+}
+
+bool eval_numeric_float(uint32_t op, double key, const PV& value) {  // numeric.go:100-127
+  if (value.t == J_FLOAT) return cmp_by(op, key, value.f);
+  if (value.t == J_STR) {
+    PV k;
+    k.t = J_FLOAT;
+    k.f = key;
+    double ks, vs;
+    if (parse_durations(k, value, &ks, &vs)) return cmp_by(op, ks, vs);
+    double f;
+    if (go_parse_float(value.s, &f)) return cmp_by(op, key, f);
+    int64_t i;
+    if (go_parse_int(value.s, &i)) return cmp_by(op, key, (double)i);
+    return false;
+  }
+  return false;
+}
+
+bool eval_numeric(uint32_t op, const PV& key, const PV& value) {  // numeric.go:54-168
+  if (key.t == J_FLOAT) return eval_numeric_float(op, key.f, value);
+  if (key.t != J_STR) return false;
+  double ks, vs;
+  if (parse_durations(key, value, &ks, &vs)) return cmp_by(op, ks, vs);
+  double f;
+  if (go_parse_float(key.s, &f)) return eval_numeric_float(op, f, value);
+  int64_t i;
+  if (go_parse_int(key.s, &i)) {  // validateValueWithIntPattern: float64(key) against the value
+    return eval_numeric_float(op, (double)i, value);
+  }
+  const QCanon qk = parse_quantity(key.s);
+  if (qk.valid) {
+    if (value.t != J_STR) return false;
+    const QCanon qv = parse_quantity(value.s);
+    if (!qv.valid) return false;
+    return cmp_by(op, (double)qcanon_cmp(qk, qv), 0.0);
+  }
+  return false;
+}
+
+// fmt.Sprint of a scalar
+bool sprint(const PV& v, std::string* out) {
+  switch (v.t) {
+    case J_NULL: *out = "<nil>"; return true;
+    case J_BOOL: *out = v.b ? "true" : "false"; return true;
+    case J_FLOAT: *out = go_format_g(v.f); return true;
+    case J_STR: *out = v.s; return true;
+    default: return false;
+  }
+}
+
+// json.Unmarshal([]byte(s), &[]string): null is an empty list, a null element ""
+bool json_string_array(const std::string& s, std::vector<std::string>* out) {
+  JDoc d;
+  try {
+    parse_json(s.data(), s.size(), NUM_FLOAT, &d);
+  } catch (const std::exception&) {
+    return false;
+  }
+  const JNode& r = d.at(d.root);
+  if (r.t == J_NULL) return true;
+  if (r.t != J_ARR) return false;
+  for (uint32_t c = r.first; c < r.first + r.count; c++) {
+    const JNode& e = d.at(c);
+    if (e.t == J_STR) out->push_back(std::string(d.sval(e)));
+    else if (e.t == J_NULL) out->push_back("");
+    else return false;
+  }
+  return true;
+}
+
+// keyExistsInArray (in.go:58-94): 0 no, 1 yes, -1 invalid type
+int key_exists(const std::string& key, const PV& value, bool* range) {
+  if (value.t == J_ARR) {
+    for (const PV& e : value.a) {
+      std::string s;
+      if (!sprint(e, &s)) { *range = true; return -1; }
+      if (wildcard_match_host(key, s)) return 1;
+    }
+    return 0;
+  }
+  if (value.t == J_STR) {
+    if (wildcard_match_host(value.s, key)) return 1;
+    std::vector<std::string> arr;
+    if (!json_string_array(value.s, &arr)) return -1;
+    for (const std::string& e : arr)
+      if (e == key) return 1;
+    return 0;
+  }
+  return -1;
+}
+
+}  // namespace
+
+uint32_t cond_op(const std::string& name) {
+  const std::string s = lower(name);
+  if (s == "equal" || s == "equals") return CD_EQ;
+  if (s == "notequal" || s == "notequals") return CD_NE;
+  if (s == "in") return CD_IN;
+  if (s == "anyin") return CD_ANYIN;
+  if (s == "allin") return CD_ALLIN;
+  if (s == "notin") return CD_NOTIN;
+  if (s == "anynotin") return CD_ANYNOTIN;
+  if (s == "allnotin") return CD_ALLNOTIN;
+  if (s == "greaterthanorequals") return CD_GE;
+  if (s == "greaterthan") return CD_GT;
+  if (s == "lessthanorequals") return CD_LE;
+  if (s == "lessthan") return CD_LT;
+  if (s == "durationgreaterthanorequals" || s == "durationgreaterthan" || s == "durationlessthanorequals" ||
+      s == "durationlessthan")
+    return CD_DURATION;
+  return CD_UNKNOWN;
+}
+
+// time.ParseDuration (format.go): [-+]?([0-9]*(\.[0-9]*)?[a-z]+)+, "0" alone is zero
+bool go_parse_duration(const std::string& str, int64_t* out) {
+  size_t i = 0;
+  const size_t n = str.size();
+  bool neg = false;
+  if (n && (str[0] == '-' || str[0] == '+')) {
+    neg = str[0] == '-';
+    i = 1;
+  }
+  if (str.compare(i, std::string::npos, "0") == 0) { *out = 0; return true; }
+  if (i == n) return false;
+  const uint64_t lim = 1ull << 63;
+  uint64_t d = 0;
+  auto digit = [&](size_t k) { return k < n && str[k] >= '0' && str[k] <= '9'; };
+  while (i < n) {
+    uint64_t v = 0, f = 0;
+    double scale = 1.0;
+    if (!(str[i] == '.' || digit(i))) return false;
+    const size_t p0 = i;
+    while (digit(i)) {  // leadingInt
+      if (v > lim / 10) return false;
+      v = v * 10 + (uint64_t)(str[i] - '0');
+      if (v > lim) return false;
+      i++;
+    }
+    const bool pre = i != p0;
+    bool post = false;
+    if (i < n && str[i] == '.') {
+      i++;
+      const size_t p1 = i;
+      bool overflow = false;
+      while (digit(i)) {  // leadingFraction
+        if (!overflow) {
+          if (f > (lim - 1) / 10) overflow = true;
+          else {
+            const uint64_t y = f * 10 + (uint64_t)(str[i] - '0');
+            if (y > lim) overflow = true;
+            else { f = y; scale *= 10; }
+          }
+        }
+        i++;
+      }
+      post = i != p1;
+    }
+    if (!pre && !post) return false;
+    const size_t u0 = i;
+    while (i < n && str[i] != '.' && !digit(i)) i++;
+    if (i == u0) return false;
+    const std::string u = str.substr(u0, i - u0);
+    uint64_t unit;
+    if (u == "ns") unit = 1;
+    else if (u == "us" || u == "\xC2\xB5s" || u == "\xCE\xBCs") unit = 1000;
+    else if (u == "ms") unit = 1000000;
+    else if (u == "s") unit = 1000000000ull;
+    else if (u == "m") unit = 60ull * 1000000000ull;
+    else if (u == "h") unit = 3600ull * 1000000000ull;
+    else return false;
+    if (v > lim / unit) return false;
+    v *= unit;
+    if (f > 0) {
+      v += (uint64_t)((double)f * ((double)unit / scale));
+      if (v > lim) return false;
+    }
+    d += v;
+    if (d > lim) return false;
+  }
+  if (neg) { *out = (int64_t)(0 - d); return true; }
+  if (d > lim - 1) return false;
+  *out = (int64_t)d;
+  return true;
+}
+
+bool cond_eval(uint32_t op, const PV& key, const PV& value, bool* range) {
+  *range = false;
+  if (op == CD_DURATION || key.t == J_MAP || key.t == J_ARR || value.t == J_MAP) {
+    *range = true;
+    return false;
+  }
+  if (value.t == J_ARR)
+    for (const PV& e : value.a)
+      if (e.t == J_MAP || e.t == J_ARR) { *range = true; return false; }
+  switch (op) {
+    case CD_EQ: return eval_equal(key, value, false);
+    case CD_NE: return eval_equal(key, value, true);
+    case CD_GT:
+    case CD_GE:
+    case CD_LT:
+    case CD_LE: return eval_numeric(op, key, value);
+    case CD_IN:
+    case CD_ANYIN:
+    case CD_ALLIN:
+    case CD_NOTIN:
+    case CD_ANYNOTIN:
+    case CD_ALLNOTIN: {
+      // scalar keys (in.go:30-46 and its siblings): a string, or fmt.Sprint of a number; every
+      // other key type is "Unsupported type", false
+      std::string k;
+      if (key.t == J_STR) k = key.s;
+      else if (key.t == J_FLOAT) k = go_format_g(key.f);
+      else return false;
+      const int e = key_exists(k, value, range);
+      if (e < 0) return false;  // invalid type: false in every handler
+      const bool notin = op == CD_NOTIN || op == CD_ANYNOTIN || op == CD_ALLNOTIN;
+      return notin ? e == 0 : e == 1;
+    }
+    default: return false;  // unknown operator: CreateOperatorHandler returns nil (evaluate.go:13-16)
+  }
+}
+
+// ------------------------------------------------------------------ compile
+namespace {
+
+bool has_escape_or_ref(const std::string& s) {
+  return s.find("$(") != std::string::npos || s.find("\\{{") != std::string::npos;
+}
+
+bool tree_has_var(const PV& p) {
+  if (p.t == J_STR) return var_string(p.s) || has_escape_or_ref(p.s);
+  for (const PV& e : p.a)
+    if (tree_has_var(e)) return true;
+  for (size_t i = 0; i < p.mv.size(); i++)
+    if (tree_has_var(p.mv[i]) || var_string(p.mk[i]) || has_escape_or_ref(p.mk[i])) return true;
+  return false;
+}
+
+// a constant operand: a scalar or a list of scalars
+bool const_operand_ok(const PV& p, bool is_key) {
+  if (p.t == J_MAP) return false;
+  if (p.t == J_ARR) {
+    if (is_key) return false;  // (list keys: the set forms of the In family stay on the CPU route)
+    for (const PV& e : p.a)
+      if (e.t == J_MAP || e.t == J_ARR) return false;
+  }
+  return true;
+}
+
+std::string pv_key(const PV& p) {  // interning key of a constant operand
+  switch (p.t) {
+    case J_NULL: return "n";
+    case J_BOOL: return p.b ? "b1" : "b0";
+    case J_FLOAT: { std::string o = "f"; o.append((const char*)&p.f, 8); return o; }
+    case J_STR: return "s" + std::to_string(p.s.size()) + ":" + p.s;
+    default: {
+      std::string o = "[";
+      for (const PV& e : p.a) o += pv_key(e) + ",";
+      return o + "]";
+    }
+  }
+}
+
+// one condition: 0 constant false, 1 constant true, 2 dynamic (*rec), -1 outside the scope
+int compile_condition(PolicySet& ps, const JDoc& d, uint32_t node, uint32_t* rec) {
+  if (d.at(node).t != J_MAP) return -1;
+  const int64_t kn = d.get(node, "key"), on = d.get(node, "operator"), vn = d.get(node, "value");
+  if (kn < 0 || vn < 0) return -1;
+  const JNode& cn = d.at(node);
+  for (uint32_t c = cn.first; c < cn.first + cn.count; c++) {
+    const std::string_view k = d.key(d.at(c));
+    if (k != "key" && k != "operator" && k != "value") return -1;
+  }
+  std::string opname;
+  if (on >= 0) {
+    if (d.at((uint32_t)on).t != J_STR) return -1;
+    opname = std::string(d.sval(d.at((uint32_t)on)));
+    if (var_string(opname) || has_escape_or_ref(opname)) return -1;
+  }
+  const uint32_t op = cond_op(opname);
+  if (op == CD_DURATION) return -1;
+  const PV key = to_pv(d, (uint32_t)kn), value = to_pv(d, (uint32_t)vn);
+  const bool kv = key.t == J_STR && var_string(key.s), vv = value.t == J_STR && var_string(value.s);
+  if (kv && vv) return -1;
+  for (const PV* p : {&key, &value}) {
+    if (p->t == J_STR) {
+      if (has_escape_or_ref(p->s)) return -1;
+      if (var_string(p->s) && !cond_string_in_scope(p->s)) return -1;
+    } else if (tree_has_var(*p)) {
+      return -1;  // variables inside a list or map operand
+    }
+  }
+  if (!(kv ? true : const_operand_ok(key, true)) || !(vv ? true : const_operand_ok(value, false))) return -1;
+  if (!kv && !vv) {  // folded
+    bool range = false;
+    const bool r = cond_eval(op, key, value, &range);
+    return range ? -1 : (r ? 1 : 0);
+  }
+  if (op == CD_UNKNOWN) return 0;
+  const std::string& text = kv ? key.s : value.s;
+  auto ck = ps.ckey_id.find(text);
+  if (ck == ps.ckey_id.end()) {
+    ck = ps.ckey_id.emplace(text, (uint32_t)ps.ckeys.size()).first;
+    ps.ckeys.push_back(text);
+  }
+  CondRec c;
+  c.op = op;
+  c.var_is_key = kv;
+  c.cstr = ck->second;
+  c.other = kv ? value : key;
+  const std::string id = std::to_string(op) + (kv ? "k" : "v") + std::to_string(c.cstr) + "|" + pv_key(c.other);
+  auto it = ps.cond_id.find(id);
+  if (it == ps.cond_id.end()) {
+    it = ps.cond_id.emplace(id, (uint32_t)ps.conds.size()).first;
+    ps.conds.push_back(std::move(c));
+  }
+  *rec = it->second;
+  return 2;
+}
+
+}  // namespace
+
+uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
+  const JNode& n = d.at(node);
+  int64_t any = -1, all = -1;
+  bool old_form = false;
+  if (n.t == J_ARR) {
+    old_form = true;  // []kyverno.Condition: AND (evaluate.go:69-78)
+  } else if (n.t == J_MAP) {
+    for (uint32_t c = n.first; c < n.first + n.count; c++) {
+      const std::string_view k = d.key(d.at(c));
+      if (k == "any") any = c;
+      else if (k == "all") all = c;
+      else return 0;  // "unknown field" (util.go:223-239)
+    }
+  } else {
+    return 0;
+  }
+  // checkpoint of the interning tables: a block outside the scope leaves nothing behind
+  const size_t ck0 = ps.ckeys.size(), cd0 = ps.conds.size();
+  auto rollback = [&]() {
+    for (size_t i = ck0; i < ps.ckeys.size(); i++) ps.ckey_id.erase(ps.ckeys[i]);
+    ps.ckeys.resize(ck0);
+    for (auto it = ps.cond_id.begin(); it != ps.cond_id.end();)
+      it = it->second >= cd0 ? ps.cond_id.erase(it) : std::next(it);
+    ps.conds.resize(cd0);
+    return 0u;
+  };
+  CondSet s;
+  bool any_true = false;
+  auto list = [&](int64_t ln, bool is_any) {
+    const JNode& l = d.at((uint32_t)ln);
+    if (l.t != J_ARR) return false;
+    for (uint32_t c = l.first; c < l.first + l.count; c++) {
+      uint32_t rec = 0;
+      const int r = compile_condition(ps, d, c, &rec);
+      if (r < 0) return false;
+      if (is_any) {
+        if (r == 1) any_true = true;
+        else if (r == 2) s.any.push_back(rec);
+      } else {
+        if (r == 0) s.const_false = true;
+        else if (r == 2) s.all.push_back(rec);
+      }
+    }
+    return true;
+  };
+  if (old_form) {
+    if (!list(node, false)) return rollback();
+  } else {
+    if (any >= 0) {
+      const JNode& l = d.at((uint32_t)any);
+      if (l.t == J_NULL) any = -1;  // a nil list: absent
+      else if (l.t != J_ARR || l.count == 0) return rollback();  // `any: []`: nil or empty after DeepCopy
+    }
+    if (all >= 0 && d.at((uint32_t)all).t == J_NULL) all = -1;
+    if (any >= 0) {
+      if (!list(any, true)) return rollback();
+      if (any_true) s.any.clear();
+      else {
+        s.any_present = true;
+        if (s.any.empty()) s.const_false = true;  // every member a constant false
+      }
+    }
+    if (all >= 0 && !list(all, false)) return rollback();
+  }
+  if (s.const_false) {
+    s.any.clear();
+    s.all.clear();
+    s.any_present = false;
+  }
+  if (!s.const_false && !s.any_present && s.all.empty()) return 0xFFFFFFFFu;
+  // a lane loads each condition string once: its conditions follow each other
+  auto by_str = [&](uint32_t a, uint32_t b) {
+    return ps.conds[a].cstr != ps.conds[b].cstr ? ps.conds[a].cstr < ps.conds[b].cstr : a < b;
+  };
+  std::sort(s.any.begin(), s.any.end(), by_str);
+  std::sort(s.all.begin(), s.all.end(), by_str);
+  s.any.erase(std::unique(s.any.begin(), s.any.end()), s.any.end());
+  s.all.erase(std::unique(s.all.begin(), s.all.end()), s.all.end());
+  std::string id = s.const_false ? "F" : (s.any_present ? "A" : "-");
+  for (uint32_t c : s.any) id += std::to_string(c) + ",";
+  id += "|";
+  for (uint32_t c : s.all) id += std::to_string(c) + ",";
+  auto it = ps.cset_id.find(id);
+  if (it == ps.cset_id.end()) {
+    it = ps.cset_id.emplace(id, (uint32_t)ps.csets.size()).first;
+    ps.csets.push_back(std::move(s));
+  }
+  return it->second + 1;
+}
+
+// ------------------------------------------------------------------ per batch
+void build_pre(const PolicySet& ps, const Batch& b, PreHost* out) {
+  PreHost& h = *out;
+  h = PreHost();
+  if (ps.csets.empty()) return;
+  const uint64_t n = b.res.size();
+  const size_t K = ps.vout_width(), k0 = ps.vkeys.size(), C = ps.ckeys.size();
+  for (const CondSet& s : ps.csets) {
+    h.sets.push_back((uint32_t)(h.ents.size() / 2));
+    h.sets.push_back((uint32_t)s.any.size() | (s.any_present ? 0x80000000u : 0u));
+    h.sets.push_back((uint32_t)s.all.size());
+    h.sets.push_back(s.const_false ? 1u : 0u);
+    for (uint32_t c : s.any) { h.ents.push_back(ps.conds[c].cstr); h.ents.push_back(c); }
+    for (uint32_t c : s.all) { h.ents.push_back(ps.conds[c].cstr); h.ents.push_back(c); }
+  }
+  // outcome ids, [condition string][res] (a lane's load is coalesced)
+  h.outc.resize(C * n);
+  if (b.vout.size() != K * n) throw std::runtime_error("build_pre: outcome rows do not match the policy set");
+  for (uint64_t r = 0; r < n; r++)
+    for (size_t c = 0; c < C; c++) h.outc[c * n + r] = b.vout[r * K + k0 + c];
+  // the outcomes each condition string takes in this batch
+  const size_t T = b.vout_tab.size();
+  const uint32_t W = (uint32_t)std::max<size_t>((T + 31) / 32, 1);
+  h.words = W;
+  std::vector<uint32_t> seen(C * W, 0);
+  for (size_t c = 0; c < C; c++)
+    for (uint64_t r = 0; r < n; r++) {
+      const uint32_t o = h.outc[c * n + r];
+      seen[c * W + o / 32] |= 1u << (o % 32);
+    }
+  h.truth.assign(ps.conds.size() * W, 0);
+  h.unk.assign(ps.conds.size() * W, 0);
+  for (size_t ci = 0; ci < ps.conds.size(); ci++) {
+    const CondRec& c = ps.conds[ci];
+    for (size_t o = 0; o < T; o++) {
+      if (!((seen[c.cstr * W + o / 32] >> (o % 32)) & 1u)) continue;
+      const std::string& oc = b.vout_tab[o];
+      const char t = oc.empty() ? 'C' : oc[0];
+      if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N')) {  // a map / array, outside the scope
+        h.unk[ci * W + o / 32] |= 1u << (o % 32);
+        continue;
+      }
+      const PV v = outcome_value(oc);
+      bool range = false;
+      const bool r = c.var_is_key ? cond_eval(c.op, v, c.other, &range) : cond_eval(c.op, c.other, v, &range);
+      if (range) h.unk[ci * W + o / 32] |= 1u << (o % 32);
+      else if (r) h.truth[ci * W + o / 32] |= 1u << (o % 32);
+    }
+  }
+}
+
+uint8_t pre_status_host(const PreHost& h, uint32_t set, uint64_t n_res, uint64_t r) {
+  return (uint8_t)kv_pre_lane(h.sets.data(), h.ents.data(), h.outc.data(), h.truth.data(), h.unk.data(), h.words, set,
+                              n_res, r);
+}
+
+}  // namespace kvh

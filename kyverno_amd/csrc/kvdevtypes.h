@@ -135,6 +135,18 @@ struct DevBatch {
   // words, every row of a family laid out by cell format (below), so a lookup loads only the
   // words its consumers read (4 bytes for a narrow cell, 12 or 16 for a wide one)
   const uint32_t* pcol;
+  // preconditions (kvcond.h PreHost, kvpre.h): the policy set's condition sets (4 words each) and
+  // their entries (condition string, condition), the outcome id per [condition string][res], the
+  // truth / unknown bit planes per [condition][pre_words] over outcome ids, and the gate
+  // kv_precond_kernel writes once per batch: pre_st[set * n_res + res] = 0 (evaluate the
+  // pattern), ST_SKIP ("preconditions not met") or ST_CPU (undecided on the device)
+  const uint32_t* pre_sets;
+  const uint32_t* pre_ents;
+  const uint32_t* pre_outc;
+  const uint32_t* pre_truth;
+  const uint32_t* pre_unk;
+  uint32_t pre_words, n_pre_sets;
+  const uint8_t* pre_st;
 };
 
 // ------------------------------------------------------------------ path columns

@@ -716,8 +716,11 @@ struct Ingest {
       r.flags |= RF_MAGIC;
     b.res.push_back(r);  // root row assigned by flush_group
     // pattern variables: every distinct (string, path) resolved on this resource (kvvars.cpp)
-    for (const auto& vk : ps.vkeys) {
-      std::string o = resolve_var_string(vk.first, vk.second, d);
+    // (then every distinct precondition string, under the preconditions resolver)
+    const size_t nvk = ps.vkeys.size(), nck = ps.ckeys.size();
+    for (size_t k = 0; k < nvk + nck; k++) {
+      std::string o = k < nvk ? resolve_var_string(ps.vkeys[k].first, ps.vkeys[k].second, d)
+                              : resolve_var_string(ps.ckeys[k - nvk], "", d, true);
       auto it = b.vout_id.find(o);
       if (it == b.vout_id.end()) {
         it = b.vout_id.emplace(o, (uint32_t)b.vout_tab.size()).first;

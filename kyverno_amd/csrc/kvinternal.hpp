@@ -60,6 +60,20 @@ struct VarStr {
   bool want_string = false;  // under metadata.labels / annotations (ExpandInMetadata needs a string)
 };
 
+// Rule preconditions (kvcond.h). One interned condition with a variable operand:
+struct CondRec {
+  uint32_t op = 0;         // CondOp
+  bool var_is_key = true;  // the variable string is `key` (else `value`)
+  uint32_t cstr = 0;       // PolicySet::ckeys index
+  PV other;                // the constant operand
+};
+// One interned condition set, constants folded: the conditions left of `any` (any_present: the
+// list exists and no constant member is true) and of `all`; const_false: a constant decides SKIP.
+struct CondSet {
+  bool any_present = false, const_false = false;
+  std::vector<uint32_t> any, all;  // CondRec indices, ordered by condition string
+};
+
 // Projection trie over resource key paths referenced by any compiled pattern
 // or match block. Arrays are transparent: `elem` is the element trie.
 struct Trie {
@@ -177,6 +191,15 @@ struct PolicySet {
   std::vector<std::pair<std::string, std::string>> vkeys;
   std::vector<uint32_t> dleaf_vstr;
   std::vector<std::pair<uint32_t, uint32_t>> dyn_rules;
+  // preconditions (kvcond.cpp): the distinct condition strings holding variables (a key space of
+  // their own: the preconditions resolver substitutes "" where the pattern resolver fails), the
+  // interned conditions and condition sets (RuleRec::pre - 1)
+  std::vector<std::string> ckeys;
+  std::vector<CondRec> conds;
+  std::vector<CondSet> csets;
+  std::unordered_map<std::string, uint32_t> ckey_id, cond_id, cset_id;
+  // columns of a Batch::vout row: the pattern-variable keys, then the condition strings
+  size_t vout_width() const { return vkeys.size() + ckeys.size(); }
 };
 
 // Compiles a JSON list of (already autogen-expanded) ClusterPolicy/Policy
@@ -337,8 +360,9 @@ struct Batch {
   std::vector<uint32_t> ns_bits;     // [n_ns][ceil(n_nssel/32)]
   uint32_t ns_words = 1;
   uint64_t bytes_referenced = 0;     // algorithmic bytes of the projected store
-  // pattern variables: outcome id per (resource, PolicySet::vkeys entry), resource-major,
-  // and the distinct outcomes (kvvars.cpp resolve_var_string encoding)
+  // pattern variables and precondition strings: outcome id per (resource, PolicySet::vkeys
+  // entry, then PolicySet::ckeys entry), resource-major, and the distinct outcomes (kvvars.cpp
+  // resolve_var_string encoding)
   std::vector<uint32_t> vout;
   std::vector<std::string> vout_tab;
   std::unordered_map<std::string, uint32_t> vout_id;  // (ingest only)
@@ -358,7 +382,10 @@ void build_dyn(const PolicySet& ps, const Batch& b, DynHost* out);
 bool var_string(const std::string& s);
 bool var_string_in_scope(const std::string& s, const std::string& path);
 std::string unescape_var_string(const std::string& s);
-std::string resolve_var_string(const std::string& tmpl, const std::string& path, const JDoc& d);
+// precond: the preconditions resolver (vars.go:62-74): a variable that fails to resolve is ""
+std::string resolve_var_string(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond = false);
+// every variable of `s` is a request.object path of the device subset (no {{@}})
+bool cond_string_in_scope(const std::string& s);
 PV outcome_value(const std::string& o);
 uint32_t compile_leaf_pred(PolicySet& tbl, const PV& value);  // kvcompile.cpp
 std::string pattern_go_v(const PV& p);                         // Go %v of a scalar pattern value

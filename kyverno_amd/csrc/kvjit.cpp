@@ -1512,7 +1512,8 @@ struct Gen {
     const RuleRec& rr = ps.rules[ri];
     // (pattern-variable rules stay out of groups: their substitution status is decided per
     // member before the walk, and a group's record layout may be per resource slot)
-    if (rr.route != 0 || rr.dyn) return "";
+    // (nor rules with preconditions: their gate is applied per rule before the walk)
+    if (rr.route != 0 || rr.dyn || rr.pre) return "";
     const uint32_t b = rr.prog, e = prog_end(ps, b);
     std::ostringstream f;
     auto rel = [&](uint32_t t) { return (int64_t)t - (int64_t)b; };
@@ -1800,6 +1801,9 @@ struct Gen {
           k << "    if (rflags & RF_MAGIC) rs" << s << " = FIN_ | ST_CPU;\n";
           if (rr.flags & RR_META_EXPAND)
             k << "    else if (rflags & " << u32(meta_bad_flags(rr.flags)) << ") rs" << s << " = FIN_ | ST_CPU;\n";
+          if (rr.pre)  // preconditions precede pattern substitution (validation.go:175-193)
+            k << "    else if (B.pre_st[(size_t)" << (rr.pre - 1) << "u * n_res + r]) rs" << s << " = FIN_ | B.pre_st[(size_t)"
+              << (rr.pre - 1) << "u * n_res + r];\n";
           if (rr.dyn)
             k << "    else if (B.dyn_st[(size_t)" << (rr.dyn - 1) << "u * n_res + r]) rs" << s << " = FIN_ | B.dyn_st[(size_t)"
               << (rr.dyn - 1) << "u * n_res + r];\n";

@@ -33,6 +33,7 @@ using namespace kv;
 #include "kvdevfn.h"
 #include "kvfac.h"
 #include "kvcol.h"
+#include "kvpre.h"
 
 // ------------------------------------------------------------------ kernel
 extern "C" __global__ __launch_bounds__(KV_WG) __attribute__((amdgpu_waves_per_eu(4))) void kv_validate_kernel(const DevPS* __restrict__ Pp,
@@ -87,6 +88,8 @@ extern "C" __global__ __launch_bounds__(KV_WG) __attribute__((amdgpu_waves_per_e
         else if (route == 3) st = (uint8_t)uni(rr.const_status);
         else if (rflags & RF_MAGIC) st = ST_CPU;
         else if (rflags & meta_bad_flags(uni(rr.flags))) st = ST_CPU;
+        // preconditions precede pattern substitution (validation.go:175-193): SKIP or CPU is final
+        else if (uni(rr.pre) && B.pre_st[(size_t)(uni(rr.pre) - 1u) * n_res + r]) st = B.pre_st[(size_t)(uni(rr.pre) - 1u) * n_res + r];
         else if (uni(rr.dyn) && B.dyn_st[(size_t)(uni(rr.dyn) - 1u) * n_res + r]) st = B.dyn_st[(size_t)(uni(rr.dyn) - 1u) * n_res + r];
         else run = true;
       }
@@ -347,6 +350,32 @@ hipError_t launch_validate(const DevPS* P, const DevBatch* B, uint32_t n_res, co
   dim3 grid(rb8 * n_chunks);
   hipLaunchKernelGGL(kv_validate_kernel, grid, dim3(KV_WG), 0, stream, P, B, O, rule_begin, rule_end, n_chunks,
                      rblocks);
+  return hipGetLastError();
+}
+}  // namespace kv
+
+// ---------------------------------------------------------------------------
+// Precondition gate (kvcond.h, kvpre.h): one lane per resource, grid.x = workgroups of 256
+// resources, grid.y = condition sets (a workgroup walks sets blockIdx.y, + gridDim.y, ...). The
+// set's entry list is wave-uniform (scalar loads); per condition string one coalesced 32-bit load
+// of the lane's outcome id, then two gathers into the bit planes (small: they stay in L2). One
+// byte per (set, resource): 0 pass, ST_SKIP, ST_CPU; lanes past n_res write nothing.
+constexpr uint32_t KV_PRE_YMAX = 1024u;
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_precond_kernel(const DevBatch* __restrict__ Bp, uint32_t n_res,
+                                                                       uint32_t n_sets, uint8_t* __restrict__ pre_st) {
+  const DevBatch& B = *Bp;
+  const uint64_t r = (uint64_t)blockIdx.x * KV_WG + threadIdx.x;
+  if (r >= n_res) return;
+  for (uint32_t s = blockIdx.y; s < n_sets; s += gridDim.y)
+    pre_st[(size_t)s * n_res + r] =
+        (uint8_t)kv_pre_lane(B.pre_sets, B.pre_ents, B.pre_outc, B.pre_truth, B.pre_unk, B.pre_words, s, n_res, r);
+}
+
+namespace kv {
+hipError_t launch_precond(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* pre_st, hipStream_t stream) {
+  if (n_res == 0 || n_sets == 0) return hipSuccess;
+  hipLaunchKernelGGL(kv_precond_kernel, dim3((n_res + KV_WG - 1) / KV_WG, n_sets < KV_PRE_YMAX ? n_sets : KV_PRE_YMAX),
+                     dim3(KV_WG), 0, stream, B, n_res, n_sets, pre_st);
   return hipGetLastError();
 }
 }  // namespace kv

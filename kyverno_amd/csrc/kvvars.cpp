@@ -308,6 +308,18 @@ bool var_string_in_scope(const std::string& s, const std::string& path) {
   return true;
 }
 
+bool cond_string_in_scope(const std::string& s) {
+  std::vector<QStep> steps;
+  for (std::string v : find_vars(s)) {
+    if (!var_initial(v)) {
+      if ((unsigned char)v[0] >= 0x80) return false;
+      v = v.substr(1);
+    }
+    if (!parse_query(var_name(v), &steps)) return false;
+  }
+  return true;
+}
+
 std::string unescape_var_string(const std::string& s) {
   std::string v = s;
   for (const auto& e : find_escaped_vars(v)) v = replace_all(v, e, e.substr(1));
@@ -318,7 +330,7 @@ std::string unescape_var_string(const std::string& s) {
 // with request.object = resource `d`. Outcome encoding (interned per batch): "S" + string,
 // "F" + 8 raw bytes of a float64, "B0" / "B1", "N" (null), "E" + the error text, "C" (outside
 // the device scope), "M" (a map or array: a structural pattern, outside the scope).
-std::string resolve_var_string(const std::string& tmpl, const std::string& path, const JDoc& d) {
+std::string resolve_var_string(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond) {
   std::string value = tmpl;
   std::vector<QStep> steps;
   auto vars = find_vars(value);
@@ -337,8 +349,13 @@ std::string resolve_var_string(const std::string& tmpl, const std::string& path,
       if (!var_query(var_name(v), path, &q) || !parse_query(q, &steps)) return "C";
       int64_t node = -1;
       std::string missing;
-      if (query_doc(steps, d, &node, &missing) == 1) return "EUnknown key \"" + missing + "\" in path";
+      bool unresolved = false;
+      if (query_doc(steps, d, &node, &missing) == 1) {
+        if (!precond) return "EUnknown key \"" + missing + "\" in path";
+        unresolved = true;  // newPreconditionsVariableResolver (vars.go:62-74): the value is ""
+      }
       if (original == v) {  // the whole string: the value itself
+        if (unresolved) return "S";
         if (node < 0) return "N";
         const JNode& n = d.at((uint32_t)node);
         switch (n.t) {
@@ -356,7 +373,8 @@ std::string resolve_var_string(const std::string& tmpl, const std::string& path,
       }
       const std::string prefix = initial ? "" : old.substr(0, 1);
       std::string sub;
-      if (node >= 0 && d.at((uint32_t)node).t == J_STR) sub = std::string(d.sval(d.at((uint32_t)node)));
+      if (unresolved) sub.clear();
+      else if (node >= 0 && d.at((uint32_t)node).t == J_STR) sub = std::string(d.sval(d.at((uint32_t)node)));
       else json_value(sub, d, node);
       value = replace_first(original, prefix + v, prefix + sub);
     }
@@ -381,8 +399,8 @@ void build_dyn(const PolicySet& ps, const Batch& b, DynHost* out) {
   DynHost& h = *out;
   h = DynHost();
   const uint64_t n = b.res.size();
-  const size_t K = ps.vkeys.size();
-  if (!K) return;
+  const size_t K = ps.vout_width();
+  if (ps.vkeys.empty()) return;
   const std::vector<std::string>& tab = b.vout_tab;
   // batch predicate table: one predicate per distinct outcome (pred id == outcome id)
   for (size_t o = 0; o < tab.size(); o++) {

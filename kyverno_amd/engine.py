@@ -10,9 +10,12 @@ error (``addRuleResponse``, validation.go:111-123). A response without rule resp
 ``EngineResponse`` (``buildResponse`` returns early, validation.go:53-56). Policies are taken as
 given: the CLI's defaults + autogen (``kyverno_amd.autogen``) happen before, as in the reference.
 
-Rules the device does not evaluate (context, preconditions, deny, foreach, pattern variables other
-than ``request.object`` paths: ``KV_ROUTE_CPU``) come back with status ``"cpu"``: the Go host runs
-``processValidationRule`` for them. They are not counted.
+Rules the device does not evaluate (context, deny, foreach, pattern variables other than
+``request.object`` paths, preconditions outside the device forms: ``KV_ROUTE_CPU``) come back with
+status ``"cpu"``: the Go host runs ``processValidationRule`` for them. They are not
+counted. Preconditions of the device forms (``kyverno_amd.batch``) are evaluated with the rule: a
+pair whose preconditions do not hold is ``"skip"`` with the message ``preconditions not met``
+(validation.go:175-184).
 """
 from __future__ import annotations
 

@@ -109,6 +109,37 @@ def c2_policies() -> list[dict]:
     return [_policy("c2-pod-rules", rules)]
 
 
+# Eight precondition blocks over the labels of the synthetic Pods (kv_synth: app on 90 %, owner on
+# 60 %, tier on 50 % of them), of every device form: old list, any, all, any + all.
+C2_PRECONDITION_SETS = [
+    [{"key": "{{request.object.metadata.labels.tier}}", "operator": "Equals", "value": "frontend"}],
+    {"all": [{"key": "{{request.object.metadata.labels.app}}", "operator": "NotEquals", "value": ""}]},
+    {"any": [{"key": "{{request.object.metadata.labels.tier}}", "operator": "In", "value": ["frontend", "backend"]},
+             {"key": "{{request.object.metadata.labels.owner}}", "operator": "Equals", "value": "team-*"}]},
+    {"all": [{"key": "{{request.object.metadata.labels.app}}", "operator": "AnyNotIn", "value": ["web", "api"]},
+             {"key": "{{request.object.metadata.labels.owner}}", "operator": "NotEquals", "value": ""}]},
+    {"any": [{"key": "{{request.object.metadata.labels.app}}", "operator": "Equals", "value": "*e*"}],
+     "all": [{"key": "{{request.object.metadata.labels.tier}}", "operator": "NotEquals", "value": "data"}]},
+    {"all": [{"key": "{{request.object.metadata.labels.owner}}", "operator": "AllNotIn", "value": ["platform"]}]},
+    {"any": [{"key": "{{request.object.metadata.labels.tier}}", "operator": "Equals", "value": ""},
+             {"key": "{{request.object.metadata.labels.tier}}", "operator": "Equals", "value": "data"}]},
+    {"all": [{"key": "{{request.object.metadata.namespace}}/{{request.object.metadata.labels.app}}",
+              "operator": "NotEquals", "value": "ns-1*/db"}]},
+]
+
+
+def c2_precondition_policies() -> list[dict]:
+    """The C2 rule set with every rule behind one of eight precondition blocks (rule i: block
+    i mod 8): the workload of the precondition gate's measurement (DESIGN.md §3 *Preconditions*)."""
+    import copy
+
+    pols = c2_policies()
+    for i, r in enumerate(pols[0]["spec"]["rules"]):
+        r["preconditions"] = copy.deepcopy(C2_PRECONDITION_SETS[i % len(C2_PRECONDITION_SETS)])
+    pols[0]["metadata"]["name"] = "c2-pod-rules-preconditions"
+    return pols
+
+
 C3_KIND_MIX = 2  # kv_synth stream of C3: Pods/Deployments/Services 60/25/15 over 1 000 namespaces
 C3_NAMESPACES = 1000
 

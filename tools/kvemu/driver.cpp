@@ -27,6 +27,8 @@
 #include "../../kyverno_amd/csrc/kvdevtypes.h"
 #include "../../kyverno_amd/csrc/kvinternal.hpp"
 #include "../../kyverno_amd/csrc/kvjit.hpp"
+#include "../../kyverno_amd/csrc/kvcond.h"
+#include "../../kyverno_amd/csrc/kvpre.h"
 
 using namespace kv;
 using namespace kvh;
@@ -221,6 +223,26 @@ int main(int argc, char** argv) {
     B.dps = &PD;
     B.dleaf = dyn.dleaf.data();
     B.dyn_st = dyn.dyn_st.data();
+    // preconditions (as dev_batch): the gate's tables, then every (set, resource) through the
+    // per-lane function kv_precond_kernel runs (kvpre.h)
+    PreHost pre;
+    std::vector<uint8_t> pre_st;
+    if (!ps.csets.empty() && !b.res.empty()) {
+      build_pre(ps, b, &pre);
+      B.pre_sets = pre.sets.data();
+      B.pre_ents = pre.ents.data();
+      B.pre_outc = pre.outc.data();
+      B.pre_truth = pre.truth.data();
+      B.pre_unk = pre.unk.data();
+      B.pre_words = pre.words;
+      B.n_pre_sets = (uint32_t)ps.csets.size();
+      pre_st.assign((size_t)B.n_pre_sets * B.n_res, 0xEE);
+      for (uint32_t s = 0; s < B.n_pre_sets; s++)
+        for (uint32_t r = 0; r < B.n_res; r++)
+          pre_st[(size_t)s * B.n_res + r] = (uint8_t)kv_pre_lane(B.pre_sets, B.pre_ents, B.pre_outc, B.pre_truth,
+                                                                 B.pre_unk, B.pre_words, s, B.n_res, r);
+      B.pre_st = pre_st.data();
+    }
     // path columns of the image (as dev_batch: built once per batch)
     std::vector<uint32_t> pcol_erow;
     std::vector<uint32_t> pcol;  // rows by cell format (kvcol.h col_put)
