@@ -42,7 +42,16 @@ enum { KV_ROUTE_GPU = 0, KV_ROUTE_CPU = 1, KV_ROUTE_NORESPONSE = 2, KV_ROUTE_CON
 enum {
   /* also lower every rule to a specialized gfx950 kernel (hiprtc, at compile
    * time); kv_validate/kv_session then run those instead of the bytecode VM */
-  KV_COMPILE_SPECIALIZE = 1
+  KV_COMPILE_SPECIALIZE = 1,
+  /* evaluate validate.deny rules on the device (opt-in; without it every such rule is
+   * KV_ROUTE_CPU, reason "deny"). In scope: a rule with validate.deny and no pattern /
+   * anyPattern, context or foreach, preconditions absent or of the device forms, and
+   * deny.conditions an any / all block (or the old list) whose conditions are of the forms the
+   * preconditions accept: a request.object variable string on one side, a constant scalar or
+   * list on the other, or both constant. A pair is FAIL when the conditions hold, PASS when they
+   * do not, ERROR when a variable of the block does not resolve (kv_result_deny_message), CPU
+   * when the device cannot decide (a map or array operand). Other forms keep the CPU route. */
+  KV_COMPILE_DENY = 2
 };
 
 /* kv_validate modes (bit set). KV_MODE_SCOPES adds per-scope counts
@@ -95,6 +104,17 @@ int kv_policyset_cond_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* con
  * float64: *result = 0 or 1. KV_E_RANGE when an operand is outside the device scope (a map, a
  * list key, the deprecated Duration* operators), KV_E_PARSE for bad JSON. Needs no GPU. */
 int kv_condition_eval(const char* condition_json, size_t len, int* result);
+/* validate.deny rules evaluated on the device (KV_COMPILE_DENY): interned deny sets, their
+ * conditions with a variable operand, and their distinct condition strings (a key space apart
+ * from the preconditions': deny strings resolve under the strict resolver). Any may be NULL. */
+int kv_policyset_deny_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings);
+/* *set = 1 + the deny set of rule `rule`, 0 for a rule that is not a device deny rule */
+int kv_rule_deny_set(const kv_policyset* ps, uint32_t rule, uint32_t* set);
+/* The deny fold of deny set `set` (0-based) over an ingested batch, on the host: status[i] of
+ * resource i (caller order) is what kv_deny_kernel writes for it, KV_STATUS_PASS / _FAIL / _ERROR /
+ * _CPU, before match / exclude and the preconditions are applied. `n` must be the batch's
+ * resource count. Diagnostics and tests; needs no GPU. */
+int kv_batch_deny_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint64_t n);
 int kv_rule_info_get(const kv_policyset* ps, uint32_t rule, kv_rule_info* out);
 
 /* Ingest resources (JSON array or NDJSON of unstructured objects; numbers typed
@@ -154,7 +174,8 @@ int kv_device_trim(int device);
  * "status_d2h", "records_count", "records_scatter_d2h", ...) and wall-clock milliseconds;
  * KV_E_RANGE past the last phase. Diagnostics of the host boundary (no reference counterpart).
  * "precond" (policy sets with device-evaluated preconditions): the HIP-event time of the
- * precondition gate's kernel, which runs once per batch when the batch is uploaded. */
+ * precondition gate's kernel, which runs once per batch when the batch is uploaded. "deny"
+ * (policy sets with device deny rules): the same for the deny fold's kernel. */
 int kv_result_phase(const kv_result* r, uint32_t i, const char** name, double* ms);
 /* counts[(scope * n_rules + rule) * 8 + status] (KV_MODE_SCOPES) */
 int kv_result_scope_counts(const kv_result* r, const int64_t** counts, uint32_t* n_scopes);
@@ -185,6 +206,15 @@ int kv_result_subst_error(const kv_result* r, uint32_t rule, uint64_t res, char*
  * and returns its length; 0 when the status has another cause (a conditional-anchor SKIP of the
  * pattern). Negative codes as kv_result_subst_error. */
 int kv_result_precond_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
+
+/* Deny rules (KV_COMPILE_DENY): when rule `rule` is ERROR on `res` because a variable of its
+ * deny conditions does not resolve (pkg/engine/validation.go:299-304), writes the RuleResponse
+ * message "failed to substitute variables in deny conditions: <error>" and returns its length; 0
+ * when the status has another cause or the rule is not a device deny rule. With several
+ * unresolved strings the error is the first in document order (the reference ranges over a Go
+ * map there: its order is not fixed). Negative codes as kv_result_subst_error. The PASS and FAIL
+ * messages are formed by the caller from kv_rule_info. */
+int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
 double kv_result_kernel_ms(const kv_result* r);
 
 /* Bulk export of the failing pairs (KV_MODE_ERRORS): every FAIL / ERROR / SKIP pair,

@@ -11,7 +11,10 @@ Equal(s), NotEqual(s), the In family and the four numeric comparisons, each with
 ``request.object`` variables on one side and a constant scalar or list on the other,
 are evaluated on the device (``kv_precond_kernel``): a pair whose preconditions do
 not hold is ``SKIP`` (``Result.precond_message``), one they cannot decide there (a
-map or array operand) is ``CPU``.
+map or array operand) is ``CPU``. ``PolicySet(..., deny=True)`` (``KV_COMPILE_DENY``, opt-in)
+also evaluates ``validate.deny`` rules whose conditions are of those forms on the device
+(``kv_deny_kernel``): ``FAIL`` when the conditions hold, ``PASS`` when they do not, ``ERROR`` when
+a variable does not resolve (``Result.deny_message``).
 """
 from __future__ import annotations
 
@@ -28,7 +31,7 @@ PASS, FAIL, WARN, ERROR, SKIP, NOMATCH, CPU = range(7)
 STATUS_NAMES = ["pass", "fail", "warn", "error", "skip", "nomatch", "cpu"]
 
 MODE_STATUS, MODE_ERRORS, MODE_COUNTS, MODE_SCOPES = 1, 2, 4, 8
-COMPILE_SPECIALIZE = 1
+COMPILE_SPECIALIZE, COMPILE_DENY = 1, 2
 ROUTE_GPU, ROUTE_CPU, ROUTE_NORESPONSE, ROUTE_CONSTANT = range(4)
 
 
@@ -64,6 +67,7 @@ class Rule:
     any_pattern: bool
     const_status: int
     const_message: str
+    deny: bool = False  # a validate.deny rule evaluated on the device (PolicySet(deny=True))
 
 
 class PolicySet:
@@ -72,17 +76,24 @@ class PolicySet:
     ``specialize=True`` also lowers every rule to specialized gfx950 kernels
     (hiprtc, at construction); evaluation then runs those instead of the
     bytecode interpreter. ``jit_info`` reports their build cost.
+
+    ``deny=True`` (``KV_COMPILE_DENY``, opt-in) routes ``validate.deny`` rules of the device forms
+    to the GPU: any / all (or old list) conditions as the preconditions accept them, over
+    ``request.object`` variables. A pair is ``FAIL`` when the conditions hold, ``PASS`` when they
+    do not, ``ERROR`` when a variable does not resolve (``Result.deny_message``), ``CPU`` when the
+    device cannot decide. Without it every deny rule is CPU-routed, reason ``"deny"``.
     """
 
-    def __init__(self, policies, specialize: bool = False):
+    def __init__(self, policies, specialize: bool = False, deny: bool = False):
         L = lib()
         data = _dumps(policies)
         h = ctypes.c_void_p()
         err = new_err()
-        flags = COMPILE_SPECIALIZE if specialize else 0
+        flags = (COMPILE_SPECIALIZE if specialize else 0) | (COMPILE_DENY if deny else 0)
         check(L.kv_compile(data, len(data), flags, ctypes.byref(h), ctypes.byref(err)), err)
         self._h = h
         self.specialize = specialize
+        self.deny = deny
         np_, nr = ctypes.c_uint32(), ctypes.c_uint32()
         L.kv_policyset_info(h, ctypes.byref(np_), ctypes.byref(nr))
         self.n_policies, self.n_rules = np_.value, nr.value
@@ -93,6 +104,9 @@ class PolicySet:
             d = lambda b: (b or b"").decode("utf-8")  # noqa: E731
             self.rules.append(Rule(i, ri.policy, d(ri.policy_name), d(ri.name), ri.route, d(ri.route_reason),
                                    d(ri.message), bool(ri.any_pattern), ri.const_status, d(ri.const_message)))
+            ds = ctypes.c_uint32()
+            L.kv_rule_deny_set(h, i, ctypes.byref(ds))
+            self.rules[-1].deny = ds.value != 0
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -120,6 +134,32 @@ class PolicySet:
         s, c, k = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         lib().kv_policyset_cond_sets(self._h, ctypes.byref(s), ctypes.byref(c), ctypes.byref(k))
         return {"sets": s.value, "conditions": c.value, "strings": k.value}
+
+    @property
+    def deny_info(self) -> dict:
+        """Deny rules evaluated on the device: interned deny sets, their conditions with a variable
+        operand and their distinct condition strings (``kv_policyset_deny_sets``), and per rule
+        1 + its deny set, 0 for a rule that is not a device deny rule (``kv_rule_deny_set``)."""
+        s, c, k = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        lib().kv_policyset_deny_sets(self._h, ctypes.byref(s), ctypes.byref(c), ctypes.byref(k))
+        rule_sets = []
+        for i in range(self.n_rules):
+            ds = ctypes.c_uint32()
+            lib().kv_rule_deny_set(self._h, i, ctypes.byref(ds))
+            rule_sets.append(ds.value)
+        return {"sets": s.value, "conditions": c.value, "strings": k.value, "rule_sets": rule_sets}
+
+    def deny_fold(self, b: "Batch") -> np.ndarray:
+        """u8 [deny sets][n_res]: the deny fold of every deny set over batch ``b`` on the host
+        (``kv_batch_deny_fold``, no GPU): what ``kv_deny_kernel`` writes, before match / exclude
+        and the preconditions are applied."""
+        n_sets = self.deny_info["sets"]
+        out = np.zeros((n_sets, b.n_res), dtype=np.uint8)
+        for s in range(n_sets):
+            rc = lib().kv_batch_deny_fold(self._h, b._h, s, out[s].ctypes.data, b.n_res)
+            if rc != 0:
+                raise RuntimeError(f"kv_batch_deny_fold: code {rc}")
+        return out
 
     def policy_rules(self, policy: int) -> list[Rule]:
         return [r for r in self.rules if r.policy == policy]
@@ -259,6 +299,16 @@ class Result:
         buf = ctypes.create_string_buffer(64)
         n = lib().kv_result_precond_message(self._h, rule, res, buf, 64)
         return buf.raw[:n].decode("utf-8") if n > 0 else None
+
+    def deny_message(self, rule: int, res: int) -> str | None:
+        """"failed to substitute variables in deny conditions: ..." for an ERROR pair of a device
+        deny rule (``kv_result_deny_message``), else None."""
+        n = lib().kv_result_deny_message(self._h, rule, res, None, 0)
+        if n <= 0:
+            return None
+        buf = ctypes.create_string_buffer(n + 1)
+        lib().kv_result_deny_message(self._h, rule, res, buf, n + 1)
+        return buf.raw[:n].decode("utf-8")
 
     def subst_error(self, rule: int, res: int) -> str | None:
         """The RuleResponse message of an ERROR pair caused by the pattern's variables failing to

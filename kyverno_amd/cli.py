@@ -22,8 +22,10 @@ context, deny, foreach, preconditions outside the device forms — ``KV_ROUTE_CP
 routed to the reference engine and not counted; preconditions of the device forms (any / all of
 Equals, In, GreaterThan ... conditions on ``request.object`` paths) are evaluated with the rule: a
 pair whose preconditions do not hold is `skip`, "preconditions not met"; a Go host runs them through ``engine.Validate``.
+``--device-deny`` (``evaluate(deny=True)``, ``KV_COMPILE_DENY``) also evaluates ``validate.deny`` rules
+whose conditions are of those forms on the device, with the messages of ``validateDeny``.
 
-    python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N]
+    python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N] [--device-deny]
     python -m kyverno_amd test test/cli/test/simple
 """
 from __future__ import annotations
@@ -103,6 +105,7 @@ class Evaluation:
     errors: dict = field(default_factory=dict)  # (rule, res) -> err.Error() of ERROR / SKIP pairs
     subst: dict = field(default_factory=dict)   # (rule, res) -> message of a pattern-variable substitution ERROR
     precond: dict = field(default_factory=dict)  # (rule, res) -> message of a SKIP decided by the preconditions
+    deny: dict = field(default_factory=dict)    # (rule, res) -> message of an ERROR of a deny rule's substitution
     anypattern: dict = field(default_factory=dict)  # (rule, res) -> [(status, path)] per pattern
     warnings: list = field(default_factory=list)    # host-side limits met while rendering messages
 
@@ -111,21 +114,24 @@ class Evaluation:
 
 
 def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messages: bool = True,
-             namespace_labels: dict | None = None, specialize: bool = False, gpus: int = 1) -> Evaluation:
+             namespace_labels: dict | None = None, specialize: bool = False, gpus: int = 1,
+             deny: bool = False) -> Evaluation:
     """All (rule, resource) pairs on the GPU (``kv_compile`` → ``kv_ingest`` → ``kv_validate``).
     ``specialize`` selects the per-policy-set specialized kernels (worth their hiprtc compile on
     large batches) over the bytecode interpreter; both write the same statuses and error records.
-    ``gpus`` > 1 shards the resources over devices [device, device + gpus) (kv_validate_devices)."""
+    ``gpus`` > 1 shards the resources over devices [device, device + gpus) (kv_validate_devices).
+    ``deny`` evaluates ``validate.deny`` rules of the device forms on the GPU (``KV_COMPILE_DENY``)
+    instead of routing them to the reference engine."""
     from . import batch
 
-    ps = batch.PolicySet(policies, specialize=specialize)
+    ps = batch.PolicySet(policies, specialize=specialize, deny=deny)
     b = batch.Batch(ps, resources, namespace_labels)
     mask = ((1 << gpus) - 1) << device if gpus > 1 else None
     r = batch.validate(ps, b, device=device, device_mask=mask)
     ev = Evaluation(policies, resources, ps.rules, r.status)
     if messages:
         for ri, res in zip(*np.nonzero(r.status == FAIL)):
-            if not ps.rules[ri].any_pattern:
+            if not ps.rules[ri].any_pattern and not ps.rules[ri].deny:  # (a deny FAIL has no failing path)
                 ev.paths[(int(ri), int(res))] = r.path(int(ri), int(res))
         collect_errors(ev, ps, r, resources)
         _evaluate_anypatterns(ev, device, specialize, namespace_labels)
@@ -141,6 +147,10 @@ def collect_errors(ev: Evaluation, ps, r, resources: list) -> None:
             m = r.subst_error(*key)
             if m is not None:
                 ev.subst[key] = m
+                continue
+            m = r.deny_message(*key)
+            if m is not None:
+                ev.deny[key] = m
                 continue
         else:
             m = r.precond_message(*key)
@@ -224,6 +234,19 @@ def rule_message(ev: Evaluation, rule, res: int) -> str:
         return ev.subst[(rule.index, res)]
     if st == SKIP and (rule.index, res) in ev.precond:  # "preconditions not met" (validation.go:183-184)
         return ev.precond[(rule.index, res)]
+    if getattr(rule, "deny", False):  # validateDeny / getDenyMessage (validation.go:299-339)
+        if st == PASS:
+            return f"validation rule '{rule.name}' passed."
+        if st == FAIL:
+            if not rule.message:
+                return f"validation error: rule {rule.name} failed"
+            try:  # the substituted message as it is (no "validation error:" prefix) ...
+                return _message(ev, rule, res)
+            except msgvars.MessageVariableNotFound:  # ... or, when that errors, as written
+                return rule.message
+        if st == ERROR:  # ruleError("failed to substitute variables in deny conditions", err)
+            return ev.deny.get((rule.index, res), "")
+        return ""
     if rule.any_pattern:
         outs = ev.anypattern.get((rule.index, res), [])
         if st == PASS:
@@ -333,17 +356,17 @@ def policy_has_validate(policy: dict) -> bool:
 
 
 def apply(policy_paths: list[str], resource_paths: list[str], policy_report: bool = False, device: int = 0,
-          out=sys.stdout, evaluation_fn=None, gpus: int = 1) -> tuple[ResultCounts, list]:
+          out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False) -> tuple[ResultCounts, list]:
     """applyCommandHelper (apply_command.go:147-310) for resource files. Returns counts and the
     policyreport infos. ``evaluation_fn(policies, resources) -> Evaluation`` replaces the device
     evaluation (tests of the host logic)."""
     policies = load_policies(policy_paths)
     resources = load_resources(resource_paths)
-    return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus)
+    return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny)
 
 
 def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool = False, device: int = 0,
-               out=sys.stdout, evaluation_fn=None, gpus: int = 1) -> tuple[ResultCounts, list]:
+               out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False) -> tuple[ResultCounts, list]:
     mutated = autogen.mutate_policies(policies)
     if len(mutated) > 0 and len(resources) > 0:
         msg_p = "1 policy" if len(mutated) <= 1 else f"{len(policies)} policies"
@@ -355,7 +378,7 @@ def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool 
     active = [p for p in mutated if not has_unset_variables(p)]
     infos = []
     if active and resources:
-        ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus)))(active, resources)
+        ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus, deny=deny)))(active, resources)
         for pi, pol in enumerate(active):
             if not policy_has_validate(pol):
                 continue
@@ -413,13 +436,13 @@ def build_policy_reports(infos: list) -> list[dict]:
 
 
 def run_test(spec: dict, policies: list[dict], resources: list[dict], device: int = 0,
-             evaluation_fn=None) -> list[dict]:
+             evaluation_fn=None, deny: bool = False) -> list[dict]:
     """`kyverno test` result matching (pkg/kyverno/test/test_command.go:347-494) for validate rules:
     the expected rule name falls back to autogen-<rule> / autogen-cronjob-<rule> when the policy's
     response does not hold it; a rule absent from the response is `skip`. Returns one row per
     expected result with the actual result ("cpu" for rules routed to the reference engine)."""
     mutated = autogen.mutate_policies(policies)
-    ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, messages=False)))(mutated, resources)
+    ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, messages=False, deny=deny)))(mutated, resources)
     rows = []
     for t in spec["results"]:
         want = t.get("result") or t.get("status")
@@ -459,13 +482,15 @@ def main(argv: list[str] | None = None) -> int:
     a.add_argument("--policy-report", action="store_true", help="Generates policy report when passed")
     a.add_argument("--device", type=int, default=0, help="HIP device (first device with --gpus)")
     a.add_argument("--gpus", type=int, default=1, help="shard the resources over this many devices")
+    a.add_argument("--device-deny", action="store_true",
+                   help="evaluate validate.deny rules of the device forms on the GPU (KV_COMPILE_DENY)")
     t = sub.add_parser("test", help="run tests from a directory holding test.yaml")
     t.add_argument("dir")
     t.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     if args.cmd == "apply":
         try:
-            rc, _ = apply(args.policies, args.resource, args.policy_report, args.device, gpus=args.gpus)
+            rc, _ = apply(args.policies, args.resource, args.policy_report, args.device, gpus=args.gpus, deny=args.device_deny)
         except msgvars.MessageVariableError as e:
             # the Go CLI dies in buildErrorMessage (msgRaw.(string), validation.go:519-524): a
             # panic, exit status 2

@@ -291,6 +291,8 @@ struct RuleRec {
   uint32_t n_alts;          // 0: pattern; >0: anyPattern alternatives
   uint32_t dyn;             // pattern variables: 1 + dynamic-rule index (DevBatch::dyn_st), 0 none
   uint32_t pre;             // preconditions: 1 + condition-set index (DevBatch::pre_st), 0 none
+  uint32_t deny;            // validate.deny on the device: 1 + deny-set index (DevBatch::deny_st), 0 none;
+                            // such a rule has no pattern program (prog is unused)
 };
 // RR_META_LABELS / RR_META_ANN: the pattern's ExpandInMetadata sites read labels / annotations
 // (wildcards.go:69-139 panics on a resource whose map of that tag is not a string map)

@@ -399,6 +399,10 @@ struct DevBatchRes {
   // HIP-event time
   DevBuf presets, preents, preoutc, pretruth, preunk, prest;
   double pre_ms = 0;
+  // validate.deny on the device (kvcond.h): the fold's tables, the plane kv_deny_kernel wrote and
+  // its HIP-event time
+  DevBuf dnsets, dnents, dnoutc, dntruth, dnunk, dnerr, dnoos, dnst;
+  double deny_ms = 0;
   DevBatch view{};
 };
 
@@ -1162,8 +1166,37 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     v.n_pre_sets = n_sets;
     v.pre_st = (const uint8_t*)d->prest.p;
   }
+  // validate.deny: the fold's tables and its kernel, as the gate's
+  DenyHost dn;
+  const uint32_t n_dsets = (uint32_t)ps.dsets.size();
+  if (n_dsets && !b.res.empty()) {
+    build_deny(ps, b, &dn);
+    auto up = [&](DevBuf& buf, const std::vector<uint32_t>& src) {
+      buf.alloc(std::max<size_t>(src.size() * sizeof(uint32_t), 16), device);
+      if (!src.empty())
+        HIPCHK(hipMemcpyAsync(buf.p, src.data(), src.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us));
+    };
+    up(d->dnsets, dn.sets);
+    up(d->dnents, dn.ents);
+    up(d->dnoutc, dn.outc);
+    up(d->dntruth, dn.truth);
+    up(d->dnunk, dn.unk);
+    up(d->dnerr, dn.err);
+    up(d->dnoos, dn.oos);
+    d->dnst.alloc((size_t)n_dsets * b.res.size(), device);
+    v.deny_sets = (const uint32_t*)d->dnsets.p;
+    v.deny_ents = (const uint32_t*)d->dnents.p;
+    v.deny_outc = (const uint32_t*)d->dnoutc.p;
+    v.deny_truth = (const uint32_t*)d->dntruth.p;
+    v.deny_unk = (const uint32_t*)d->dnunk.p;
+    v.deny_err = (const uint32_t*)d->dnerr.p;
+    v.deny_oos = (const uint32_t*)d->dnoos.p;
+    v.deny_words = dn.words;
+    v.n_deny_sets = n_dsets;
+    v.deny_st = (const uint8_t*)d->dnst.p;
+  }
   d->view_dev.upload_raw(&d->view, sizeof(DevBatch), device);
-  hipEvent_t pe0 = nullptr, pe1 = nullptr;
+  hipEvent_t pe0 = nullptr, pe1 = nullptr, de0 = nullptr, de1 = nullptr;
   if (v.pre_st) {
     HIPCHK(hipEventCreate(&pe0));
     HIPCHK(hipEventCreate(&pe1));
@@ -1171,7 +1204,21 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     HIPCHK(launch_precond((const DevBatch*)d->view_dev.p, v.n_res, n_sets, (uint8_t*)d->prest.p, us));
     HIPCHK(hipEventRecord(pe1, us));
   }
+  if (v.deny_st) {
+    HIPCHK(hipEventCreate(&de0));
+    HIPCHK(hipEventCreate(&de1));
+    HIPCHK(hipEventRecord(de0, us));
+    HIPCHK(launch_deny((const DevBatch*)d->view_dev.p, v.n_res, n_dsets, (uint8_t*)d->dnst.p, us));
+    HIPCHK(hipEventRecord(de1, us));
+  }
   HIPCHK(hipStreamSynchronize(us));
+  if (de0) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, de0, de1));
+    d->deny_ms = ms;
+    (void)hipEventDestroy(de0);
+    (void)hipEventDestroy(de1);
+  }
   if (pe0) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, pe0, pe1));
@@ -2365,6 +2412,9 @@ void run(kv_policyset* ps, kv_batch* bt, const char* ctx_json, const std::vector
     // the precondition gate's kernel (HIP events; it ran when the batch was first uploaded)
     if (!ps->ps.csets.empty() && !s.parts.empty() && s.parts[0]->batch_ref)
       out->phases.push_back({"precond", s.parts[0]->batch_ref->pre_ms});
+    // the deny fold's kernel, likewise
+    if (!ps->ps.dsets.empty() && !s.parts.empty() && s.parts[0]->batch_ref)
+      out->phases.push_back({"deny", s.parts[0]->batch_ref->deny_ms});
     s.fetch(out, t);
   }
   if (getenv("KVGPU_VERBOSE")) {  // host-boundary breakdown
@@ -2391,7 +2441,7 @@ int kv_compile(const char* policies_json, size_t len, uint32_t flags, kv_policys
   try {
     auto* s = new kv_policyset();
     try {
-      compile_policies(policies_json, len, &s->ps);
+      compile_policies(policies_json, len, &s->ps, flags & KV_COMPILE_DENY);
       if (flags & KV_COMPILE_SPECIALIZE) {
         s->jit = std::make_unique<JitImage>();
         const uint32_t chunk = jit_chunk_rules();
@@ -2681,6 +2731,7 @@ int kv_result_path(const kv_result* r, uint32_t rule, uint64_t res, char* buf, s
   res = r->sidx(res);
   size_t o = (size_t)rule * r->n_res + res;
   if (const_cast<kv_result*>(r)->st_store()[o] != ST_FAIL) return KV_E_INVALID;
+  if (r->ps->ps.rules[rule].deny) return KV_E_INVALID;  // (a deny FAIL has no failing path, as a gated SKIP)
   ErrRec e;
   const Batch* bt = nullptr;
   if (!r->err(rule, res, &e, &bt)) return KV_E_INVALID;
@@ -2805,6 +2856,68 @@ int kv_result_precond_message(const kv_result* r, uint32_t rule, uint64_t res, c
   }
 }
 
+int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
+  if (!r) return KV_E_INVALID;
+  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
+  if (!r->has_status()) return KV_E_INVALID;  // counts-only result: no statuses were fetched
+  const uint64_t s = r->store_of(res);          // (the batch's tables are in store order)
+  res = r->sidx(res);
+  try {
+    const RuleRec& rr = r->ps->ps.rules[rule];
+    if (!rr.deny || const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res] != ST_ERROR) return 0;
+    const ResultPart* p = r->part_of(s);
+    if (!p) return 0;
+    const kv_batch* kb = p->shard ? p->shard.get() : r->b;
+    // the error recomputed from the batch's outcome rows: the first unresolved string of the block
+    const std::string e = deny_error_host(r->ps->ps, kb->b, rr.deny - 1, s - p->lo);
+    if (e.empty()) return 0;
+    // ruleError(rule, Validation, "failed to substitute variables in deny conditions", err)
+    // (validation.go:301-304)
+    const std::string m = "failed to substitute variables in deny conditions: " + e;
+    if (buf && cap) {
+      size_t n = std::min(cap - 1, m.size());
+      memcpy(buf, m.data(), n);
+      buf[n] = 0;
+    }
+    return (int)m.size();
+  } catch (const std::bad_alloc&) {  // (the lazily built store-order status matrix)
+    return KV_E_NOMEM;
+  } catch (const std::exception&) {
+    return KV_E_INVALID;
+  }
+}
+
+int kv_policyset_deny_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings) {
+  if (!ps) return KV_E_INVALID;
+  if (sets) *sets = (uint32_t)ps->ps.dsets.size();
+  if (conditions) *conditions = (uint32_t)ps->ps.dconds.size();
+  if (strings) *strings = (uint32_t)ps->ps.dkeys.size();
+  return 0;
+}
+
+int kv_batch_deny_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint64_t n) {
+  if (!ps || !b || !status) return KV_E_INVALID;
+  if (set >= ps->ps.dsets.size() || n != b->b.res.size()) return KV_E_RANGE;
+  try {
+    DenyHost h;
+    build_deny(ps->ps, b->b, &h);
+    const std::vector<uint32_t>& order = b->b.order;  // store index -> caller index (empty: identity)
+    for (uint64_t s = 0; s < n; s++) status[order.empty() ? s : order[s]] = deny_status_host(h, set, n, s);
+    return 0;
+  } catch (const std::bad_alloc&) {
+    return KV_E_NOMEM;
+  } catch (const std::exception&) {
+    return KV_E_INVALID;
+  }
+}
+
+int kv_rule_deny_set(const kv_policyset* ps, uint32_t rule, uint32_t* set) {
+  if (!ps || !set) return KV_E_INVALID;
+  if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
+  *set = ps->ps.rules[rule].deny;
+  return 0;
+}
+
 int kv_condition_eval(const char* condition_json, size_t len, int* result) {
   if (!condition_json || !result) return KV_E_INVALID;
   try {
@@ -2857,7 +2970,7 @@ int kv_result_failures(const kv_result* cr, uint64_t* n, const uint32_t** rule, 
             const uint8_t st = row[q];
             if (st != ST_FAIL && st != ST_ERROR && st != ST_SKIP) continue;
             uint32_t id = KV_PATH_NONE;
-            if (st == ST_FAIL) {
+            if (st == ST_FAIL && !ps.rules[rl].deny) {  // (a deny FAIL has an empty record: no failing path)
               const ErrRec8 c = p.r8(rl, i);
               if ((c.w0 & ERR8_WIDE) && !p.recw.empty()) {
                 const std::string path = render_path(ps, r->batch_of(p), p.recw[i]);

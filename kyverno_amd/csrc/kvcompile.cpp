@@ -1413,7 +1413,7 @@ static bool compile_pattern_program(Compiler& C, const std::vector<PV>& patterns
   return true;
 }
 
-void compile_policies(const char* json, size_t len, PolicySet* ps) {
+void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flags) {
   JDoc d;
   parse_json(json, len, NUM_FLOAT, &d);
   const JNode& root = d.at(d.root);
@@ -1451,7 +1451,7 @@ void compile_policies(const char* json, size_t len, PolicySet* ps) {
         compile_block(C, d, d.get(rn, "exclude"), false, rr, rh);
         int64_t val = d.get(rn, "validate");
         bool has_validate = false, patP = false, anyP = false, denyP = false, feP = false;
-        int64_t pat = -1, ap = -1;
+        int64_t pat = -1, ap = -1, deny = -1;
         std::string msg;
         if (val >= 0 && d.at((uint32_t)val).t == J_MAP) {
           uint32_t v = (uint32_t)val;
@@ -1462,6 +1462,7 @@ void compile_policies(const char* json, size_t len, PolicySet* ps) {
           patP = pat >= 0 && d.at((uint32_t)pat).t != J_NULL;
           anyP = ap >= 0 && d.at((uint32_t)ap).t != J_NULL;
           denyP = dn >= 0 && d.at((uint32_t)dn).t != J_NULL;
+          deny = dn;
           feP = fe >= 0 && d.at((uint32_t)fe).t != J_NULL;
           has_validate = !msg.empty() || patP || anyP || denyP || feP;
         }
@@ -1469,19 +1470,23 @@ void compile_policies(const char* json, size_t len, PolicySet* ps) {
         int64_t ctx = d.get(rn, "context"), pre = d.get(rn, "preconditions");
         bool ctxP = ctx >= 0 && d.at((uint32_t)ctx).t == J_ARR && d.at((uint32_t)ctx).count > 0;
         bool preP = pre >= 0 && d.at((uint32_t)pre).t != J_NULL;
-        uint32_t pre_set = 0;
+        uint32_t pre_set = 0, deny_set = 0;
+        // validate.deny on the device (KV_COMPILE_DENY, kvcond.h): a rule without pattern /
+        // anyPattern (validate() ignores deny beside one, validation.go:187-198)
+        const bool denyD = (flags & 2u /* KV_COMPILE_DENY */) && denyP && !patP && !anyP;
         rr.route = 0;
         if (!has_validate) { rr.route = 2; rh.route_reason = "no validate"; }
         else if (feP) { rr.route = 1; rh.route_reason = "foreach"; }
         else if (ctxP) { rr.route = 1; rh.route_reason = "context"; }
         // preconditions: evaluated on the device where the block and the rule's pattern are in
         // scope (kvcond.h); everything else keeps the CPU route and its reason
-        else if (preP && ((!patP && !anyP) || (pre_set = compile_preconditions(*ps, d, (uint32_t)pre)) == 0)) {
+        else if (preP && ((!patP && !anyP && !denyD) || (pre_set = compile_preconditions(*ps, d, (uint32_t)pre)) == 0)) {
           rr.route = 1;
           rh.route_reason = "preconditions";
         }
         else if (!patP && !anyP) {
-          if (denyP) { rr.route = 1; rh.route_reason = "deny"; }
+          if (denyD && (deny_set = compile_deny(*ps, d, (uint32_t)deny)) != 0) rr.deny = deny_set;  // no program
+          else if (denyP) { rr.route = 1; rh.route_reason = "deny"; }
           else { rr.route = 2; rh.route_reason = "no pattern"; }  // validate() returns nil
         } else {
           PV doc = to_pv(d, patP ? (uint32_t)pat : (uint32_t)ap);
@@ -1540,7 +1545,9 @@ void compile_policies(const char* json, size_t len, PolicySet* ps) {
           // is not a form the kernels have)
           rr.route = 1;
           rr.const_status = 0;
-          rh.route_reason = "preconditions";
+          // (a deny block outside the device forms behind preconditions inside them: the deny
+          // block is the obstacle)
+          if (!denyD) rh.route_reason = "preconditions";
           rh.const_message.clear();
         } else if (preP && pre_set != 0xFFFFFFFFu) {
           rr.pre = pre_set;

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "kvpre.h"
+#include "kvdeny.h"
 
 namespace kvh {
 
@@ -368,8 +369,20 @@ std::string pv_key(const PV& p) {  // interning key of a constant operand
   }
 }
 
+// The interning tables a block compiles into: the preconditions' (PolicySet::ckeys / conds) or
+// the deny blocks' (dkeys / dconds). strs (deny): every condition string of the block, those of
+// conditions folded to a constant included.
+struct CondSpace {
+  std::vector<std::string>& keys;
+  std::vector<CondRec>& conds;
+  std::unordered_map<std::string, uint32_t>& key_id;
+  std::unordered_map<std::string, uint32_t>& cond_id;
+  std::vector<uint32_t>* strs;
+  size_t any_strs = 0;  // how many of them the `any` list gave (it is compiled first)
+};
+
 // one condition: 0 constant false, 1 constant true, 2 dynamic (*rec), -1 outside the scope
-int compile_condition(PolicySet& ps, const JDoc& d, uint32_t node, uint32_t* rec) {
+int compile_condition(CondSpace& sp, const JDoc& d, uint32_t node, uint32_t* rec) {
   if (d.at(node).t != J_MAP) return -1;
   const int64_t kn = d.get(node, "key"), on = d.get(node, "operator"), vn = d.get(node, "value");
   if (kn < 0 || vn < 0) return -1;
@@ -403,31 +416,34 @@ int compile_condition(PolicySet& ps, const JDoc& d, uint32_t node, uint32_t* rec
     const bool r = cond_eval(op, key, value, &range);
     return range ? -1 : (r ? 1 : 0);
   }
-  if (op == CD_UNKNOWN) return 0;
+  if (op == CD_UNKNOWN && !sp.strs) return 0;
   const std::string& text = kv ? key.s : value.s;
-  auto ck = ps.ckey_id.find(text);
-  if (ck == ps.ckey_id.end()) {
-    ck = ps.ckey_id.emplace(text, (uint32_t)ps.ckeys.size()).first;
-    ps.ckeys.push_back(text);
+  auto ck = sp.key_id.find(text);
+  if (ck == sp.key_id.end()) {
+    ck = sp.key_id.emplace(text, (uint32_t)sp.keys.size()).first;
+    sp.keys.push_back(text);
   }
+  if (sp.strs) sp.strs->push_back(ck->second);
+  if (op == CD_UNKNOWN) return 0;  // (deny: the string still has to resolve)
   CondRec c;
   c.op = op;
   c.var_is_key = kv;
   c.cstr = ck->second;
   c.other = kv ? value : key;
   const std::string id = std::to_string(op) + (kv ? "k" : "v") + std::to_string(c.cstr) + "|" + pv_key(c.other);
-  auto it = ps.cond_id.find(id);
-  if (it == ps.cond_id.end()) {
-    it = ps.cond_id.emplace(id, (uint32_t)ps.conds.size()).first;
-    ps.conds.push_back(std::move(c));
+  auto it = sp.cond_id.find(id);
+  if (it == sp.cond_id.end()) {
+    it = sp.cond_id.emplace(id, (uint32_t)sp.conds.size()).first;
+    sp.conds.push_back(std::move(c));
   }
   *rec = it->second;
   return 2;
 }
 
-}  // namespace
-
-uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
+// An any / all block or the old list (utils.go:392-406 transformConditions, util.go:220-262)
+// into *out, constants folded. False when the block is outside the device scope (the interning
+// tables are left as they were); *always: no condition is left and none is a constant false.
+bool compile_block(CondSpace& sp, const JDoc& d, uint32_t node, CondSet* out, bool* always) {
   const JNode& n = d.at(node);
   int64_t any = -1, all = -1;
   bool old_form = false;
@@ -438,29 +454,31 @@ uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
       const std::string_view k = d.key(d.at(c));
       if (k == "any") any = c;
       else if (k == "all") all = c;
-      else return 0;  // "unknown field" (util.go:223-239)
+      else return false;  // "unknown field" (util.go:223-239)
     }
   } else {
-    return 0;
+    return false;
   }
   // checkpoint of the interning tables: a block outside the scope leaves nothing behind
-  const size_t ck0 = ps.ckeys.size(), cd0 = ps.conds.size();
+  const size_t ck0 = sp.keys.size(), cd0 = sp.conds.size();
   auto rollback = [&]() {
-    for (size_t i = ck0; i < ps.ckeys.size(); i++) ps.ckey_id.erase(ps.ckeys[i]);
-    ps.ckeys.resize(ck0);
-    for (auto it = ps.cond_id.begin(); it != ps.cond_id.end();)
-      it = it->second >= cd0 ? ps.cond_id.erase(it) : std::next(it);
-    ps.conds.resize(cd0);
-    return 0u;
+    for (size_t i = ck0; i < sp.keys.size(); i++) sp.key_id.erase(sp.keys[i]);
+    sp.keys.resize(ck0);
+    for (auto it = sp.cond_id.begin(); it != sp.cond_id.end();)
+      it = it->second >= cd0 ? sp.cond_id.erase(it) : std::next(it);
+    sp.conds.resize(cd0);
+    if (sp.strs) sp.strs->clear();
+    return false;
   };
-  CondSet s;
+  CondSet& s = *out;
+  s = CondSet();
   bool any_true = false;
   auto list = [&](int64_t ln, bool is_any) {
     const JNode& l = d.at((uint32_t)ln);
     if (l.t != J_ARR) return false;
     for (uint32_t c = l.first; c < l.first + l.count; c++) {
       uint32_t rec = 0;
-      const int r = compile_condition(ps, d, c, &rec);
+      const int r = compile_condition(sp, d, c, &rec);
       if (r < 0) return false;
       if (is_any) {
         if (r == 1) any_true = true;
@@ -483,6 +501,7 @@ uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
     if (all >= 0 && d.at((uint32_t)all).t == J_NULL) all = -1;
     if (any >= 0) {
       if (!list(any, true)) return rollback();
+      if (sp.strs) sp.any_strs = sp.strs->size();
       if (any_true) s.any.clear();
       else {
         s.any_present = true;
@@ -496,19 +515,35 @@ uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
     s.all.clear();
     s.any_present = false;
   }
-  if (!s.const_false && !s.any_present && s.all.empty()) return 0xFFFFFFFFu;
+  *always = !s.const_false && !s.any_present && s.all.empty();
   // a lane loads each condition string once: its conditions follow each other
   auto by_str = [&](uint32_t a, uint32_t b) {
-    return ps.conds[a].cstr != ps.conds[b].cstr ? ps.conds[a].cstr < ps.conds[b].cstr : a < b;
+    return sp.conds[a].cstr != sp.conds[b].cstr ? sp.conds[a].cstr < sp.conds[b].cstr : a < b;
   };
   std::sort(s.any.begin(), s.any.end(), by_str);
   std::sort(s.all.begin(), s.all.end(), by_str);
   s.any.erase(std::unique(s.any.begin(), s.any.end()), s.any.end());
   s.all.erase(std::unique(s.all.begin(), s.all.end()), s.all.end());
+  return true;
+}
+
+std::string set_key(const CondSet& s) {  // interning key of a folded block
   std::string id = s.const_false ? "F" : (s.any_present ? "A" : "-");
   for (uint32_t c : s.any) id += std::to_string(c) + ",";
   id += "|";
   for (uint32_t c : s.all) id += std::to_string(c) + ",";
+  return id;
+}
+
+}  // namespace
+
+uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
+  CondSpace sp{ps.ckeys, ps.conds, ps.ckey_id, ps.cond_id, nullptr};
+  CondSet s;
+  bool always = false;
+  if (!compile_block(sp, d, node, &s, &always)) return 0;
+  if (always) return 0xFFFFFFFFu;
+  const std::string id = set_key(s);
   auto it = ps.cset_id.find(id);
   if (it == ps.cset_id.end()) {
     it = ps.cset_id.emplace(id, (uint32_t)ps.csets.size()).first;
@@ -517,13 +552,103 @@ uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
   return it->second + 1;
 }
 
+uint32_t compile_deny(PolicySet& ps, const JDoc& d, uint32_t node) {
+  // validate.deny: {conditions: <any / all block | old list>} (kyverno.Deny); `deny: {}` and a
+  // missing or null `conditions` stay on the CPU route
+  if (d.at(node).t != J_MAP) return 0;
+  const JNode& n = d.at(node);
+  int64_t cn = -1;
+  for (uint32_t c = n.first; c < n.first + n.count; c++) {
+    if (d.key(d.at(c)) != "conditions") return 0;
+    cn = c;
+  }
+  if (cn < 0 || d.at((uint32_t)cn).t == J_NULL) return 0;
+  DenySet s;
+  CondSpace sp{ps.dkeys, ps.dconds, ps.dkey_id, ps.dcond_id, &s.strs};
+  bool always = false;
+  if (!compile_block(sp, d, (uint32_t)cn, &s.fold, &always)) return 0;
+  // the strings in the order of the substitution's traversal with canonical key order, as for
+  // pattern strings (kvvars.cpp): `all` before `any`, each list by index
+  for (size_t i = sp.any_strs; i < s.strs.size(); i++) s.order.push_back(s.strs[i]);
+  for (size_t i = 0; i < sp.any_strs; i++) s.order.push_back(s.strs[i]);
+  std::sort(s.strs.begin(), s.strs.end());
+  s.strs.erase(std::unique(s.strs.begin(), s.strs.end()), s.strs.end());
+  std::string id = set_key(s.fold) + "#";
+  for (uint32_t k : s.order) id += std::to_string(k) + ",";
+  auto it = ps.dset_id.find(id);
+  if (it == ps.dset_id.end()) {
+    it = ps.dset_id.emplace(id, (uint32_t)ps.dsets.size()).first;
+    ps.dsets.push_back(std::move(s));
+  }
+  return it->second + 1;
+}
+
 // ------------------------------------------------------------------ per batch
+namespace {
+
+// Outcome ids per [condition string][res] of the C condition strings at column k0 of the
+// outcome rows, and per condition the truth / unknown planes over the outcomes its string takes
+// in this batch. err / oos (deny): per string, the outcomes that are a substitution error /
+// outside the device scope.
+void fill_planes(const PolicySet& ps, const Batch& b, const std::vector<CondRec>& conds, size_t k0, size_t C,
+                 std::vector<uint32_t>* outc, std::vector<uint32_t>* truth, std::vector<uint32_t>* unk, uint32_t* words,
+                 std::vector<uint32_t>* err, std::vector<uint32_t>* oos, const char* who) {
+  const uint64_t n = b.res.size();
+  const size_t K = ps.vout_width();
+  // outcome ids, [condition string][res] (a lane's load is coalesced)
+  outc->resize(C * n);
+  if (b.vout.size() != K * n) throw std::runtime_error(std::string(who) + ": outcome rows do not match the policy set");
+  for (uint64_t r = 0; r < n; r++)
+    for (size_t c = 0; c < C; c++) (*outc)[c * n + r] = b.vout[r * K + k0 + c];
+  // the outcomes each condition string takes in this batch
+  const size_t T = b.vout_tab.size();
+  const uint32_t W = (uint32_t)std::max<size_t>((T + 31) / 32, 1);
+  *words = W;
+  std::vector<uint32_t> seen(C * W, 0);
+  for (size_t c = 0; c < C; c++)
+    for (uint64_t r = 0; r < n; r++) {
+      const uint32_t o = (*outc)[c * n + r];
+      seen[c * W + o / 32] |= 1u << (o % 32);
+    }
+  if (err) {
+    err->assign(C * W, 0);
+    oos->assign(C * W, 0);
+    for (size_t c = 0; c < C; c++)
+      for (size_t o = 0; o < T; o++) {
+        if (!((seen[c * W + o / 32] >> (o % 32)) & 1u)) continue;
+        const char t = b.vout_tab[o].empty() ? 'C' : b.vout_tab[o][0];
+        if (t == 'E') (*err)[c * W + o / 32] |= 1u << (o % 32);
+        else if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N' || t == 'M')) (*oos)[c * W + o / 32] |= 1u << (o % 32);
+      }
+  }
+  truth->assign(conds.size() * W, 0);
+  unk->assign(conds.size() * W, 0);
+  for (size_t ci = 0; ci < conds.size(); ci++) {
+    const CondRec& c = conds[ci];
+    for (size_t o = 0; o < T; o++) {
+      if (!((seen[c.cstr * W + o / 32] >> (o % 32)) & 1u)) continue;
+      const std::string& oc = b.vout_tab[o];
+      const char t = oc.empty() ? 'C' : oc[0];
+      if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N')) {  // a map / array, outside the scope
+        (*unk)[ci * W + o / 32] |= 1u << (o % 32);
+        continue;
+      }
+      const PV v = outcome_value(oc);
+      bool range = false;
+      const bool r = c.var_is_key ? cond_eval(c.op, v, c.other, &range) : cond_eval(c.op, c.other, v, &range);
+      if (range) (*unk)[ci * W + o / 32] |= 1u << (o % 32);
+      else if (r) (*truth)[ci * W + o / 32] |= 1u << (o % 32);
+    }
+  }
+}
+
+}  // namespace
+
 void build_pre(const PolicySet& ps, const Batch& b, PreHost* out) {
   PreHost& h = *out;
   h = PreHost();
   if (ps.csets.empty()) return;
-  const uint64_t n = b.res.size();
-  const size_t K = ps.vout_width(), k0 = ps.vkeys.size(), C = ps.ckeys.size();
+  const size_t k0 = ps.vkeys.size(), C = ps.ckeys.size();
   for (const CondSet& s : ps.csets) {
     h.sets.push_back((uint32_t)(h.ents.size() / 2));
     h.sets.push_back((uint32_t)s.any.size() | (s.any_present ? 0x80000000u : 0u));
@@ -532,45 +657,51 @@ void build_pre(const PolicySet& ps, const Batch& b, PreHost* out) {
     for (uint32_t c : s.any) { h.ents.push_back(ps.conds[c].cstr); h.ents.push_back(c); }
     for (uint32_t c : s.all) { h.ents.push_back(ps.conds[c].cstr); h.ents.push_back(c); }
   }
-  // outcome ids, [condition string][res] (a lane's load is coalesced)
-  h.outc.resize(C * n);
-  if (b.vout.size() != K * n) throw std::runtime_error("build_pre: outcome rows do not match the policy set");
-  for (uint64_t r = 0; r < n; r++)
-    for (size_t c = 0; c < C; c++) h.outc[c * n + r] = b.vout[r * K + k0 + c];
-  // the outcomes each condition string takes in this batch
-  const size_t T = b.vout_tab.size();
-  const uint32_t W = (uint32_t)std::max<size_t>((T + 31) / 32, 1);
-  h.words = W;
-  std::vector<uint32_t> seen(C * W, 0);
-  for (size_t c = 0; c < C; c++)
-    for (uint64_t r = 0; r < n; r++) {
-      const uint32_t o = h.outc[c * n + r];
-      seen[c * W + o / 32] |= 1u << (o % 32);
+  fill_planes(ps, b, ps.conds, k0, C, &h.outc, &h.truth, &h.unk, &h.words, nullptr, nullptr, "build_pre");
+}
+
+void build_deny(const PolicySet& ps, const Batch& b, DenyHost* out) {
+  DenyHost& h = *out;
+  h = DenyHost();
+  if (ps.dsets.empty()) return;
+  for (const DenySet& s : ps.dsets) {
+    h.sets.push_back((uint32_t)(h.ents.size() / 2));
+    const size_t e0 = h.ents.size();
+    // one run of entries per string of the block, in string order: its `any` conditions, its
+    // `all` conditions, or a bare entry where no condition of the string is left to evaluate
+    for (uint32_t k : s.strs) {
+      const size_t e1 = h.ents.size();
+      for (uint32_t c : s.fold.any)
+        if (ps.dconds[c].cstr == k) { h.ents.push_back(k); h.ents.push_back(c); }
+      for (uint32_t c : s.fold.all)
+        if (ps.dconds[c].cstr == k) { h.ents.push_back(k); h.ents.push_back(c | KV_DENY_ALL); }
+      if (h.ents.size() == e1) { h.ents.push_back(k); h.ents.push_back(KV_DENY_NOCOND); }
     }
-  h.truth.assign(ps.conds.size() * W, 0);
-  h.unk.assign(ps.conds.size() * W, 0);
-  for (size_t ci = 0; ci < ps.conds.size(); ci++) {
-    const CondRec& c = ps.conds[ci];
-    for (size_t o = 0; o < T; o++) {
-      if (!((seen[c.cstr * W + o / 32] >> (o % 32)) & 1u)) continue;
-      const std::string& oc = b.vout_tab[o];
-      const char t = oc.empty() ? 'C' : oc[0];
-      if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N')) {  // a map / array, outside the scope
-        h.unk[ci * W + o / 32] |= 1u << (o % 32);
-        continue;
-      }
-      const PV v = outcome_value(oc);
-      bool range = false;
-      const bool r = c.var_is_key ? cond_eval(c.op, v, c.other, &range) : cond_eval(c.op, c.other, v, &range);
-      if (range) h.unk[ci * W + o / 32] |= 1u << (o % 32);
-      else if (r) h.truth[ci * W + o / 32] |= 1u << (o % 32);
-    }
+    h.sets.push_back((uint32_t)((h.ents.size() - e0) / 2));
+    h.sets.push_back(s.fold.any_present ? 1u : 0u);
+    h.sets.push_back(s.fold.const_false ? 1u : 0u);
   }
+  fill_planes(ps, b, ps.dconds, ps.vkeys.size() + ps.ckeys.size(), ps.dkeys.size(), &h.outc, &h.truth, &h.unk, &h.words,
+              &h.err, &h.oos, "build_deny");
 }
 
 uint8_t pre_status_host(const PreHost& h, uint32_t set, uint64_t n_res, uint64_t r) {
   return (uint8_t)kv_pre_lane(h.sets.data(), h.ents.data(), h.outc.data(), h.truth.data(), h.unk.data(), h.words, set,
                               n_res, r);
+}
+
+uint8_t deny_status_host(const DenyHost& h, uint32_t set, uint64_t n_res, uint64_t r) {
+  return (uint8_t)kv_deny_lane(h.sets.data(), h.ents.data(), h.outc.data(), h.truth.data(), h.unk.data(), h.err.data(),
+                               h.oos.data(), h.words, set, n_res, r);
+}
+
+std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, uint64_t r) {
+  const size_t K = ps.vout_width(), k0 = ps.vkeys.size() + ps.ckeys.size();
+  for (uint32_t k : ps.dsets[set].order) {
+    const std::string& o = b.vout_tab[b.vout[r * K + k0 + k]];
+    if (!o.empty() && o[0] == 'E') return o.substr(1);
+  }
+  return std::string();
 }
 
 }  // namespace kvh

@@ -57,4 +57,39 @@ void build_pre(const PolicySet& ps, const Batch& b, PreHost* out);
 // the gate of one (set, resource) on the host: 0 pass, ST_SKIP, ST_CPU (as kv_pre_lane)
 uint8_t pre_status_host(const PreHost& h, uint32_t set, uint64_t n_res, uint64_t r);
 
+// validate.deny on the device (KV_COMPILE_DENY; pkg/engine/validation.go:299-339 validateDeny).
+// The reference substitutes the deny conditions per (rule, resource) with the default resolver
+// (variables.SubstituteAll, vars.go:76-80,315-317: an unresolved variable is an error, and the
+// whole document is substituted before anything is evaluated), converts them as the preconditions
+// (utils.go:392-406) and evaluates the same any / all fold: true is FAIL, false is PASS. Here the
+// preconditions' machinery runs with another resolver and another verdict, and no pattern walk:
+//  * compile (compile_deny): blocks, conditions and strings are interned in tables of their own
+//    (PolicySet::dsets / dconds / dkeys). A block whose conditions fold to a constant is still a
+//    deny set, so preconditions compose with it. The strings are keyed by their text alone: the
+//    string's path inside the conditions document shows only in the reference's non-NotFound
+//    errors, all of which are outside the device scope here (outcome "C");
+//  * ingest: deny strings resolve with the strict resolver into further columns of Batch::vout;
+//  * per batch (build_deny): truth / unknown planes per condition as for the preconditions, and
+//    per string an error plane (the outcome is a substitution error) and an out-of-scope plane;
+//  * device (kvdeny.h kv_deny_lane, kv_deny_kernel): DevBatch::deny_st[set][res], the final
+//    status of the pair once match / exclude and the preconditions let it through.
+// Parses the `deny` node of a rule: 0 when it is outside the device scope (the rule stays
+// CPU-routed, reason "deny"), else 1 + the interned deny set's index.
+uint32_t compile_deny(PolicySet& ps, const JDoc& d, uint32_t node);
+
+struct DenyHost {
+  std::vector<uint32_t> sets;   // 4 words per set: first entry, entries, any_present, const_false
+  std::vector<uint32_t> ents;   // 2 words per entry: string, condition | KV_DENY_ALL, or KV_DENY_NOCOND; by string
+  std::vector<uint32_t> outc;   // outcome id per [deny string][res]
+  std::vector<uint32_t> truth, unk;  // [condition][words] bit planes over outcome ids
+  std::vector<uint32_t> err, oos;    // [string][words]: the outcome is an error / outside the device scope
+  uint32_t words = 1;
+};
+void build_deny(const PolicySet& ps, const Batch& b, DenyHost* out);
+// one (deny set, resource) on the host: ST_PASS, ST_FAIL, ST_ERROR or ST_CPU (as kv_deny_lane)
+uint8_t deny_status_host(const DenyHost& h, uint32_t set, uint64_t n_res, uint64_t r);
+// the error of the first unresolved string of the set on store resource r, in the order of the
+// reference's traversal with canonical key order ("" when every string resolves)
+std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, uint64_t r);
+
 }  // namespace kvh

@@ -19,6 +19,10 @@ hipError_t launch_validate(const DevPS* P, const DevBatch* B, uint32_t n_res, co
 // (DevBatch::pre_*), once per (policy set, batch) with the batch's other device preparation.
 hipError_t launch_precond(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* pre_st, hipStream_t stream);
 
+// The deny fold of a batch (kvdeny.h): deny_st[set][res] for every deny set of B (DevBatch::deny_*),
+// with the precondition gate.
+hipError_t launch_deny(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* deny_st, hipStream_t stream);
+
 // Match tables of a pass (DevPS::mt_*): `words` = mt_ns_words + mt_ann_words +
 // mt_sel_words rows, max_entities = max(n_nsm, n_asets, n_lsets).
 hipError_t launch_mtab(const DevPS* P, const DevBatch* B, uint32_t words, uint32_t max_entities, uint32_t* ns,

@@ -147,6 +147,21 @@ struct DevBatch {
   const uint32_t* pre_unk;
   uint32_t pre_words, n_pre_sets;
   const uint8_t* pre_st;
+  // validate.deny on the device (kvcond.h DenyHost, kvdeny.h): the deny sets (4 words each),
+  // their entries ordered by string (string, condition | flags), the outcome id per
+  // [deny string][res], the truth / unknown planes per [condition][deny_words], the error and
+  // out-of-scope planes per [string][deny_words], and the plane kv_deny_kernel writes once per
+  // batch: deny_st[set * n_res + res] = ST_PASS, ST_FAIL, ST_ERROR or ST_CPU, the final status
+  // of a deny rule's pair that match / exclude and the preconditions let through
+  const uint32_t* deny_sets;
+  const uint32_t* deny_ents;
+  const uint32_t* deny_outc;
+  const uint32_t* deny_truth;
+  const uint32_t* deny_unk;
+  const uint32_t* deny_err;
+  const uint32_t* deny_oos;
+  uint32_t deny_words, n_deny_sets;
+  const uint8_t* deny_st;
 };
 
 // ------------------------------------------------------------------ path columns

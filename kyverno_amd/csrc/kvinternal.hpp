@@ -73,6 +73,15 @@ struct CondSet {
   bool any_present = false, const_false = false;
   std::vector<uint32_t> any, all;  // CondRec indices, ordered by condition string
 };
+// One interned deny block: its fold (CondRec indices into PolicySet::dconds; no conditions left
+// and not const_false: the block always holds) and every condition string of the block
+// (PolicySet::dkeys indices, sorted), those of folded-away conditions included: an unresolved
+// variable anywhere in the block is an error before anything is evaluated (vars.go:315-317).
+struct DenySet {
+  CondSet fold;
+  std::vector<uint32_t> strs;
+  std::vector<uint32_t> order;  // the same strings in the substitution's traversal order (repeats kept)
+};
 
 // Projection trie over resource key paths referenced by any compiled pattern
 // or match block. Arrays are transparent: `elem` is the element trie.
@@ -198,13 +207,21 @@ struct PolicySet {
   std::vector<CondRec> conds;
   std::vector<CondSet> csets;
   std::unordered_map<std::string, uint32_t> ckey_id, cond_id, cset_id;
-  // columns of a Batch::vout row: the pattern-variable keys, then the condition strings
-  size_t vout_width() const { return vkeys.size() + ckeys.size(); }
+  // validate.deny on the device (KV_COMPILE_DENY, kvcond.cpp compile_deny): the same three
+  // tables for the deny blocks (RuleRec::deny - 1), in a key space of their own: deny strings
+  // resolve under the strict resolver (an unresolved variable is an error, not "")
+  std::vector<std::string> dkeys;
+  std::vector<CondRec> dconds;
+  std::vector<DenySet> dsets;
+  std::unordered_map<std::string, uint32_t> dkey_id, dcond_id, dset_id;
+  // columns of a Batch::vout row: the pattern-variable keys, then the condition strings of the
+  // preconditions, then those of the deny blocks
+  size_t vout_width() const { return vkeys.size() + ckeys.size() + dkeys.size(); }
 };
 
 // Compiles a JSON list of (already autogen-expanded) ClusterPolicy/Policy
-// objects. Throws std::runtime_error on malformed input.
-void compile_policies(const char* json, size_t len, PolicySet* ps);
+// objects (flags: kv_compile's KV_COMPILE_DENY). Throws std::runtime_error on malformed input.
+void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flags = 0);
 
 // Host memory of the large store arrays of an ingested batch. libkvgpu (kvapi.cpp)
 // installs a pooled page-locked allocator, so the store's H2D upload is one direct

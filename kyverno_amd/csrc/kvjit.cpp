@@ -54,6 +54,9 @@ std::string hex32(uint32_t v) {
   snprintf(b, sizeof b, "0x%08xu", v);
   return b;
 }
+// rules whose status is final after match / route: the other routes, and device deny rules
+// (RuleRec::deny: their status is a byte of DevBatch::deny_st, they have no pattern program)
+bool no_program(const RuleRec& rr) { return rr.route != 0 || rr.deny != 0; }
 std::string u32(uint32_t v) { return std::to_string(v) + "u"; }
 std::string u64(uint64_t v) { return std::to_string(v) + "ull"; }
 std::string i64(int64_t v) {
@@ -1513,7 +1516,8 @@ struct Gen {
     // (pattern-variable rules stay out of groups: their substitution status is decided per
     // member before the walk, and a group's record layout may be per resource slot)
     // (nor rules with preconditions: their gate is applied per rule before the walk)
-    if (rr.route != 0 || rr.dyn || rr.pre) return "";
+    // (nor deny rules: they have no program)
+    if (rr.route != 0 || rr.dyn || rr.pre || rr.deny) return "";
     const uint32_t b = rr.prog, e = prog_end(ps, b);
     std::ostringstream f;
     auto rel = [&](uint32_t t) { return (int64_t)t - (int64_t)b; };
@@ -1651,7 +1655,7 @@ struct Gen {
     size_t K = 0;
     for (uint32_t q = 0; q < nr; q++) {
       const uint32_t ri = ch.rules[q];
-      if (ps.rules[ri].route != 0) continue;
+      if (no_program(ps.rules[ri])) continue;
       auto git = gof.find(ri);
       if (git != gof.end() && ginfo[git->second].members[0] != ri) continue;  // a group member
       RGen g = analyze(ri);
@@ -1807,7 +1811,10 @@ struct Gen {
           if (rr.dyn)
             k << "    else if (B.dyn_st[(size_t)" << (rr.dyn - 1) << "u * n_res + r]) rs" << s << " = FIN_ | B.dyn_st[(size_t)"
               << (rr.dyn - 1) << "u * n_res + r];\n";
-          k << "    else rs" << s << " = " << u32(rr.prog) << ";\n";
+          if (rr.deny)  // validate.deny (validation.go:195-197): the fold's plane is the status
+            k << "    else rs" << s << " = FIN_ | B.deny_st[(size_t)" << (rr.deny - 1) << "u * n_res + r];\n";
+          else
+            k << "    else rs" << s << " = " << u32(rr.prog) << ";\n";
           break;
       }
       k << "  }\n";
@@ -2057,7 +2064,7 @@ struct Gen {
     }
     // rules of other routes are final after match / route
     for (uint32_t q = 0; q < nr; q++)
-      if (ps.rules[ch.rules[q]].route != 0) k << match_code(q) << store(q);
+      if (no_program(ps.rules[ch.rules[q]])) k << match_code(q) << store(q);
     k << body.str();
     return k.str();
   }
@@ -2266,7 +2273,7 @@ struct Gen {
   // / resume pc, error kind, cursors per depth, loop counters and error indices per loop
   // level, anchor bitsets, wildcard-key node); 0 for rules of other routes.
   uint32_t rule_weight(uint32_t ri) {
-    if (ps.rules[ri].route != 0) return 0;
+    if (no_program(ps.rules[ri])) return 0;
     const RGen g = analyze(ri);
     uint32_t w = 2 + g.maxd;
     if (!g.loops.empty()) w += 4 * (g.max_level + 1);
@@ -2411,7 +2418,7 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
       diag + kPrelude + std::string("\nusing namespace kv;\n\n") +
       "__device__ __noinline__ bool kv_dleaf_impl(const DevBatch& B, const Node* __restrict__ N, uint32_t dp, Node vn);\n\n";
   for (uint32_t ri = 0; ri < ps.rules.size(); ri++)
-    if (ps.rules[ri].route == 0) g.leaf_classes(ri);
+    if (!no_program(ps.rules[ri])) g.leaf_classes(ri);
   for (uint32_t ri = 0; ri < ps.rules.size(); ri++) g.match_fn(ri);
   out->chunks.clear();
   const uint32_t n = (uint32_t)ps.rules.size();
@@ -2422,7 +2429,7 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
     // rules grouped by the kinds they match first, walk signature second (round 3: C5 4.07 ->
     // 3.72 ms against signature only, C3 10.19 -> 10.32)
     for (uint32_t ri = 0; ri < n; ri++)
-      order.push_back({ps.rules[ri].route == 0 ? "0" + rule_kind_key(ps, ri) + "#" + rule_signature(ps, ri) : "1", ri});
+      order.push_back({!no_program(ps.rules[ri]) ? "0" + rule_kind_key(ps, ri) + "#" + rule_signature(ps, ri) : "1", ri});
     std::stable_sort(order.begin(), order.end());
     // One kernel per range of the signature order: its rules run as one fused block (every
     // array they walk is walked once per resource, all rules of the range in one loop over

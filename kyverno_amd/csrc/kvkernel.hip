@@ -34,6 +34,7 @@ using namespace kv;
 #include "kvfac.h"
 #include "kvcol.h"
 #include "kvpre.h"
+#include "kvdeny.h"
 
 // ------------------------------------------------------------------ kernel
 extern "C" __global__ __launch_bounds__(KV_WG) __attribute__((amdgpu_waves_per_eu(4))) void kv_validate_kernel(const DevPS* __restrict__ Pp,
@@ -91,6 +92,8 @@ extern "C" __global__ __launch_bounds__(KV_WG) __attribute__((amdgpu_waves_per_e
         // preconditions precede pattern substitution (validation.go:175-193): SKIP or CPU is final
         else if (uni(rr.pre) && B.pre_st[(size_t)(uni(rr.pre) - 1u) * n_res + r]) st = B.pre_st[(size_t)(uni(rr.pre) - 1u) * n_res + r];
         else if (uni(rr.dyn) && B.dyn_st[(size_t)(uni(rr.dyn) - 1u) * n_res + r]) st = B.dyn_st[(size_t)(uni(rr.dyn) - 1u) * n_res + r];
+        // validate.deny (validation.go:195-197): the fold's plane is the status, no pattern program
+        else if (uni(rr.deny)) st = B.deny_st[(size_t)(uni(rr.deny) - 1u) * n_res + r];
         else run = true;
       }
       uint32_t ekind = 0, eflags = 0, epn = 0, ekey = ABSENT, eres = ABSENT;
@@ -376,6 +379,32 @@ hipError_t launch_precond(const DevBatch* B, uint32_t n_res, uint32_t n_sets, ui
   if (n_res == 0 || n_sets == 0) return hipSuccess;
   hipLaunchKernelGGL(kv_precond_kernel, dim3((n_res + KV_WG - 1) / KV_WG, n_sets < KV_PRE_YMAX ? n_sets : KV_PRE_YMAX),
                      dim3(KV_WG), 0, stream, B, n_res, n_sets, pre_st);
+  return hipGetLastError();
+}
+}  // namespace kv
+
+// ---------------------------------------------------------------------------
+// Deny fold (kvcond.h, kvdeny.h): the same launch shape as the precondition gate: one lane per
+// resource, grid.x = workgroups of 256 resources, grid.y = deny sets (a workgroup walks sets
+// blockIdx.y, + gridDim.y, ...). The set's entry list is wave-uniform; per string one coalesced
+// 32-bit load of the lane's outcome id and two bit tests in the string's planes, per condition two
+// more. One byte per (set, resource): ST_PASS, ST_FAIL, ST_ERROR or ST_CPU; lanes past n_res
+// write nothing.
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_deny_kernel(const DevBatch* __restrict__ Bp, uint32_t n_res,
+                                                                    uint32_t n_sets, uint8_t* __restrict__ deny_st) {
+  const DevBatch& B = *Bp;
+  const uint64_t r = (uint64_t)blockIdx.x * KV_WG + threadIdx.x;
+  if (r >= n_res) return;
+  for (uint32_t s = blockIdx.y; s < n_sets; s += gridDim.y)
+    deny_st[(size_t)s * n_res + r] = (uint8_t)kv_deny_lane(B.deny_sets, B.deny_ents, B.deny_outc, B.deny_truth, B.deny_unk,
+                                                           B.deny_err, B.deny_oos, B.deny_words, s, n_res, r);
+}
+
+namespace kv {
+hipError_t launch_deny(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* deny_st, hipStream_t stream) {
+  if (n_res == 0 || n_sets == 0) return hipSuccess;
+  hipLaunchKernelGGL(kv_deny_kernel, dim3((n_res + KV_WG - 1) / KV_WG, n_sets < KV_PRE_YMAX ? n_sets : KV_PRE_YMAX),
+                     dim3(KV_WG), 0, stream, B, n_res, n_sets, deny_st);
   return hipGetLastError();
 }
 }  // namespace kv

@@ -25,11 +25,16 @@ import decimal
 import re
 
 __all__ = ["MessageVariableError", "UnsupportedMessageVariable", "substitute_message", "has_variable",
-           "go_json_marshal"]
+           "go_json_marshal", "MessageVariableNotFound"]
 
 
 class MessageVariableError(ValueError):
     """The reference engine panics on this message (unresolvable or non-string substitution)."""
+
+
+class MessageVariableNotFound(MessageVariableError):
+    """The substitution fails with an error (a key the resource does not have), where
+    buildErrorMessage panics and getDenyMessage returns the message as written."""
 
 
 class UnsupportedMessageVariable(ValueError):
@@ -99,7 +104,7 @@ def _query(expr: str, context) -> object:
         key = m.group(1) if m.group(1) is not None else re.sub(r"\\(.)", r"\1", m.group(2))
         if isinstance(cur, dict):
             if key not in cur:
-                raise MessageVariableError(f'Unknown key "{key}" in path')
+                raise MessageVariableNotFound(f'Unknown key "{key}" in path')
             cur = cur[key]
         else:
             cur = None

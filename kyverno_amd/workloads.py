@@ -140,6 +140,21 @@ def c2_precondition_policies() -> list[dict]:
     return pols
 
 
+def c2_deny_policies() -> list[dict]:
+    """The deny twin of ``c2_precondition_policies``: the 100 C2 rules, each with its pattern
+    replaced by ``validate.deny`` over one of the same eight blocks (rule i: block i mod 8), to be
+    compiled with ``PolicySet(..., deny=True)``: the workload of the deny fold's measurement
+    (DESIGN.md §3 *Deny*)."""
+    import copy
+
+    pols = c2_policies()
+    for i, r in enumerate(pols[0]["spec"]["rules"]):
+        r["validate"] = {"message": r["validate"].get("message", ""),
+                         "deny": {"conditions": copy.deepcopy(C2_PRECONDITION_SETS[i % len(C2_PRECONDITION_SETS)])}}
+    pols[0]["metadata"]["name"] = "c2-pod-rules-deny"
+    return pols
+
+
 C3_KIND_MIX = 2  # kv_synth stream of C3: Pods/Deployments/Services 60/25/15 over 1 000 namespaces
 C3_NAMESPACES = 1000
 

@@ -1,0 +1,266 @@
+"""validate.deny on the device, without a GPU (kvcond.cpp compile_deny / build_deny, kvdeny.h;
+reference pkg/engine/validation.go:299-339): the deny model against the reference's own test cases
+(tests/golden/deny.json, the duration-test rules of tests/golden/cli.json), rule routing with the
+compile flag on and off, interning of deny sets, the exported symbols, and the host fold
+(`kv_batch_deny_fold`, the per-lane function the device kernel runs) against the model."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import cond_model
+import deny_data as dd
+import deny_model
+from kyverno_amd import _native, autogen, batch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def model(orc):
+    return deny_model.Model(orc)
+
+
+# ------------------------------------------------------------------ the model, pinned
+def _model_verdict(orc, model, policy, resource):
+    """(status name, messages) of Rules[0] by the decomposition, for a one-rule policy."""
+    e = dd.Expected(orc, policy, [resource])
+    st = int(e.status[0, 0])
+    return {dd.PASS: "pass", dd.FAIL: "fail", dd.ERROR: "error", dd.SKIP: "skip"}[st], e.messages.get((0, 0))
+
+
+def test_golden_fixture_shape():
+    assert [c["name"] for c in dd.CASES] == ["VariablesInMessageAreResolved", "EmptyStringInDenyCondition",
+                                             "StringInDenyCondition"]
+    assert all(c["src"].startswith("pkg/engine/validation_test.go:") for c in dd.CASES)
+    dur = [p for p in dd.CLI_SIMPLE["policies"] if p["metadata"]["name"] == "duration-test"]
+    assert len(dur) == 1 and len(dur[0]["spec"]["rules"]) == 4
+    assert all("deny" in r["validate"] for r in dur[0]["spec"]["rules"])
+
+
+@pytest.mark.parametrize("case", dd.CASES, ids=lambda c: c["name"])
+def test_model_matches_golden(orc, model, case):
+    st, msgs = _model_verdict(orc, model, case["policy"], case["resource"])
+    assert (st in ("pass", "skip")) == case["successful"], (st, msgs)  # EngineResponse.IsSuccessful
+    if case["status"] is not None:
+        assert st == case["status"]
+        assert msgs == [case["message"]]
+
+
+def test_model_golden_details(orc, model):
+    """What the two IsSuccessful cases come down to: the annotation map is absent, so the strict
+    resolver fails (ERROR, not a FAIL of `"" != "true"` as under the preconditions resolver); with
+    the annotation "true" the condition is false."""
+    by = {c["name"]: c for c in dd.CASES}
+    st, msgs = _model_verdict(orc, model, by["EmptyStringInDenyCondition"]["policy"], by["EmptyStringInDenyCondition"]["resource"])
+    assert (st, msgs) == ("error", ['failed to substitute variables in deny conditions: Unknown key "annotations" in path'])
+    st, msgs = _model_verdict(orc, model, by["StringInDenyCondition"]["policy"], by["StringInDenyCondition"]["resource"])
+    assert (st, msgs) == ("pass", ["validation rule 'match-service-type' passed."])
+
+
+def test_model_matches_cli_duration_case(orc, model):
+    """test/cli/test/simple, policy duration-test: fail / pass / fail / pass on test-lifetime-fail."""
+    case = dd.CLI_SIMPLE
+    pol = next(p for p in autogen.mutate_policies(case["policies"]) if p["metadata"]["name"] == "duration-test")
+    res = next(r for r in case["resources"] if r["metadata"]["name"] == "test-lifetime-fail")
+    e = dd.Expected(orc, pol, [res])
+    got = {r["name"]: {dd.PASS: "pass", dd.FAIL: "fail"}[int(e.status[i, 0])] for i, r in enumerate(pol["spec"]["rules"])}
+    want = {t["rule"]: t["result"] for t in case["results"] if t["policy"] == "duration-test"}
+    assert len(want) == 4 and {k: got[k] for k in want} == want
+    assert e.messages[(0, 0)] == ["Pod lifetime exceeds limit of 8h"]  # no "validation error:" prefix
+
+
+def test_model_operators_are_the_conditions_table(model):
+    """The deny model evaluates with cond_model.Model's operators (pinned by conditions.json)."""
+    import precond_data as pd
+
+    assert isinstance(model, cond_model.Model)
+    for row in pd.ROWS[::7]:
+        assert model.evaluate(row["key"], row["operator"], row["value"]) == row["result"], row
+
+
+# ------------------------------------------------------------------ routing
+V = "{{request.object.metadata.labels.app}}"
+
+
+def _cond(key=V, op="Equals", value="busybox"):
+    return {"key": key, "operator": op, "value": value}
+
+
+IN_SCOPE = {
+    "old-list": [_cond()],
+    "any": {"any": [_cond()]},
+    "all": {"all": [_cond()]},
+    "any-all": {"any": [_cond(), _cond(value="nginx")], "all": [_cond(op="NotEquals", value="x")]},
+    "empty-list": [],
+    "empty-map": {},
+    "in": {"all": [_cond(op="In", value=["a", "b"])]},
+    "allnotin": {"all": [_cond(op="AllNotIn", value="a")]},
+    "gt": {"all": [_cond(op="GreaterThan", value="8h")]},
+    "unknown-operator": {"all": [_cond(op="Resembles")]},
+    "variable-in-value": {"all": [_cond(key="busybox", value=V)]},
+    "no-variables": {"all": [_cond(key="a", value="a")], "any": [_cond(key=1, op="GreaterThan", value=0)]},
+    "in-string": {"all": [_cond(key="x-" + V + "-{{request.object.metadata.namespace}}")]},
+    "quoted": {"all": [_cond(key='{{ request.object.metadata.annotations."pod.kubernetes.io/lifetime" }}')]},
+}
+OUT_OF_SCOPE = {
+    "request-operation": {"all": [_cond(key="{{request.operation}}", value="CREATE")]},
+    "user-info": {"all": [_cond(key="{{request.userInfo.username}}")]},
+    "at": {"all": [_cond(key="{{@}}")]},
+    "custom-jmespath": {"all": [_cond(key="{{request.object.spec.containers[*].image}}")]},
+    "both-sides": {"all": [_cond(value="{{request.object.metadata.name}}")]},
+    "variable-in-list": {"all": [_cond(key="a", op="In", value=["x", V])]},
+    "variable-in-map": {"all": [_cond(value={"a": V})]},
+    "reference": {"all": [_cond(value="$(./../key)")]},
+    "escape": {"all": [_cond(value="\\{{literal}}")]},
+    "variable-in-operator": {"all": [_cond(op="{{request.object.metadata.name}}")]},
+    "duration-operator": {"all": [_cond(op="DurationGreaterThan", value="1h")]},
+    "map-operand": {"all": [_cond(value={"a": "b"})]},
+    "list-key": {"all": [_cond(key=["a", "b"], op="AnyIn", value=V)]},
+    "missing-key": {"all": [{"operator": "Equals", "value": "busybox"}]},
+    "missing-value": {"all": [{"key": V, "operator": "Equals"}]},
+    "any-empty": {"any": []},
+}
+PATTERN = {"spec": {"containers": [{"image": "*:*"}]}}
+PRE = {"all": [_cond(key="{{request.object.metadata.labels.tier}}", value="web")]}
+PRE_OUT = {"all": [_cond(key="{{request.operation}}", value="CREATE")]}
+
+
+def _routing_policy():
+    def rule(name, validate, **more):
+        return {"name": name, "match": dd.POD, "validate": validate, **more}
+    rules = [rule(n, {"message": "m", "deny": {"conditions": c}}) for n, c in list(IN_SCOPE.items()) + list(OUT_OF_SCOPE.items())]
+    rules += [
+        rule("x-empty-deny", {"deny": {}}),
+        rule("x-null-conditions", {"deny": {"conditions": None}}),
+        rule("x-behind-preconditions", {"deny": {"conditions": [_cond()]}}, preconditions=PRE),
+        rule("x-preconditions-out", {"deny": {"conditions": [_cond()]}}, preconditions=PRE_OUT),
+        rule("x-deny-out-behind-preconditions", {"deny": {"conditions": OUT_OF_SCOPE["at"]}}, preconditions=PRE),
+        rule("x-context", {"deny": {"conditions": [_cond()]}},
+             context=[{"name": "cm", "configMap": {"name": "a", "namespace": "b"}}]),
+        rule("x-foreach", {"foreach": [{"list": "request.object.spec.containers", "deny": {"conditions": [_cond()]}}]}),
+        rule("x-pattern-beside-deny", {"message": "m", "pattern": PATTERN, "deny": {"conditions": [_cond()]}}),
+        rule("x-plain-pattern", {"message": "m", "pattern": PATTERN}),
+        rule("x-pattern-behind-preconditions", {"message": "m", "pattern": PATTERN}, preconditions=PRE),
+    ]
+    return dd.pd._policy("deny-routing", rules)
+
+
+def test_routing_flag_on():
+    """One rule per in-scope form (GPU route, a deny set) and per out-of-scope form (CPU route,
+    reason "deny", or "preconditions" where they are the obstacle); a pattern beside deny wins."""
+    ps = batch.PolicySet([_routing_policy()], deny=True)
+    got = {r.name: (r.route, r.route_reason) for r in ps.rules}
+    sets = dict(zip([r.name for r in ps.rules], ps.deny_info["rule_sets"]))
+    for name in IN_SCOPE:
+        assert got[name] == (batch.ROUTE_GPU, "") and sets[name] > 0, (name, got[name], sets[name])
+    for name in OUT_OF_SCOPE:
+        assert got[name] == (batch.ROUTE_CPU, "deny") and sets[name] == 0, (name, got[name])
+    assert got["x-empty-deny"] == got["x-null-conditions"] == (batch.ROUTE_CPU, "deny")
+    assert got["x-behind-preconditions"] == (batch.ROUTE_GPU, "") and sets["x-behind-preconditions"] > 0
+    assert got["x-preconditions-out"] == (batch.ROUTE_CPU, "preconditions")
+    assert got["x-deny-out-behind-preconditions"] == (batch.ROUTE_CPU, "deny")
+    assert got["x-context"] == (batch.ROUTE_CPU, "context")
+    assert got["x-foreach"] == (batch.ROUTE_CPU, "foreach")
+    for name in ("x-pattern-beside-deny", "x-plain-pattern", "x-pattern-behind-preconditions"):
+        assert got[name] == (batch.ROUTE_GPU, "") and sets[name] == 0, name
+    assert [r.deny for r in ps.rules] == [s > 0 for s in ps.deny_info["rule_sets"]]
+    # a block without variables is a deny set like any other, not a constant route
+    assert ps.rules[[r.name for r in ps.rules].index("no-variables")].route != batch.ROUTE_CONSTANT
+
+
+def test_routing_flag_off():
+    """Without KV_COMPILE_DENY nothing changes: every deny rule is (CPU, "deny"), or "preconditions"
+    behind any preconditions; no deny sets; the preconditions' tables are those of the pattern rules."""
+    pol = _routing_policy()
+    ps = batch.PolicySet([pol])
+    got = {r.name: (r.route, r.route_reason) for r in ps.rules}
+    for name in list(IN_SCOPE) + list(OUT_OF_SCOPE) + ["x-empty-deny", "x-null-conditions"]:
+        assert got[name] == (batch.ROUTE_CPU, "deny"), (name, got[name])
+    for name in ("x-behind-preconditions", "x-preconditions-out", "x-deny-out-behind-preconditions"):
+        assert got[name] == (batch.ROUTE_CPU, "preconditions"), (name, got[name])
+    assert got["x-context"] == (batch.ROUTE_CPU, "context") and got["x-foreach"] == (batch.ROUTE_CPU, "foreach")
+    for name in ("x-pattern-beside-deny", "x-plain-pattern", "x-pattern-behind-preconditions"):
+        assert got[name] == (batch.ROUTE_GPU, ""), name
+    info = ps.deny_info
+    assert (info["sets"], info["conditions"], info["strings"]) == (0, 0, 0) and not any(info["rule_sets"])
+    assert not any(r.deny for r in ps.rules)
+    assert ps.precondition_info == {"sets": 1, "conditions": 1, "strings": 1}
+    # ... and the flag leaves the preconditions of pattern rules as they are
+    only_patterns = dd.pd._policy("p", [r for r in pol["spec"]["rules"] if r["name"].startswith("x-p")])
+    assert batch.PolicySet([only_patterns], deny=True).precondition_info == \
+        batch.PolicySet([only_patterns]).precondition_info == {"sets": 1, "conditions": 1, "strings": 1}
+
+
+def test_interning():
+    """30 deny rules over 3 distinct blocks compile to 3 deny sets; the precondition tables stay
+    empty (deny strings have a key space of their own)."""
+    blocks = [{"all": [_cond()]},
+              {"any": [_cond(value="a"), _cond(key="{{request.object.metadata.labels.tier}}", op="In", value=["x", "y"])]},
+              [_cond(), _cond(key="{{request.object.metadata.labels.tier}}", op="NotEquals", value="z")]]
+    rules = [{"name": f"r{i}", "match": dd.POD, "validate": {"deny": {"conditions": json.loads(json.dumps(blocks[i % 3]))}}}
+             for i in range(30)]
+    ps = batch.PolicySet([dd.pd._policy("interning", rules)], deny=True)
+    assert all(r.route == batch.ROUTE_GPU and r.deny for r in ps.rules)
+    info = ps.deny_info
+    assert (info["sets"], info["conditions"], info["strings"]) == (3, 4, 2), info
+    assert info["rule_sets"] == [1 + i % 3 for i in range(30)]
+    assert ps.precondition_info == {"sets": 0, "conditions": 0, "strings": 0}
+
+
+def test_exported_symbols():
+    lib = _native.lib()
+    for s in ("kv_result_deny_message", "kv_policyset_deny_sets", "kv_rule_deny_set", "kv_batch_deny_fold"):
+        assert s in _native.EXPORTED_SYMBOLS and getattr(lib, s) is not None
+    hdr = open(os.path.join(ROOT, "include", "kvgpu.h")).read()
+    assert "KV_COMPILE_DENY = 2" in hdr
+    assert "int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);" in hdr
+    assert "int kv_policyset_deny_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings);" in hdr
+    assert "int kv_rule_deny_set(const kv_policyset* ps, uint32_t rule, uint32_t* set);" in hdr
+    assert batch.COMPILE_DENY == 2
+
+
+def test_workload_twin():
+    from kyverno_amd import workloads
+
+    pols = workloads.c2_deny_policies()
+    assert len(pols[0]["spec"]["rules"]) == 100
+    ps = batch.PolicySet(pols, deny=True)
+    assert all(r.route == batch.ROUTE_GPU and r.deny for r in ps.rules)
+    assert ps.deny_info["sets"] == 8
+    assert all((r.route, r.route_reason) == (batch.ROUTE_CPU, "deny") for r in batch.PolicySet(pols).rules)
+
+
+# ------------------------------------------------------------------ the host fold against the model
+def test_crafted_expected_covers_the_cases(orc):
+    e = dd.Expected(orc, dd.crafted_policy(), dd.crafted_resources(513))
+    e.check_honest(full=True)
+    tiers = {json.dumps((r["metadata"].get("labels") or {}).get("tier")) for r in e.resources}
+    assert len(tiers) >= 70
+
+
+@pytest.mark.parametrize("n", [1, 65, 513])
+def test_host_fold_matches_model(orc, n):
+    """kv_batch_deny_fold (kv_deny_lane on the host, over the tables the device gets) per deny set,
+    against the deny model alone: ERROR / CPU / FAIL / PASS of the block on every resource,
+    whatever match and the preconditions say."""
+    pol, ress = dd.crafted_policy(), dd.crafted_resources(n)
+    model = deny_model.Model(orc)
+    ps = batch.PolicySet([pol], deny=True)
+    assert all((r.route, r.route_reason) == (batch.ROUTE_GPU, "") for r in ps.rules)
+    fold = ps.deny_fold(batch.Batch(ps, ress))
+    sets = ps.deny_info["rule_sets"]
+    names = [r["name"] for r in pol["spec"]["rules"]]
+    assert sets[names.index("shared-a")] == sets[names.index("shared-b")] > 0
+    assert sets[names.index("plain-pattern")] == 0
+    code = {"error": dd.ERROR, deny_model.UNKNOWN: dd.CPU, "fail": dd.FAIL, "pass": dd.PASS}
+    bad = []
+    for ri, rule in enumerate(pol["spec"]["rules"]):
+        if not dd.is_deny(rule):
+            continue
+        for k, res in enumerate(ress):
+            want = code[model.deny(rule["validate"]["deny"]["conditions"], res)[0]]
+            if fold[sets[ri] - 1, k] != want:
+                bad.append((rule["name"], k, int(fold[sets[ri] - 1, k]), want))
+    assert not bad, bad[:20]

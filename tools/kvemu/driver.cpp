@@ -29,6 +29,7 @@
 #include "../../kyverno_amd/csrc/kvjit.hpp"
 #include "../../kyverno_amd/csrc/kvcond.h"
 #include "../../kyverno_amd/csrc/kvpre.h"
+#include "../../kyverno_amd/csrc/kvdeny.h"
 
 using namespace kv;
 using namespace kvh;
@@ -97,7 +98,8 @@ int main(int argc, char** argv) {
     const std::string pol = slurp(argv[1]), res = slurp(argv[2]);
     std::string ctx = strcmp(argv[3], "-") ? slurp(argv[3]) : std::string();
     PolicySet ps;
-    compile_policies(pol.data(), pol.size(), &ps);
+    // KVEMU_COMPILE_FLAGS: kv_compile's flags (2: KV_COMPILE_DENY), as the binary's source was generated
+    compile_policies(pol.data(), pol.size(), &ps, getenv("KVEMU_COMPILE_FLAGS") ? (uint32_t)atoi(getenv("KVEMU_COMPILE_FLAGS")) : 0u);
     Batch whole;
     ingest_resources(ps, res.data(), res.size(), nullptr, &whole);
     // KVEMU_SHARDS=G: evaluate G contiguous shards (kvshard.cpp, as kv_validate_devices does)
@@ -242,6 +244,29 @@ int main(int argc, char** argv) {
           pre_st[(size_t)s * B.n_res + r] = (uint8_t)kv_pre_lane(B.pre_sets, B.pre_ents, B.pre_outc, B.pre_truth,
                                                                  B.pre_unk, B.pre_words, s, B.n_res, r);
       B.pre_st = pre_st.data();
+    }
+    // validate.deny (as dev_batch): the fold's tables, then every (set, resource) through the
+    // per-lane function kv_deny_kernel runs (kvdeny.h)
+    DenyHost dn;
+    std::vector<uint8_t> deny_st;
+    if (!ps.dsets.empty() && !b.res.empty()) {
+      build_deny(ps, b, &dn);
+      B.deny_sets = dn.sets.data();
+      B.deny_ents = dn.ents.data();
+      B.deny_outc = dn.outc.data();
+      B.deny_truth = dn.truth.data();
+      B.deny_unk = dn.unk.data();
+      B.deny_err = dn.err.data();
+      B.deny_oos = dn.oos.data();
+      B.deny_words = dn.words;
+      B.n_deny_sets = (uint32_t)ps.dsets.size();
+      deny_st.assign((size_t)B.n_deny_sets * B.n_res, 0xEE);
+      for (uint32_t s = 0; s < B.n_deny_sets; s++)
+        for (uint32_t r = 0; r < B.n_res; r++)
+          deny_st[(size_t)s * B.n_res + r] = (uint8_t)kv_deny_lane(B.deny_sets, B.deny_ents, B.deny_outc, B.deny_truth,
+                                                                   B.deny_unk, B.deny_err, B.deny_oos, B.deny_words, s,
+                                                                   B.n_res, r);
+      B.deny_st = deny_st.data();
     }
     // path columns of the image (as dev_batch: built once per batch)
     std::vector<uint32_t> pcol_erow;
