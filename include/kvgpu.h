@@ -51,7 +51,20 @@ enum {
    * list on the other, or both constant. A pair is FAIL when the conditions hold, PASS when they
    * do not, ERROR when a variable of the block does not resolve (kv_result_deny_message), CPU
    * when the device cannot decide (a map or array operand). Other forms keep the CPU route. */
-  KV_COMPILE_DENY = 2
+  KV_COMPILE_DENY = 2,
+  /* evaluate validate.foreach rules on the device (opt-in, independent of KV_COMPILE_DENY;
+   * without it every such rule is KV_ROUTE_CPU, reason "foreach"). In scope: validate.foreach a
+   * list of exactly one entry {list, preconditions?, deny} with nothing beside it in validate and
+   * no rule-level context; rule preconditions absent or of the device forms; `list` a bare
+   * request.object field / quoted-field / index chain; deny.conditions as KV_COMPILE_DENY
+   * accepts them and the entry's preconditions a map of any / all of the device forms, both over
+   * {{element<chain>}} and {{request.object<chain>}} variables. Per pair: the elements are
+   * evaluated in order; the first FAIL (the conditions hold), ERROR (a deny variable does not
+   * resolve) or CPU (the device cannot decide) element is the pair's status; else PASS when an
+   * element passed, SKIP "rule skipped" when the list is missing or empty or every element is
+   * gated by the entry's preconditions. CPU also when the list is not a list of maps (or a
+   * map), holds a null anywhere, or has more than 65536 elements. */
+  KV_COMPILE_FOREACH = 4
 };
 
 /* kv_validate modes (bit set). KV_MODE_SCOPES adds per-scope counts
@@ -81,6 +94,7 @@ typedef struct kv_rule_info {
   uint32_t any_pattern;     /* 1 for anyPattern rules */
   uint32_t const_status;    /* KV_ROUTE_CONSTANT */
   const char* const_message;
+  uint32_t foreach_set;     /* 1 + the foreach set of a device foreach rule (KV_COMPILE_FOREACH), else 0 */
 } kv_rule_info;
 
 /* Compile a JSON list of ClusterPolicy/Policy objects (already through
@@ -115,6 +129,21 @@ int kv_rule_deny_set(const kv_policyset* ps, uint32_t rule, uint32_t* set);
  * _CPU, before match / exclude and the preconditions are applied. `n` must be the batch's
  * resource count. Diagnostics and tests; needs no GPU. */
 int kv_batch_deny_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint64_t n);
+/* validate.foreach rules evaluated on the device (KV_COMPILE_FOREACH): interned foreach sets
+ * (list, entry preconditions, deny block), distinct lists, conditions with a variable operand and
+ * element-scoped condition strings (keyed by list, text and resolver). Any may be NULL. */
+int kv_policyset_foreach_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* lists, uint32_t* conditions,
+                              uint32_t* strings);
+/* *set = 1 + the foreach set of rule `rule`, 0 for a rule that is not a device foreach rule
+ * (kv_rule_deny_set is 0 for a foreach rule) */
+int kv_rule_foreach_set(const kv_policyset* ps, uint32_t rule, uint32_t* set);
+/* The foreach fold of foreach set `set` (0-based) over an ingested batch, on the host: the twin
+ * of kv_foreach_elem_kernel and kv_foreach_fin_kernel. status[i] of resource i (caller order) is
+ * KV_STATUS_PASS / _FAIL / _ERROR / _SKIP / _CPU before match / exclude and the rule's
+ * preconditions are applied; elem[i] (may be NULL) the index of the deciding element in its list,
+ * 0xFFFFFFFF without one. `n` must be the batch's resource count. Needs no GPU. */
+int kv_batch_foreach_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint32_t* elem,
+                          uint64_t n);
 int kv_rule_info_get(const kv_policyset* ps, uint32_t rule, kv_rule_info* out);
 
 /* Ingest resources (JSON array or NDJSON of unstructured objects; numbers typed
@@ -175,7 +204,8 @@ int kv_device_trim(int device);
  * KV_E_RANGE past the last phase. Diagnostics of the host boundary (no reference counterpart).
  * "precond" (policy sets with device-evaluated preconditions): the HIP-event time of the
  * precondition gate's kernel, which runs once per batch when the batch is uploaded. "deny"
- * (policy sets with device deny rules): the same for the deny fold's kernel. */
+ * (policy sets with device deny rules): the same for the deny fold's kernel. "foreach" (device
+ * foreach rules): the same for the foreach fold's two kernels and the clearing of their keys. */
 int kv_result_phase(const kv_result* r, uint32_t i, const char** name, double* ms);
 /* counts[(scope * n_rules + rule) * 8 + status] (KV_MODE_SCOPES) */
 int kv_result_scope_counts(const kv_result* r, const int64_t** counts, uint32_t* n_scopes);
@@ -215,6 +245,18 @@ int kv_result_precond_message(const kv_result* r, uint32_t rule, uint64_t res, c
  * map there: its order is not fixed). Negative codes as kv_result_subst_error. The PASS and FAIL
  * messages are formed by the caller from kv_rule_info. */
 int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
+
+/* Foreach rules (KV_COMPILE_FOREACH). kv_result_foreach_element: *index = the index in its list
+ * of the element that decided a FAIL or ERROR pair of a device foreach rule (the caller
+ * substitutes the rule's message with it as `element`: "validation failed in foreach rule for " +
+ * message), 0xFFFFFFFF for every other pair. kv_result_foreach_message: for an
+ * ERROR pair "validation failed in foreach rule for failed to substitute variables in deny
+ * conditions: <error>" (the first unresolved string of the deciding element, in the order of
+ * kv_result_deny_message); for a SKIP pair the fold decided "rule skipped" (a SKIP of the rule's
+ * own preconditions is kv_result_precond_message's); returns the length, 0 for any other cause
+ * (kv_result_deny_message is 0 for foreach rules). Negative codes as kv_result_subst_error. */
+int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* index);
+int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
 double kv_result_kernel_ms(const kv_result* r);
 
 /* Bulk export of the failing pairs (KV_MODE_ERRORS): every FAIL / ERROR / SKIP pair,

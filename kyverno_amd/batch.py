@@ -14,7 +14,11 @@ not hold is ``SKIP`` (``Result.precond_message``), one they cannot decide there 
 map or array operand) is ``CPU``. ``PolicySet(..., deny=True)`` (``KV_COMPILE_DENY``, opt-in)
 also evaluates ``validate.deny`` rules whose conditions are of those forms on the device
 (``kv_deny_kernel``): ``FAIL`` when the conditions hold, ``PASS`` when they do not, ``ERROR`` when
-a variable does not resolve (``Result.deny_message``).
+a variable does not resolve (``Result.deny_message``). ``PolicySet(..., foreach=True)``
+(``KV_COMPILE_FOREACH``, opt-in) evaluates single-entry ``validate.foreach`` rules with a ``deny``
+block over ``{{element...}}`` the same way, one lane per list element (``kv_foreach_elem_kernel``):
+the first ``FAIL`` / ``ERROR`` element decides (``Result.foreach_element``), else ``PASS`` when an
+element passed, else ``SKIP`` "rule skipped" (``Result.foreach_message``).
 """
 from __future__ import annotations
 
@@ -31,7 +35,7 @@ PASS, FAIL, WARN, ERROR, SKIP, NOMATCH, CPU = range(7)
 STATUS_NAMES = ["pass", "fail", "warn", "error", "skip", "nomatch", "cpu"]
 
 MODE_STATUS, MODE_ERRORS, MODE_COUNTS, MODE_SCOPES = 1, 2, 4, 8
-COMPILE_SPECIALIZE, COMPILE_DENY = 1, 2
+COMPILE_SPECIALIZE, COMPILE_DENY, COMPILE_FOREACH = 1, 2, 4
 ROUTE_GPU, ROUTE_CPU, ROUTE_NORESPONSE, ROUTE_CONSTANT = range(4)
 
 
@@ -68,6 +72,7 @@ class Rule:
     const_status: int
     const_message: str
     deny: bool = False  # a validate.deny rule evaluated on the device (PolicySet(deny=True))
+    foreach: bool = False  # a validate.foreach rule evaluated on the device (PolicySet(foreach=True))
 
 
 class PolicySet:
@@ -82,18 +87,25 @@ class PolicySet:
     ``request.object`` variables. A pair is ``FAIL`` when the conditions hold, ``PASS`` when they
     do not, ``ERROR`` when a variable does not resolve (``Result.deny_message``), ``CPU`` when the
     device cannot decide. Without it every deny rule is CPU-routed, reason ``"deny"``.
+
+    ``foreach=True`` (``KV_COMPILE_FOREACH``, opt-in, independent of ``deny``) routes
+    ``validate.foreach`` rules of one entry ``{list, preconditions?, deny}`` to the GPU: ``list`` a
+    ``request.object`` path, the conditions over ``{{element...}}`` / ``{{request.object...}}``
+    variables. Without it every foreach rule is CPU-routed, reason ``"foreach"``.
     """
 
-    def __init__(self, policies, specialize: bool = False, deny: bool = False):
+    def __init__(self, policies, specialize: bool = False, deny: bool = False, foreach: bool = False):
         L = lib()
         data = _dumps(policies)
         h = ctypes.c_void_p()
         err = new_err()
-        flags = (COMPILE_SPECIALIZE if specialize else 0) | (COMPILE_DENY if deny else 0)
+        flags = ((COMPILE_SPECIALIZE if specialize else 0) | (COMPILE_DENY if deny else 0)
+                 | (COMPILE_FOREACH if foreach else 0))
         check(L.kv_compile(data, len(data), flags, ctypes.byref(h), ctypes.byref(err)), err)
         self._h = h
         self.specialize = specialize
         self.deny = deny
+        self.foreach = foreach
         np_, nr = ctypes.c_uint32(), ctypes.c_uint32()
         L.kv_policyset_info(h, ctypes.byref(np_), ctypes.byref(nr))
         self.n_policies, self.n_rules = np_.value, nr.value
@@ -107,6 +119,7 @@ class PolicySet:
             ds = ctypes.c_uint32()
             L.kv_rule_deny_set(h, i, ctypes.byref(ds))
             self.rules[-1].deny = ds.value != 0
+            self.rules[-1].foreach = ri.foreach_set != 0
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -160,6 +173,34 @@ class PolicySet:
             if rc != 0:
                 raise RuntimeError(f"kv_batch_deny_fold: code {rc}")
         return out
+
+    @property
+    def foreach_info(self) -> dict:
+        """Foreach rules evaluated on the device: interned foreach sets, lists, conditions with a
+        variable operand and element-scoped strings (``kv_policyset_foreach_sets``), and per rule
+        1 + its foreach set, 0 for a rule that is not a device foreach rule."""
+        v = [ctypes.c_uint32() for _ in range(4)]
+        lib().kv_policyset_foreach_sets(self._h, *[ctypes.byref(x) for x in v])
+        rule_sets = []
+        for i in range(self.n_rules):
+            fs = ctypes.c_uint32()
+            lib().kv_rule_foreach_set(self._h, i, ctypes.byref(fs))
+            rule_sets.append(fs.value)
+        return {"sets": v[0].value, "lists": v[1].value, "conditions": v[2].value, "strings": v[3].value,
+                "rule_sets": rule_sets}
+
+    def foreach_fold(self, b: "Batch") -> tuple[np.ndarray, np.ndarray]:
+        """(u8 status, u32 element) [foreach sets][n_res]: the foreach fold of every set over batch
+        ``b`` on the host (``kv_batch_foreach_fold``, no GPU), the twin of the two kernels, before
+        match / exclude and the rule's preconditions; element 0xFFFFFFFF: no deciding element."""
+        n_sets = self.foreach_info["sets"]
+        st = np.zeros((n_sets, b.n_res), dtype=np.uint8)
+        el = np.full((n_sets, b.n_res), 0xFFFFFFFF, dtype=np.uint32)
+        for s in range(n_sets):
+            rc = lib().kv_batch_foreach_fold(self._h, b._h, s, st[s].ctypes.data, el[s].ctypes.data, b.n_res)
+            if rc != 0:
+                raise RuntimeError(f"kv_batch_foreach_fold: code {rc}")
+        return st, el
 
     def policy_rules(self, policy: int) -> list[Rule]:
         return [r for r in self.rules if r.policy == policy]
@@ -308,6 +349,24 @@ class Result:
             return None
         buf = ctypes.create_string_buffer(n + 1)
         lib().kv_result_deny_message(self._h, rule, res, buf, n + 1)
+        return buf.raw[:n].decode("utf-8")
+
+    def foreach_element(self, rule: int, res: int) -> int | None:
+        """The index in its list of the element that decided a FAIL / ERROR pair of a device foreach
+        rule (``kv_result_foreach_element``), else None."""
+        i = ctypes.c_uint32()
+        rc = lib().kv_result_foreach_element(self._h, rule, res, ctypes.byref(i))
+        return i.value if rc == 0 and i.value != 0xFFFFFFFF else None
+
+    def foreach_message(self, rule: int, res: int) -> str | None:
+        """"validation failed in foreach rule for failed to substitute ..." for an ERROR pair of a
+        device foreach rule, "rule skipped" for a SKIP the fold decided
+        (``kv_result_foreach_message``), else None."""
+        n = lib().kv_result_foreach_message(self._h, rule, res, None, 0)
+        if n <= 0:
+            return None
+        buf = ctypes.create_string_buffer(n + 1)
+        lib().kv_result_foreach_message(self._h, rule, res, buf, n + 1)
         return buf.raw[:n].decode("utf-8")
 
     def subst_error(self, rule: int, res: int) -> str | None:

@@ -24,8 +24,10 @@ Equals, In, GreaterThan ... conditions on ``request.object`` paths) are evaluate
 pair whose preconditions do not hold is `skip`, "preconditions not met"; a Go host runs them through ``engine.Validate``.
 ``--device-deny`` (``evaluate(deny=True)``, ``KV_COMPILE_DENY``) also evaluates ``validate.deny`` rules
 whose conditions are of those forms on the device, with the messages of ``validateDeny``.
+``--device-foreach`` (``evaluate(foreach=True)``, ``KV_COMPILE_FOREACH``) does the same for single-entry
+``validate.foreach`` rules with a ``deny`` block, with the messages of ``validateForEach``.
 
-    python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N] [--device-deny]
+    python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N] [--device-deny] [--device-foreach]
     python -m kyverno_amd test test/cli/test/simple
 """
 from __future__ import annotations
@@ -106,6 +108,8 @@ class Evaluation:
     subst: dict = field(default_factory=dict)   # (rule, res) -> message of a pattern-variable substitution ERROR
     precond: dict = field(default_factory=dict)  # (rule, res) -> message of a SKIP decided by the preconditions
     deny: dict = field(default_factory=dict)    # (rule, res) -> message of an ERROR of a deny rule's substitution
+    foreach: dict = field(default_factory=dict)  # (rule, res) -> message of an ERROR / SKIP of a foreach rule
+    foreach_elem: dict = field(default_factory=dict)  # (rule, res) -> index of the deciding element (FAIL)
     anypattern: dict = field(default_factory=dict)  # (rule, res) -> [(status, path)] per pattern
     warnings: list = field(default_factory=list)    # host-side limits met while rendering messages
 
@@ -115,23 +119,26 @@ class Evaluation:
 
 def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messages: bool = True,
              namespace_labels: dict | None = None, specialize: bool = False, gpus: int = 1,
-             deny: bool = False) -> Evaluation:
+             deny: bool = False, foreach: bool = False) -> Evaluation:
     """All (rule, resource) pairs on the GPU (``kv_compile`` → ``kv_ingest`` → ``kv_validate``).
     ``specialize`` selects the per-policy-set specialized kernels (worth their hiprtc compile on
     large batches) over the bytecode interpreter; both write the same statuses and error records.
     ``gpus`` > 1 shards the resources over devices [device, device + gpus) (kv_validate_devices).
     ``deny`` evaluates ``validate.deny`` rules of the device forms on the GPU (``KV_COMPILE_DENY``)
-    instead of routing them to the reference engine."""
+    instead of routing them to the reference engine; ``foreach`` does the same for
+    ``validate.foreach`` rules (``KV_COMPILE_FOREACH``)."""
     from . import batch
 
-    ps = batch.PolicySet(policies, specialize=specialize, deny=deny)
+    ps = batch.PolicySet(policies, specialize=specialize, deny=deny, foreach=foreach)
     b = batch.Batch(ps, resources, namespace_labels)
     mask = ((1 << gpus) - 1) << device if gpus > 1 else None
     r = batch.validate(ps, b, device=device, device_mask=mask)
     ev = Evaluation(policies, resources, ps.rules, r.status)
     if messages:
         for ri, res in zip(*np.nonzero(r.status == FAIL)):
-            if not ps.rules[ri].any_pattern and not ps.rules[ri].deny:  # (a deny FAIL has no failing path)
+            if ps.rules[ri].foreach:  # (no failing path either: the deciding element instead)
+                ev.foreach_elem[(int(ri), int(res))] = r.foreach_element(int(ri), int(res))
+            elif not ps.rules[ri].any_pattern and not ps.rules[ri].deny:  # (a deny FAIL has no failing path)
                 ev.paths[(int(ri), int(res))] = r.path(int(ri), int(res))
         collect_errors(ev, ps, r, resources)
         _evaluate_anypatterns(ev, device, specialize, namespace_labels)
@@ -157,6 +164,11 @@ def collect_errors(ev: Evaluation, ps, r, resources: list) -> None:
             if m is not None:
                 ev.precond[key] = m
                 continue
+        if getattr(ps.rules[ri], "foreach", False):
+            m = r.foreach_message(*key)
+            if m is not None:
+                ev.foreach[key] = m
+            continue
         if not ps.rules[ri].any_pattern:
             m = r.error_message(int(ri), int(res), resources[int(res)])
             if m is not None:
@@ -225,6 +237,18 @@ def _message(ev: Evaluation, rule, res: int) -> str:
         return rule.message
 
 
+def _foreach_element(ev: Evaluation, rule, res: int):
+    """The deciding element of a FAIL pair of a device foreach rule: the rule's list evaluated on
+    the resource (a map is a one-element list), at the index the device reported."""
+    idx = ev.foreach_elem.get((rule.index, res))
+    src = ev.policies[rule.policy]
+    rdoc = next(x for x in src["spec"]["rules"] if x.get("name") == rule.name)
+    lst = msgvars.query(rdoc["validate"]["foreach"][0]["list"], {"request": {"object": ev.resources[res]}})
+    if isinstance(lst, dict):
+        lst = [lst]
+    return lst[idx] if idx is not None and isinstance(lst, list) and idx < len(lst) else None
+
+
 def rule_message(ev: Evaluation, rule, res: int) -> str:
     """RuleResponse.Message (validatePatterns, buildErrorMessage, buildAnyPatternErrorMessage:
     pkg/engine/validation.go:421-547): pass / fail from the status and failing path, skip / error
@@ -234,6 +258,18 @@ def rule_message(ev: Evaluation, rule, res: int) -> str:
         return ev.subst[(rule.index, res)]
     if st == SKIP and (rule.index, res) in ev.precond:  # "preconditions not met" (validation.go:183-184)
         return ev.precond[(rule.index, res)]
+    if getattr(rule, "foreach", False):  # validateForEach (validation.go:204-283)
+        if st == PASS:
+            return "rule passed"
+        if st == FAIL:  # the element's validateDeny message, in the element's context
+            head = "validation failed in foreach rule for "
+            if not rule.message:
+                return head + f"validation error: rule {rule.name} failed"
+            try:
+                return head + msgvars.substitute_message(rule.message, ev.resources[res], _foreach_element(ev, rule, res))
+            except (msgvars.MessageVariableNotFound, msgvars.UnsupportedMessageVariable):
+                return head + rule.message
+        return ev.foreach.get((rule.index, res), "")  # ERROR, SKIP "rule skipped"
     if getattr(rule, "deny", False):  # validateDeny / getDenyMessage (validation.go:299-339)
         if st == PASS:
             return f"validation rule '{rule.name}' passed."
@@ -356,17 +392,19 @@ def policy_has_validate(policy: dict) -> bool:
 
 
 def apply(policy_paths: list[str], resource_paths: list[str], policy_report: bool = False, device: int = 0,
-          out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False) -> tuple[ResultCounts, list]:
+          out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
+          foreach: bool = False) -> tuple[ResultCounts, list]:
     """applyCommandHelper (apply_command.go:147-310) for resource files. Returns counts and the
     policyreport infos. ``evaluation_fn(policies, resources) -> Evaluation`` replaces the device
     evaluation (tests of the host logic)."""
     policies = load_policies(policy_paths)
     resources = load_resources(resource_paths)
-    return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny)
+    return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny, foreach)
 
 
 def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool = False, device: int = 0,
-               out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False) -> tuple[ResultCounts, list]:
+               out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
+          foreach: bool = False) -> tuple[ResultCounts, list]:
     mutated = autogen.mutate_policies(policies)
     if len(mutated) > 0 and len(resources) > 0:
         msg_p = "1 policy" if len(mutated) <= 1 else f"{len(policies)} policies"
@@ -378,7 +416,7 @@ def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool 
     active = [p for p in mutated if not has_unset_variables(p)]
     infos = []
     if active and resources:
-        ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus, deny=deny)))(active, resources)
+        ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus, deny=deny, foreach=foreach)))(active, resources)
         for pi, pol in enumerate(active):
             if not policy_has_validate(pol):
                 continue
@@ -436,13 +474,13 @@ def build_policy_reports(infos: list) -> list[dict]:
 
 
 def run_test(spec: dict, policies: list[dict], resources: list[dict], device: int = 0,
-             evaluation_fn=None, deny: bool = False) -> list[dict]:
+             evaluation_fn=None, deny: bool = False, foreach: bool = False) -> list[dict]:
     """`kyverno test` result matching (pkg/kyverno/test/test_command.go:347-494) for validate rules:
     the expected rule name falls back to autogen-<rule> / autogen-cronjob-<rule> when the policy's
     response does not hold it; a rule absent from the response is `skip`. Returns one row per
     expected result with the actual result ("cpu" for rules routed to the reference engine)."""
     mutated = autogen.mutate_policies(policies)
-    ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, messages=False, deny=deny)))(mutated, resources)
+    ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, messages=False, deny=deny, foreach=foreach)))(mutated, resources)
     rows = []
     for t in spec["results"]:
         want = t.get("result") or t.get("status")
@@ -484,13 +522,16 @@ def main(argv: list[str] | None = None) -> int:
     a.add_argument("--gpus", type=int, default=1, help="shard the resources over this many devices")
     a.add_argument("--device-deny", action="store_true",
                    help="evaluate validate.deny rules of the device forms on the GPU (KV_COMPILE_DENY)")
+    a.add_argument("--device-foreach", action="store_true",
+                   help="evaluate validate.foreach rules of the device forms on the GPU (KV_COMPILE_FOREACH)")
     t = sub.add_parser("test", help="run tests from a directory holding test.yaml")
     t.add_argument("dir")
     t.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     if args.cmd == "apply":
         try:
-            rc, _ = apply(args.policies, args.resource, args.policy_report, args.device, gpus=args.gpus, deny=args.device_deny)
+            rc, _ = apply(args.policies, args.resource, args.policy_report, args.device, gpus=args.gpus, deny=args.device_deny,
+                          foreach=args.device_foreach)
         except msgvars.MessageVariableError as e:
             # the Go CLI dies in buildErrorMessage (msgRaw.(string), validation.go:519-524): a
             # panic, exit status 2

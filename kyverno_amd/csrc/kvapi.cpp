@@ -23,6 +23,9 @@
 #include "../../include/kvgpu.h"
 #include "kvcond.h"
 #include "kvdev.h"
+#include "kvpre.h"
+#include "kvdeny.h"
+#include "kvforeach.h"
 #include "kvinternal.hpp"
 #include "kvjit.hpp"
 
@@ -403,6 +406,11 @@ struct DevBatchRes {
   // its HIP-event time
   DevBuf dnsets, dnents, dnoutc, dntruth, dnunk, dnerr, dnoos, dnst;
   double deny_ms = 0;
+  // validate.foreach on the device (kvcond.h FeHost): its tables (in FeHost's order), the
+  // reduction keys fe_acc[set][res], and the HIP-event time of the two kernels; their status
+  // bytes are the rows of dnst after the deny sets'
+  DevBuf fe[14], feacc;
+  double fe_ms = 0;
   DevBatch view{};
 };
 
@@ -433,6 +441,12 @@ struct kv_batch {
   const PreHost& pre_host(const PolicySet& ps) {
     std::call_once(pre_once, [&]() { build_pre(ps, b, &pre); });
     return pre;
+  }
+  std::once_flag fe_once;
+  FeHost fe;  // foreach tables (build_foreach), on first use by the host accessors
+  const FeHost& fe_host(const PolicySet& ps) {
+    std::call_once(fe_once, [&]() { build_foreach(ps, b, &fe); });
+    return fe;
   }
   // caller index -> store index (the inverse of Batch::order), on first use; null: identity
   std::once_flag inv_once;
@@ -1183,7 +1197,6 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     up(d->dnunk, dn.unk);
     up(d->dnerr, dn.err);
     up(d->dnoos, dn.oos);
-    d->dnst.alloc((size_t)n_dsets * b.res.size(), device);
     v.deny_sets = (const uint32_t*)d->dnsets.p;
     v.deny_ents = (const uint32_t*)d->dnents.p;
     v.deny_outc = (const uint32_t*)d->dnoutc.p;
@@ -1193,10 +1206,34 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     v.deny_oos = (const uint32_t*)d->dnoos.p;
     v.deny_words = dn.words;
     v.n_deny_sets = n_dsets;
+  }
+  // validate.foreach: its tables likewise; the plane has a row per deny set, then per foreach set
+  FeHost fh;
+  FeTables ft{};
+  const uint32_t n_fsets = (uint32_t)ps.fsets.size();
+  if (n_fsets && !b.res.empty()) {
+    build_foreach(ps, b, &fh);
+    const std::vector<uint32_t>* src[14] = {&fh.sets, &fh.lists, &fh.psets, &fh.pents, &fh.dsets, &fh.dents, &fh.outc,
+                                            &fh.truth, &fh.unk, &fh.err, &fh.oos, &fh.el_res, &fh.el_ord, &fh.lstate};
+    const uint32_t* dp[14];
+    for (int i = 0; i < 14; i++) {
+      d->fe[i].alloc(std::max<size_t>(src[i]->size() * sizeof(uint32_t), 16), device);
+      if (!src[i]->empty())
+        HIPCHK(hipMemcpyAsync(d->fe[i].p, src[i]->data(), src[i]->size() * sizeof(uint32_t), hipMemcpyHostToDevice, us));
+      dp[i] = (const uint32_t*)d->fe[i].p;
+    }
+    ft = fh.view();
+    ft.sets = dp[0]; ft.lists = dp[1]; ft.psets = dp[2]; ft.pents = dp[3]; ft.dsets = dp[4]; ft.dents = dp[5];
+    ft.outc = dp[6]; ft.truth = dp[7]; ft.unk = dp[8]; ft.err = dp[9]; ft.oos = dp[10]; ft.el_res = dp[11];
+    ft.el_ord = dp[12]; ft.lstate = dp[13];
+    d->feacc.alloc((size_t)n_fsets * b.res.size() * sizeof(uint32_t), device);
+  }
+  if ((n_dsets || n_fsets) && !b.res.empty()) {
+    d->dnst.alloc((size_t)(n_dsets + n_fsets) * b.res.size(), device);
     v.deny_st = (const uint8_t*)d->dnst.p;
   }
   d->view_dev.upload_raw(&d->view, sizeof(DevBatch), device);
-  hipEvent_t pe0 = nullptr, pe1 = nullptr, de0 = nullptr, de1 = nullptr;
+  hipEvent_t pe0 = nullptr, pe1 = nullptr, de0 = nullptr, de1 = nullptr, fe0 = nullptr, fe1 = nullptr;
   if (v.pre_st) {
     HIPCHK(hipEventCreate(&pe0));
     HIPCHK(hipEventCreate(&pe1));
@@ -1204,14 +1241,28 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     HIPCHK(launch_precond((const DevBatch*)d->view_dev.p, v.n_res, n_sets, (uint8_t*)d->prest.p, us));
     HIPCHK(hipEventRecord(pe1, us));
   }
-  if (v.deny_st) {
+  if (v.deny_st && n_dsets) {
     HIPCHK(hipEventCreate(&de0));
     HIPCHK(hipEventCreate(&de1));
     HIPCHK(hipEventRecord(de0, us));
     HIPCHK(launch_deny((const DevBatch*)d->view_dev.p, v.n_res, n_dsets, (uint8_t*)d->dnst.p, us));
     HIPCHK(hipEventRecord(de1, us));
   }
+  if (v.deny_st && n_fsets) {
+    HIPCHK(hipEventCreate(&fe0));
+    HIPCHK(hipEventCreate(&fe1));
+    HIPCHK(hipEventRecord(fe0, us));
+    HIPCHK(launch_foreach(ft, v.n_res, (uint32_t*)d->feacc.p, (uint8_t*)d->dnst.p + (size_t)n_dsets * v.n_res, us));
+    HIPCHK(hipEventRecord(fe1, us));
+  }
   HIPCHK(hipStreamSynchronize(us));
+  if (fe0) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, fe0, fe1));
+    d->fe_ms = ms;
+    (void)hipEventDestroy(fe0);
+    (void)hipEventDestroy(fe1);
+  }
   if (de0) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, de0, de1));
@@ -2415,6 +2466,9 @@ void run(kv_policyset* ps, kv_batch* bt, const char* ctx_json, const std::vector
     // the deny fold's kernel, likewise
     if (!ps->ps.dsets.empty() && !s.parts.empty() && s.parts[0]->batch_ref)
       out->phases.push_back({"deny", s.parts[0]->batch_ref->deny_ms});
+    // the foreach fold's two kernels, likewise
+    if (!ps->ps.fsets.empty() && !s.parts.empty() && s.parts[0]->batch_ref)
+      out->phases.push_back({"foreach", s.parts[0]->batch_ref->fe_ms});
     s.fetch(out, t);
   }
   if (getenv("KVGPU_VERBOSE")) {  // host-boundary breakdown
@@ -2441,7 +2495,7 @@ int kv_compile(const char* policies_json, size_t len, uint32_t flags, kv_policys
   try {
     auto* s = new kv_policyset();
     try {
-      compile_policies(policies_json, len, &s->ps, flags & KV_COMPILE_DENY);
+      compile_policies(policies_json, len, &s->ps, flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH));
       if (flags & KV_COMPILE_SPECIALIZE) {
         s->jit = std::make_unique<JitImage>();
         const uint32_t chunk = jit_chunk_rules();
@@ -2553,6 +2607,7 @@ int kv_rule_info_get(const kv_policyset* ps, uint32_t rule, kv_rule_info* out) {
   out->any_pattern = rh.anypattern ? 1 : 0;
   out->const_status = rr.const_status;
   out->const_message = rh.const_message.c_str();
+  out->foreach_set = rh.foreach_set;
   return 0;
 }
 
@@ -2864,7 +2919,8 @@ int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char
   res = r->sidx(res);
   try {
     const RuleRec& rr = r->ps->ps.rules[rule];
-    if (!rr.deny || const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res] != ST_ERROR) return 0;
+    if (!rr.deny || r->ps->ps.rhost[rule].foreach_set) return 0;
+    if (const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res] != ST_ERROR) return 0;
     const ResultPart* p = r->part_of(s);
     if (!p) return 0;
     const kv_batch* kb = p->shard ? p->shard.get() : r->b;
@@ -2914,8 +2970,128 @@ int kv_batch_deny_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, 
 int kv_rule_deny_set(const kv_policyset* ps, uint32_t rule, uint32_t* set) {
   if (!ps || !set) return KV_E_INVALID;
   if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
-  *set = ps->ps.rules[rule].deny;
+  *set = ps->ps.rhost[rule].foreach_set ? 0u : ps->ps.rules[rule].deny;
   return 0;
+}
+
+// ------------------------------------------------------------------ foreach
+int kv_policyset_foreach_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* lists, uint32_t* conditions,
+                              uint32_t* strings) {
+  if (!ps) return KV_E_INVALID;
+  if (sets) *sets = (uint32_t)ps->ps.fsets.size();
+  if (lists) *lists = (uint32_t)ps->ps.flists.size();
+  if (conditions) *conditions = (uint32_t)ps->ps.fconds.size();
+  if (strings) *strings = (uint32_t)ps->ps.fkeys.size();
+  return 0;
+}
+
+int kv_rule_foreach_set(const kv_policyset* ps, uint32_t rule, uint32_t* set) {
+  if (!ps || !set) return KV_E_INVALID;
+  if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
+  *set = ps->ps.rhost[rule].foreach_set;
+  return 0;
+}
+
+int kv_batch_foreach_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint32_t* elem,
+                          uint64_t n) {
+  if (!ps || !b || !status) return KV_E_INVALID;
+  if (set >= ps->ps.fsets.size() || n != b->b.res.size()) return KV_E_RANGE;
+  try {
+    FeHost h;
+    build_foreach(ps->ps, b->b, &h);
+    const std::vector<uint32_t>& order = b->b.order;  // store index -> caller index (empty: identity)
+    for (uint64_t s = 0; s < n; s++) {
+      uint32_t e = 0xFFFFFFFFu;
+      const uint64_t i = order.empty() ? s : order[s];
+      status[i] = foreach_fold_host(h, set, n, s, &e);
+      if (elem) elem[i] = e;
+    }
+    return 0;
+  } catch (const std::bad_alloc&) {
+    return KV_E_NOMEM;
+  } catch (const std::exception&) {
+    return KV_E_INVALID;
+  }
+}
+
+namespace {
+// the host fold of a foreach rule's pair of a result: the batch (or shard) that holds store
+// resource s and the resource's index in it; false when the rule is not a device foreach rule
+bool fe_pair(const kv_result* r, uint32_t rule, uint64_t s, kv_batch** kb, uint64_t* local) {
+  if (!r->ps->ps.rhost[rule].foreach_set) return false;
+  const ResultPart* p = r->part_of(s);
+  if (!p) return false;
+  *kb = p->shard ? p->shard.get() : const_cast<kv_batch*>(r->b);
+  *local = s - p->lo;
+  return true;
+}
+int put_message(const std::string& m, char* buf, size_t cap) {
+  if (buf && cap) {
+    size_t n = std::min(cap - 1, m.size());
+    memcpy(buf, m.data(), n);
+    buf[n] = 0;
+  }
+  return (int)m.size();
+}
+}  // namespace
+
+int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* index) {
+  if (!r || !index) return KV_E_INVALID;
+  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
+  if (!r->has_status()) return KV_E_INVALID;
+  const uint64_t s = r->store_of(res);
+  res = r->sidx(res);
+  try {
+    *index = 0xFFFFFFFFu;
+    const uint8_t st = const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res];
+    if (st != ST_FAIL && st != ST_ERROR) return 0;  // (PASS, SKIP: no deciding element; CPU: not reported)
+    kv_batch* kb = nullptr;
+    uint64_t local = 0;
+    if (!fe_pair(r, rule, s, &kb, &local)) return 0;
+    const PolicySet& ps = r->ps->ps;
+    uint32_t e = 0xFFFFFFFFu;
+    if (foreach_fold_host(kb->fe_host(ps), ps.rhost[rule].foreach_set - 1, kb->b.res.size(), local, &e) == st) *index = e;
+    return 0;
+  } catch (const std::bad_alloc&) {
+    return KV_E_NOMEM;
+  } catch (const std::exception&) {
+    return KV_E_INVALID;
+  }
+}
+
+int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
+  if (!r) return KV_E_INVALID;
+  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
+  if (!r->has_status()) return KV_E_INVALID;
+  const uint64_t s = r->store_of(res);
+  res = r->sidx(res);
+  try {
+    const uint8_t st = const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res];
+    if (st != ST_ERROR && st != ST_SKIP) return 0;
+    kv_batch* kb = nullptr;
+    uint64_t local = 0;
+    if (!fe_pair(r, rule, s, &kb, &local)) return 0;
+    const PolicySet& ps = r->ps->ps;
+    const uint32_t set = ps.rhost[rule].foreach_set - 1;
+    const FeHost& h = kb->fe_host(ps);
+    uint32_t e = 0xFFFFFFFFu;
+    // the pair recomputed from the batch's tables: a SKIP of the rule's own preconditions has
+    // another cause (kv_result_precond_message)
+    if (foreach_fold_host(h, set, kb->b.res.size(), local, &e) != st) return 0;
+    if (st == ST_SKIP) {
+      const RuleRec& rr = ps.rules[rule];
+      if (rr.pre && pre_status_host(kb->pre_host(ps), rr.pre - 1, kb->b.res.size(), local) == ST_SKIP) return 0;
+      return put_message("rule skipped", buf, cap);  // (validation.go:279-281)
+    }
+    const std::string err = foreach_error_host(ps, kb->b, h, set, local, e);
+    if (err.empty()) return 0;
+    return put_message("validation failed in foreach rule for failed to substitute variables in deny conditions: " + err,
+                       buf, cap);
+  } catch (const std::bad_alloc&) {
+    return KV_E_NOMEM;
+  } catch (const std::exception&) {
+    return KV_E_INVALID;
+  }
 }
 
 int kv_condition_eval(const char* condition_json, size_t len, int* result) {

@@ -1451,7 +1451,7 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
         compile_block(C, d, d.get(rn, "exclude"), false, rr, rh);
         int64_t val = d.get(rn, "validate");
         bool has_validate = false, patP = false, anyP = false, denyP = false, feP = false;
-        int64_t pat = -1, ap = -1, deny = -1;
+        int64_t pat = -1, ap = -1, deny = -1, fen = -1;
         std::string msg;
         if (val >= 0 && d.at((uint32_t)val).t == J_MAP) {
           uint32_t v = (uint32_t)val;
@@ -1464,6 +1464,7 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
           denyP = dn >= 0 && d.at((uint32_t)dn).t != J_NULL;
           deny = dn;
           feP = fe >= 0 && d.at((uint32_t)fe).t != J_NULL;
+          fen = fe;
           has_validate = !msg.empty() || patP || anyP || denyP || feP;
         }
         rh.message = msg;
@@ -1474,9 +1475,22 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
         // validate.deny on the device (KV_COMPILE_DENY, kvcond.h): a rule without pattern /
         // anyPattern (validate() ignores deny beside one, validation.go:187-198)
         const bool denyD = (flags & 2u /* KV_COMPILE_DENY */) && denyP && !patP && !anyP;
+        // validate.foreach on the device (KV_COMPILE_FOREACH, kvcond.h): nothing beside it in
+        // validate, no rule-level context
+        const bool feD = (flags & 4u /* KV_COMPILE_FOREACH */) && feP && !patP && !anyP && !denyP && !ctxP;
         rr.route = 0;
         if (!has_validate) { rr.route = 2; rh.route_reason = "no validate"; }
-        else if (feP) { rr.route = 1; rh.route_reason = "foreach"; }
+        else if (feP && (!feD || (rh.foreach_set = compile_foreach(*ps, d, (uint32_t)fen)) == 0)) {
+          rr.route = 1;
+          rh.route_reason = "foreach";
+        }
+        else if (feP) {  // (RuleRec::deny is set below, once the deny sets are counted; no program)
+          if (preP && (pre_set = compile_preconditions(*ps, d, (uint32_t)pre)) == 0) {
+            rr.route = 1;
+            rh.route_reason = "preconditions";
+            rh.foreach_set = 0;
+          }
+        }
         else if (ctxP) { rr.route = 1; rh.route_reason = "context"; }
         // preconditions: evaluated on the device where the block and the rule's pattern are in
         // scope (kvcond.h); everything else keeps the CPU route and its reason
@@ -1558,6 +1572,9 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
     }
     ps->policy_rule_count.push_back(nrules);
   }
+  // foreach rules read their status from the rows of the deny plane after the deny sets'
+  for (size_t i = 0; i < ps->rules.size(); i++)
+    if (ps->rhost[i].foreach_set) ps->rules[i].deny = (uint32_t)ps->dsets.size() + ps->rhost[i].foreach_set;
   // Slot-addressed map layout: every non-keep-all trie node gets a byte-sorted
   // key list; key-lookup ops get the slot index (keep-all maps: key id + AUX_SCAN).
   for (auto& tn : ps->trie.nodes) {

@@ -8,6 +8,7 @@
 
 #include "kvpre.h"
 #include "kvdeny.h"
+#include "kvforeach.h"
 
 namespace kvh {
 
@@ -379,6 +380,10 @@ struct CondSpace {
   std::unordered_map<std::string, uint32_t>& cond_id;
   std::vector<uint32_t>* strs;
   size_t any_strs = 0;  // how many of them the `any` list gave (it is compiled first)
+  // foreach entries: `element` is a variable root too, and the strings are interned under
+  // tag + text (the list and the resolver mode: PolicySet::ftags)
+  bool element = false;
+  std::string tag;
 };
 
 // one condition: 0 constant false, 1 constant true, 2 dynamic (*rec), -1 outside the scope
@@ -405,7 +410,7 @@ int compile_condition(CondSpace& sp, const JDoc& d, uint32_t node, uint32_t* rec
   for (const PV* p : {&key, &value}) {
     if (p->t == J_STR) {
       if (has_escape_or_ref(p->s)) return -1;
-      if (var_string(p->s) && !cond_string_in_scope(p->s)) return -1;
+      if (var_string(p->s) && !cond_string_in_scope(p->s, sp.element)) return -1;
     } else if (tree_has_var(*p)) {
       return -1;  // variables inside a list or map operand
     }
@@ -417,7 +422,7 @@ int compile_condition(CondSpace& sp, const JDoc& d, uint32_t node, uint32_t* rec
     return range ? -1 : (r ? 1 : 0);
   }
   if (op == CD_UNKNOWN && !sp.strs) return 0;
-  const std::string& text = kv ? key.s : value.s;
+  const std::string text = sp.tag + (kv ? key.s : value.s);
   auto ck = sp.key_id.find(text);
   if (ck == sp.key_id.end()) {
     ck = sp.key_id.emplace(text, (uint32_t)sp.keys.size()).first;
@@ -583,6 +588,95 @@ uint32_t compile_deny(PolicySet& ps, const JDoc& d, uint32_t node) {
   return it->second + 1;
 }
 
+uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node) {
+  // validate.foreach: a list of exactly one entry {list, preconditions?, deny} (with several, keys
+  // of entry k-1's last element leak into entry k's `element`: kvcond.h)
+  if (d.at(node).t != J_ARR || d.at(node).count != 1) return 0;
+  const uint32_t en = d.at(node).first;
+  if (d.at(en).t != J_MAP) return 0;
+  int64_t ln = -1, pn = -1, dn = -1;
+  for (uint32_t c = d.at(en).first; c < d.at(en).first + d.at(en).count; c++) {
+    const std::string_view k = d.key(d.at(c));
+    if (k == "list") ln = c;
+    else if (k == "preconditions") pn = c;
+    else if (k == "deny") dn = c;
+    else return 0;  // pattern, anyPattern, context, ...
+  }
+  if (ln < 0 || dn < 0 || d.at((uint32_t)ln).t != J_STR || d.at((uint32_t)dn).t != J_MAP) return 0;
+  const std::string list(d.sval(d.at((uint32_t)ln)));
+  if (!list_query_in_scope(list)) return 0;
+  if (pn >= 0 && d.at((uint32_t)pn).t == J_NULL) pn = -1;
+  // the old list form of an entry's preconditions fails common.ToMap and is dropped by the
+  // reference (validation.go:260-266): left to it
+  if (pn >= 0 && d.at((uint32_t)pn).t != J_MAP) return 0;
+  int64_t cn = -1;
+  for (uint32_t c = d.at((uint32_t)dn).first; c < d.at((uint32_t)dn).first + d.at((uint32_t)dn).count; c++) {
+    if (d.key(d.at(c)) != "conditions") return 0;
+    cn = c;
+  }
+  if (cn < 0 || d.at((uint32_t)cn).t == J_NULL) return 0;
+  // checkpoint: an entry outside the scope leaves nothing behind
+  const size_t l0 = ps.flists.size(), k0 = ps.ftags.size(), c0 = ps.fconds.size();
+  auto rollback = [&]() {
+    for (size_t i = k0; i < ps.ftags.size(); i++) ps.ftag_id.erase(ps.ftags[i]);
+    ps.ftags.resize(k0);
+    for (auto it = ps.fcond_id.begin(); it != ps.fcond_id.end();)
+      it = it->second >= c0 ? ps.fcond_id.erase(it) : std::next(it);
+    ps.fconds.resize(c0);
+    if (ps.flists.size() > l0) {
+      ps.flist_id.erase(ps.flists.back());
+      ps.flists.pop_back();
+      ps.flist_keys.pop_back();
+    }
+    return 0u;
+  };
+  auto li = ps.flist_id.find(list);
+  if (li == ps.flist_id.end()) {
+    li = ps.flist_id.emplace(list, (uint32_t)ps.flists.size()).first;
+    ps.flists.push_back(list);
+    ps.flist_keys.emplace_back();
+  }
+  FeSet s;
+  s.list = li->second;
+  bool always = false;
+  if (pn >= 0) {
+    CondSpace sp{ps.ftags, ps.fconds, ps.ftag_id, ps.fcond_id, nullptr};
+    sp.element = true;
+    sp.tag = "p" + std::to_string(s.list) + ":";
+    if (!compile_block(sp, d, (uint32_t)pn, &s.pre, &always)) return rollback();
+    s.has_pre = !always;
+    if (always) s.pre = CondSet();
+  }
+  CondSpace sp{ps.ftags, ps.fconds, ps.ftag_id, ps.fcond_id, &s.deny.strs};
+  sp.element = true;
+  sp.tag = "d" + std::to_string(s.list) + ":";
+  if (!compile_block(sp, d, (uint32_t)cn, &s.deny.fold, &always)) return rollback();
+  for (size_t i = sp.any_strs; i < s.deny.strs.size(); i++) s.deny.order.push_back(s.deny.strs[i]);
+  for (size_t i = 0; i < sp.any_strs; i++) s.deny.order.push_back(s.deny.strs[i]);
+  std::sort(s.deny.strs.begin(), s.deny.strs.end());
+  s.deny.strs.erase(std::unique(s.deny.strs.begin(), s.deny.strs.end()), s.deny.strs.end());
+  // the strings this entry added: their list, resolver mode and column in the list's element rows
+  for (size_t i = ps.fkeys.size(); i < ps.ftags.size(); i++) {
+    const std::string& t = ps.ftags[i];
+    FeKey k;
+    k.list = s.list;
+    k.precond = t[0] == 'p';
+    k.text = t.substr(t.find(':') + 1);
+    k.col = (uint32_t)ps.flist_keys[s.list].size();
+    ps.flist_keys[s.list].push_back((uint32_t)i);
+    ps.fkeys.push_back(std::move(k));
+  }
+  std::string id = std::to_string(s.list) + "|" + (s.has_pre ? set_key(s.pre) : std::string("none")) + "|" +
+                   set_key(s.deny.fold) + "#";
+  for (uint32_t k : s.deny.order) id += std::to_string(k) + ",";
+  auto it = ps.fset_id.find(id);
+  if (it == ps.fset_id.end()) {
+    it = ps.fset_id.emplace(id, (uint32_t)ps.fsets.size()).first;
+    ps.fsets.push_back(std::move(s));
+  }
+  return it->second + 1;
+}
+
 // ------------------------------------------------------------------ per batch
 namespace {
 
@@ -693,6 +787,151 @@ uint8_t pre_status_host(const PreHost& h, uint32_t set, uint64_t n_res, uint64_t
 uint8_t deny_status_host(const DenyHost& h, uint32_t set, uint64_t n_res, uint64_t r) {
   return (uint8_t)kv_deny_lane(h.sets.data(), h.ents.data(), h.outc.data(), h.truth.data(), h.unk.data(), h.err.data(),
                                h.oos.data(), h.words, set, n_res, r);
+}
+
+// ------------------------------------------------------------------ foreach
+void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out) {
+  FeHost& h = *out;
+  h = FeHost();
+  const uint64_t n = b.res.size();
+  if (ps.fsets.empty() || n == 0) return;
+  const size_t L = ps.flists.size();
+  if (b.fstate.size() != L * n || b.fcount.size() != L * n || b.fout.size() != L)
+    throw std::runtime_error("build_foreach: element rows do not match the policy set");
+  // per list: the element blocks, [string][element] outcome ids, the per-resource state
+  h.lstate.resize(L * n);
+  h.first.resize(L * n);
+  std::vector<uint32_t> plane0(L, 0);
+  uint32_t rows = 0;
+  for (size_t l = 0; l < L; l++) {
+    const size_t K = ps.flist_keys[l].size();
+    const uint32_t el0 = (uint32_t)h.el_res.size();
+    for (uint64_t r = 0; r < n; r++) {
+      h.lstate[l * n + r] = b.fstate[r * L + l];
+      h.first[l * n + r] = (uint32_t)h.el_res.size() - el0;
+      for (uint32_t i = 0; i < b.fcount[r * L + l]; i++) {
+        h.el_res.push_back((uint32_t)r);
+        h.el_ord.push_back(i);
+      }
+    }
+    const uint32_t n_el = (uint32_t)h.el_res.size() - el0;
+    if (b.fout[l].size() != (size_t)n_el * K) throw std::runtime_error("build_foreach: element rows misaligned");
+    const uint32_t o0 = (uint32_t)h.outc.size();
+    h.outc.resize(o0 + (size_t)n_el * K);
+    for (uint32_t e = 0; e < n_el; e++)
+      for (size_t c = 0; c < K; c++) h.outc[o0 + c * n_el + e] = b.fout[l][(size_t)e * K + c];
+    plane0[l] = rows;
+    h.lists.insert(h.lists.end(), {o0, n_el, rows, el0});
+    rows += (uint32_t)K;
+    h.max_el = std::max(h.max_el, n_el);
+  }
+  // the outcomes each string takes in this batch, then the planes over them
+  const size_t T = b.vout_tab.size();
+  const uint32_t W = (uint32_t)std::max<size_t>((T + 31) / 32, 1);
+  h.words = W;
+  std::vector<uint32_t> seen((size_t)rows * W, 0);
+  auto row_of = [&](uint32_t key) { return plane0[ps.fkeys[key].list] + ps.fkeys[key].col; };
+  for (size_t l = 0; l < L; l++) {
+    const uint32_t o0 = h.lists[4 * l], n_el = h.lists[4 * l + 1];
+    for (size_t c = 0; c < ps.flist_keys[l].size(); c++)
+      for (uint32_t e = 0; e < n_el; e++) {
+        const uint32_t o = h.outc[o0 + c * n_el + e];
+        seen[(size_t)(plane0[l] + c) * W + o / 32] |= 1u << (o % 32);
+      }
+  }
+  h.err.assign((size_t)rows * W, 0);
+  h.oos.assign((size_t)rows * W, 0);
+  for (size_t k = 0; k < ps.fkeys.size(); k++) {
+    if (ps.fkeys[k].precond) continue;  // (the gate's strings have no error: unresolved is "")
+    const size_t row = row_of((uint32_t)k);
+    for (size_t o = 0; o < T; o++) {
+      if (!((seen[row * W + o / 32] >> (o % 32)) & 1u)) continue;
+      const char t = b.vout_tab[o].empty() ? 'C' : b.vout_tab[o][0];
+      if (t == 'E') h.err[row * W + o / 32] |= 1u << (o % 32);
+      else if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N' || t == 'M')) h.oos[row * W + o / 32] |= 1u << (o % 32);
+    }
+  }
+  h.truth.assign(ps.fconds.size() * W, 0);
+  h.unk.assign(ps.fconds.size() * W, 0);
+  for (size_t ci = 0; ci < ps.fconds.size(); ci++) {
+    const CondRec& c = ps.fconds[ci];
+    const size_t row = row_of(c.cstr);
+    for (size_t o = 0; o < T; o++) {
+      if (!((seen[row * W + o / 32] >> (o % 32)) & 1u)) continue;
+      const std::string& oc = b.vout_tab[o];
+      const char t = oc.empty() ? 'C' : oc[0];
+      bool range = !(t == 'S' || t == 'F' || t == 'B' || t == 'N');  // a map / array, an error: outside the scope
+      bool r = false;
+      if (!range) {
+        const PV v = outcome_value(oc);
+        r = c.var_is_key ? cond_eval(c.op, v, c.other, &range) : cond_eval(c.op, c.other, v, &range);
+      }
+      if (range) h.unk[ci * W + o / 32] |= 1u << (o % 32);
+      else if (r) h.truth[ci * W + o / 32] |= 1u << (o % 32);
+    }
+  }
+  // the sets: row s of psets / dsets is foreach set s; entries carry the string's column
+  auto col = [&](uint32_t c) { return ps.fkeys[ps.fconds[c].cstr].col; };
+  for (const FeSet& s : ps.fsets) {
+    h.sets.insert(h.sets.end(), {s.list, s.has_pre ? 1u : 0u, 0u, 0u});
+    h.psets.push_back((uint32_t)(h.pents.size() / 2));
+    h.psets.push_back((uint32_t)s.pre.any.size() | (s.pre.any_present ? 0x80000000u : 0u));
+    h.psets.push_back((uint32_t)s.pre.all.size());
+    h.psets.push_back(s.pre.const_false ? 1u : 0u);
+    for (uint32_t c : s.pre.any) { h.pents.push_back(col(c)); h.pents.push_back(c); }
+    for (uint32_t c : s.pre.all) { h.pents.push_back(col(c)); h.pents.push_back(c); }
+    h.dsets.push_back((uint32_t)(h.dents.size() / 2));
+    const size_t e0 = h.dents.size();
+    for (uint32_t k : s.deny.strs) {
+      const size_t e1 = h.dents.size();
+      for (uint32_t c : s.deny.fold.any)
+        if (ps.fconds[c].cstr == k) { h.dents.push_back(ps.fkeys[k].col); h.dents.push_back(c); }
+      for (uint32_t c : s.deny.fold.all)
+        if (ps.fconds[c].cstr == k) { h.dents.push_back(ps.fkeys[k].col); h.dents.push_back(c | KV_DENY_ALL); }
+      if (h.dents.size() == e1) { h.dents.push_back(ps.fkeys[k].col); h.dents.push_back(KV_DENY_NOCOND); }
+    }
+    h.dsets.push_back((uint32_t)((h.dents.size() - e0) / 2));
+    h.dsets.push_back(s.deny.fold.any_present ? 1u : 0u);
+    h.dsets.push_back(s.deny.fold.const_false ? 1u : 0u);
+  }
+}
+
+FeTables FeHost::view() const {
+  FeTables t{};
+  t.sets = sets.data(); t.lists = lists.data(); t.psets = psets.data(); t.pents = pents.data();
+  t.dsets = dsets.data(); t.dents = dents.data(); t.outc = outc.data(); t.truth = truth.data();
+  t.unk = unk.data(); t.err = err.data(); t.oos = oos.data(); t.el_res = el_res.data();
+  t.el_ord = el_ord.data(); t.lstate = lstate.data();
+  t.words = words;
+  t.n_sets = (uint32_t)(sets.size() / 4);
+  t.n_lists = (uint32_t)(lists.size() / 4);
+  t.max_el = max_el;
+  return t;
+}
+
+uint8_t foreach_fold_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_t r, uint32_t* elem) {
+  const FeTables t = h.view();
+  const uint32_t list = h.sets[4 * set];
+  const uint32_t n_el = h.lists[4 * list + 1], el0 = h.lists[4 * list + 3];
+  uint32_t key = FE_KEY_NONE;
+  // the elements of store resource r: [first, ...) while el_res says r (what the kernel's
+  // segments are made of)
+  for (uint32_t e = h.first[(size_t)list * n_res + r]; e < n_el && h.el_res[el0 + e] == r; e++)
+    key = std::min(key, kv_fe_key(kv_foreach_elem(t, set, e), h.el_ord[el0 + e]));
+  if (elem) *elem = key < FE_KEY_PASS ? key >> 3 : 0xFFFFFFFFu;
+  return (uint8_t)kv_fe_final(h.lstate[(size_t)list * n_res + r], key);
+}
+
+std::string foreach_error_host(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t set, uint64_t r,
+                               uint32_t elem) {
+  const FeSet& s = ps.fsets[set];
+  const size_t K = ps.flist_keys[s.list].size();
+  const size_t e = (size_t)h.first[(size_t)s.list * b.res.size() + r] + elem;
+  for (uint32_t k : s.deny.order) {
+    const std::string& o = b.vout_tab[b.fout[s.list][e * K + ps.fkeys[k].col]];
+    if (!o.empty() && o[0] == 'E') return o.substr(1);
+  }
+  return std::string();
 }
 
 std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, uint64_t r) {

@@ -22,6 +22,10 @@
 
 #include "kvinternal.hpp"
 
+namespace kv {
+struct FeTables;  // kvforeach.h
+}
+
 namespace kvh {
 
 // operators (operator.go:28-78, names compare case-insensitively); CD_UNKNOWN: constant false
@@ -91,5 +95,44 @@ uint8_t deny_status_host(const DenyHost& h, uint32_t set, uint64_t n_res, uint64
 // the error of the first unresolved string of the set on store resource r, in the order of the
 // reference's traversal with canonical key order ("" when every string resolves)
 std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, uint64_t r);
+
+// validate.foreach on the device (KV_COMPILE_FOREACH; pkg/engine/validation.go:108-115,204-283
+// validateForEach). The reference queries the entry's `list` on the JSON context, and per element,
+// in order, merges {"element": <element>} into the context and runs validate() with the entry's
+// preconditions (preconditions resolver) and deny block (strict resolver): a SKIP is ignored, the
+// first result that is neither PASS nor SKIP ends the rule; without one the rule is PASS when an
+// element passed, else SKIP "rule skipped". Scope: one entry {list, preconditions?, deny} per
+// rule (with several entries, keys of the previous entry's last element leak into `element`
+// through the merge patch), preconditions a map (the old list form is dropped by the reference),
+// variables `{{element<chain>}}` / `{{request.object<chain>}}`. DESIGN.md §3 *Foreach*.
+//  * compile (compile_foreach): lists, element-scoped strings (per list and resolver mode; a
+//    string with request.object variables only is an element-scoped string too: one key space,
+//    one resolver call site), conditions and foreach sets are interned in PolicySet::f*;
+//  * ingest: per (resource, list) the list state and element count, per (element, string) an
+//    outcome id of the batch's outcome table, element-major (Batch::fstate / fcount / fout);
+//  * per batch (build_foreach): the planes of build_deny / build_pre over the element strings,
+//    the outcome ids transposed to [string][element], el_res / el_ord per element;
+//  * device (kvforeach.h, kv_foreach_elem_kernel, kv_foreach_fin_kernel): a lane per element, a
+//    segmented first-decisive-element reduction into 32-bit keys, a byte per (set, resource) in
+//    the rows of DevBatch::deny_st after the deny sets'.
+// Parses the `validate.foreach` node of a rule: 0 when it is outside the device scope (the rule
+// stays CPU-routed, reason "foreach"), else 1 + the interned foreach set's index.
+uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node);
+
+struct FeHost {
+  std::vector<uint32_t> sets, lists, psets, pents, dsets, dents;  // kvforeach.h FeTables
+  std::vector<uint32_t> outc, truth, unk, err, oos, el_res, el_ord, lstate;
+  std::vector<uint32_t> first;  // [list][res]: the resource's first element in the list's block (host only)
+  uint32_t words = 1, max_el = 0;
+  kv::FeTables view() const;
+};
+void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out);
+// one (foreach set, store resource) on the host, as the two kernels: ST_PASS, ST_FAIL, ST_ERROR,
+// ST_SKIP or ST_CPU; *elem the deciding element's index in its list, 0xFFFFFFFF without one
+uint8_t foreach_fold_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_t r, uint32_t* elem);
+// the error of the first unresolved deny string of element `elem` of store resource r, in the
+// order of deny_error_host
+std::string foreach_error_host(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t set, uint64_t r,
+                               uint32_t elem);
 
 }  // namespace kvh

@@ -23,6 +23,11 @@ hipError_t launch_precond(const DevBatch* B, uint32_t n_res, uint32_t n_sets, ui
 // with the precondition gate.
 hipError_t launch_deny(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* deny_st, hipStream_t stream);
 
+// The foreach fold of a batch (kvforeach.h): clears fe_acc[set][res] (32-bit keys), reduces every
+// set's elements into it and writes fe_st[set][res], with the deny fold. T holds device pointers.
+struct FeTables;
+hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream);
+
 // Match tables of a pass (DevPS::mt_*): `words` = mt_ns_words + mt_ann_words +
 // mt_sel_words rows, max_entities = max(n_nsm, n_asets, n_lsets).
 hipError_t launch_mtab(const DevPS* P, const DevBatch* B, uint32_t words, uint32_t max_entities, uint32_t* ns,

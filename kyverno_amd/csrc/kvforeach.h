@@ -1,0 +1,71 @@
+// validate.foreach on the device (kvcond.h): the per-element verdict and the reduction keys,
+// shared by kv_foreach_elem_kernel / kv_foreach_fin_kernel (kvkernel.hip) and the host fold
+// (kvcond.cpp foreach_fold_host). Plain code over the tables of kvcond.h FeHost; needs
+// kv_layout.h, kvpre.h and kvdeny.h.
+#pragma once
+
+namespace kv {
+
+// state of one (resource, foreach list)
+constexpr uint8_t FE_LIST_EMPTY = 0;  // the list query is NotFound: no element
+constexpr uint8_t FE_LIST_OK = 1;     // a list of maps (or one map), no null inside
+constexpr uint8_t FE_LIST_OOS = 2;    // anything else: the pair is ST_CPU
+constexpr uint32_t FE_MAX_ELEMS = 0x10000u;
+
+// Reduction keys of fe_acc[set][res] (atomicMin): the first decisive element of the resource's
+// list, (index in the list << 3 | its ST_ code), below the key of "some element passed", below
+// the initial value "no element, or every element skipped".
+constexpr uint32_t FE_KEY_PASS = 0x80000000u;
+constexpr uint32_t FE_KEY_NONE = 0xFFFFFFFFu;
+
+// The device view of FeHost (32-bit words throughout).
+struct FeTables {
+  const uint32_t* sets;    // 4 words per foreach set: list, has_pre, 0, 0
+  const uint32_t* lists;   // 4 words per list: first word of its outc block, elements, first plane row, first element
+  const uint32_t* psets;   // the entry preconditions of every set, as PreHost::sets / ents (row = set)
+  const uint32_t* pents;
+  const uint32_t* dsets;   // the deny block of every set, as DenyHost::sets / ents (row = set)
+  const uint32_t* dents;
+  const uint32_t* outc;    // per list a block [string of the list][element of the list]
+  const uint32_t* truth;   // [condition][words]
+  const uint32_t* unk;
+  const uint32_t* err;     // [plane row of the list + string][words]
+  const uint32_t* oos;
+  const uint32_t* el_res;  // per list block: the element's store resource
+  const uint32_t* el_ord;  // per list block: the element's index in its list
+  const uint32_t* lstate;  // [list][res]: FE_LIST_*
+  uint32_t words, n_sets, n_lists, max_el;
+};
+
+// One element of foreach set `set`: element e of the set's list (e < its element count).
+// validate() on the element's context (validation.go:156-202): the entry's preconditions under
+// the preconditions resolver (not met: ST_SKIP, undecided: ST_CPU), then the deny block under the
+// strict one (kv_deny_lane: ST_CPU, ST_ERROR, ST_FAIL or ST_PASS).
+KV_HD inline uint32_t kv_foreach_elem(const FeTables& T, uint32_t set, uint32_t e) {
+  const uint32_t* L = T.lists + 4u * T.sets[4u * set];
+  const uint32_t n_el = L[1];
+  const uint32_t* outc = T.outc + L[0];
+  if (T.sets[4u * set + 1u]) {
+    const uint32_t g = kv_pre_lane(T.psets, T.pents, outc, T.truth, T.unk, T.words, set, n_el, e);
+    if (g) return g;
+  }
+  const uint64_t row = (uint64_t)L[2] * T.words;
+  return kv_deny_lane(T.dsets, T.dents, outc, T.truth, T.unk, T.err + row, T.oos + row, T.words, set, n_el, e);
+}
+
+KV_HD inline bool kv_fe_decisive(uint32_t code) { return code == ST_FAIL || code == ST_ERROR || code == ST_CPU; }
+
+// the key of one element on its own (the host fold takes the minimum over a resource's elements)
+KV_HD inline uint32_t kv_fe_key(uint32_t code, uint32_t ord) {
+  return kv_fe_decisive(code) ? (ord << 3 | code) : code == ST_PASS ? FE_KEY_PASS : FE_KEY_NONE;
+}
+
+// the status byte of (set, resource) from the list state and the reduced key
+KV_HD inline uint32_t kv_fe_final(uint32_t lstate, uint32_t key) {
+  if (lstate == FE_LIST_OOS) return ST_CPU;
+  if (key == FE_KEY_NONE) return ST_SKIP;  // no element, or every element skipped: "rule skipped"
+  if (key == FE_KEY_PASS) return ST_PASS;  // applyCount > 0: "rule passed"
+  return key & 7u;
+}
+
+}  // namespace kv

@@ -730,7 +730,28 @@ struct Ingest {
       }
       b.vout.push_back(it->second);
     }
+    // foreach lists (kvcond.h): the list state and element count of this resource, and per
+    // element every string of the list resolved with `element` as a second root
+    const size_t nfl = ps.flists.size();
+    if (nfl && b.fout.size() != nfl) b.fout.resize(nfl);
+    for (size_t l = 0; l < nfl; l++) {
+      fe_elems.clear();
+      const uint8_t st = resolve_foreach_list(ps.flists[l], d, &fe_elems);
+      b.fstate.push_back(st);
+      b.fcount.push_back((uint32_t)fe_elems.size());
+      for (uint32_t en : fe_elems)
+        for (uint32_t k : ps.flist_keys[l]) {
+          std::string o = resolve_elem_string(ps.fkeys[k].text, d, en, ps.fkeys[k].precond);
+          auto it = b.vout_id.find(o);
+          if (it == b.vout_id.end()) {
+            it = b.vout_id.emplace(o, (uint32_t)b.vout_tab.size()).first;
+            b.vout_tab.push_back(std::move(o));
+          }
+          b.fout[l].push_back(it->second);
+        }
+    }
   }
+  std::vector<uint32_t> fe_elems;
 
   void take(JDoc& d) {
     if (group.size() < KV_LANES) group.resize(KV_LANES);
@@ -998,6 +1019,15 @@ void merge_batches(std::vector<Batch>& parts, Batch& b, uint32_t nstatic) {
       }
       for (uint32_t x : q.vout) b.vout.push_back(m[x]);
       std::vector<uint32_t>().swap(q.vout);
+      // (the foreach element rows travel with them: states and counts resource-major, the
+      // element rows of each list concatenated in resource order)
+      b.fstate.insert(b.fstate.end(), q.fstate.begin(), q.fstate.end());
+      b.fcount.insert(b.fcount.end(), q.fcount.begin(), q.fcount.end());
+      if (b.fout.size() < q.fout.size()) b.fout.resize(q.fout.size());
+      for (size_t l = 0; l < q.fout.size(); l++) {
+        for (uint32_t x : q.fout[l]) b.fout[l].push_back(m[x]);
+        std::vector<uint32_t>().swap(q.fout[l]);
+      }
     }
   }
   if (H >= 0xFFFFFFF0ull) throw std::runtime_error("ingest: string heap exceeds 4 GiB");

@@ -82,6 +82,24 @@ struct DenySet {
   std::vector<uint32_t> strs;
   std::vector<uint32_t> order;  // the same strings in the substitution's traversal order (repeats kept)
 };
+// validate.foreach on the device (KV_COMPILE_FOREACH, kvcond.h). One element-scoped condition
+// string of a list: resolved once per (resource, element) with `element` as a second variable
+// root, under the preconditions resolver (`precond`) or the strict one.
+struct FeKey {
+  uint32_t list = 0;     // PolicySet::flists index
+  uint32_t col = 0;      // its column in the list's element rows (Batch::fout[list])
+  bool precond = false;
+  std::string text;
+};
+// One interned foreach set: the list, the entry's preconditions (has_pre: a gate is left after
+// constant folding) and its deny block; CondRec indices into PolicySet::fconds, string indices
+// into PolicySet::fkeys.
+struct FeSet {
+  uint32_t list = 0;
+  bool has_pre = false;
+  CondSet pre;
+  DenySet deny;
+};
 
 // Projection trie over resource key paths referenced by any compiled pattern
 // or match block. Arrays are transparent: `elem` is the element trie.
@@ -139,6 +157,8 @@ struct RuleHost {
   std::vector<UserInfoSpec> filter_ui;  // per MFilter of this rule (match then exclude)
   std::vector<bool> filter_is_match;
   std::string const_message;            // route 3
+  uint32_t foreach_set = 0;             // a device foreach rule: 1 + PolicySet::fsets index (RuleRec::deny =
+                                        // dsets.size() + foreach_set: a row of the deny plane)
 };
 
 struct PolicySet {
@@ -214,13 +234,24 @@ struct PolicySet {
   std::vector<CondRec> dconds;
   std::vector<DenySet> dsets;
   std::unordered_map<std::string, uint32_t> dkey_id, dcond_id, dset_id;
+  // validate.foreach on the device (KV_COMPILE_FOREACH, kvcond.cpp compile_foreach): the list
+  // queries (text after `request.object`-rooted JMESPath), the element-scoped strings (ftags: the
+  // interning text of each, "<p|d><list>:" + text), the conditions over them and the foreach sets
+  // (RuleRec::deny - 1 - dsets.size()); flist_keys: the strings of each list in column order
+  std::vector<std::string> flists;
+  std::vector<FeKey> fkeys;
+  std::vector<std::string> ftags;
+  std::vector<std::vector<uint32_t>> flist_keys;
+  std::vector<CondRec> fconds;
+  std::vector<FeSet> fsets;
+  std::unordered_map<std::string, uint32_t> flist_id, ftag_id, fcond_id, fset_id;
   // columns of a Batch::vout row: the pattern-variable keys, then the condition strings of the
   // preconditions, then those of the deny blocks
   size_t vout_width() const { return vkeys.size() + ckeys.size() + dkeys.size(); }
 };
 
 // Compiles a JSON list of (already autogen-expanded) ClusterPolicy/Policy
-// objects (flags: kv_compile's KV_COMPILE_DENY). Throws std::runtime_error on malformed input.
+// objects (flags: kv_compile's KV_COMPILE_DENY | KV_COMPILE_FOREACH). Throws std::runtime_error on malformed input.
 void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flags = 0);
 
 // Host memory of the large store arrays of an ingested batch. libkvgpu (kvapi.cpp)
@@ -383,6 +414,13 @@ struct Batch {
   std::vector<uint32_t> vout;
   std::vector<std::string> vout_tab;
   std::unordered_map<std::string, uint32_t> vout_id;  // (ingest only)
+  // validate.foreach lists (PolicySet::flists), resource-major like vout: per (resource, list)
+  // the list state (kv::FE_LIST_*) and the element count, and per list the element rows: one
+  // outcome id (vout_tab) per (element, string of the list), element-major; the elements of a
+  // resource are contiguous, in list order, resources in store order
+  std::vector<uint8_t> fstate;
+  std::vector<uint32_t> fcount;
+  std::vector<std::vector<uint32_t>> fout;
 };
 
 // Per-batch tables of the pattern variables (kvvars.cpp build_dyn): the predicate of every
@@ -401,8 +439,17 @@ bool var_string_in_scope(const std::string& s, const std::string& path);
 std::string unescape_var_string(const std::string& s);
 // precond: the preconditions resolver (vars.go:62-74): a variable that fails to resolve is ""
 std::string resolve_var_string(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond = false);
-// every variable of `s` is a request.object path of the device subset (no {{@}})
-bool cond_string_in_scope(const std::string& s);
+// every variable of `s` is a request.object path of the device subset (no {{@}}); element: an
+// `element` path (a foreach entry's strings) is one too
+bool cond_string_in_scope(const std::string& s, bool element = false);
+// a foreach entry's `list`: a bare request.object field / quoted-field / index chain
+bool list_query_in_scope(const std::string& q);
+// One foreach list on resource `d` (pkg/engine/validation.go:225-283 evaluateList and the element
+// loop): returns the list state (kv::FE_LIST_*); for FE_LIST_OK appends the nodes of the elements
+// (all maps) to *elems.
+uint8_t resolve_foreach_list(const std::string& list, const JDoc& d, std::vector<uint32_t>* elems);
+// resolve_var_string with `element` = node `elem` of d as a second variable root
+std::string resolve_elem_string(const std::string& tmpl, const JDoc& d, uint32_t elem, bool precond);
 PV outcome_value(const std::string& o);
 uint32_t compile_leaf_pred(PolicySet& tbl, const PV& value);  // kvcompile.cpp
 std::string pattern_go_v(const PV& p);                         // Go %v of a scalar pattern value

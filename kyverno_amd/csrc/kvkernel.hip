@@ -35,6 +35,7 @@ using namespace kv;
 #include "kvcol.h"
 #include "kvpre.h"
 #include "kvdeny.h"
+#include "kvforeach.h"
 
 // ------------------------------------------------------------------ kernel
 extern "C" __global__ __launch_bounds__(KV_WG) __attribute__((amdgpu_waves_per_eu(4))) void kv_validate_kernel(const DevPS* __restrict__ Pp,
@@ -405,6 +406,88 @@ hipError_t launch_deny(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8
   if (n_res == 0 || n_sets == 0) return hipSuccess;
   hipLaunchKernelGGL(kv_deny_kernel, dim3((n_res + KV_WG - 1) / KV_WG, n_sets < KV_PRE_YMAX ? n_sets : KV_PRE_YMAX),
                      dim3(KV_WG), 0, stream, B, n_res, n_sets, deny_st);
+  return hipGetLastError();
+}
+}  // namespace kv
+
+// ---------------------------------------------------------------------------
+// Foreach fold (kvcond.h, kvforeach.h). kv_foreach_elem_kernel: one lane per *element* of a
+// set's list, grid.x = workgroups of 256 elements of the longest list, grid.y = foreach sets (a
+// workgroup walks sets blockIdx.y, + gridDim.y, ...). A lane folds its element (kv_foreach_elem:
+// coalesced loads of outc[string][element]) into one ST_ code. The elements of a resource are
+// contiguous and in list order, so the wave reduces them per resource with ballots alone: a lane
+// is a segment head when it is lane 0 or the previous lane's el_res differs (__shfl_up); the
+// head takes the ballots of FAIL / ERROR / CPU / PASS lanes under the mask of its piece (up to
+// the next head), finds the first decisive lane (ctz) and forms (el_ord << 3 | code) from its own
+// el_ord plus the lane distance, else the PASS key, and folds it into fe_acc[set][res] with one
+// atomicMin per (wave, segment piece). Any decisive key < FE_KEY_PASS < FE_KEY_NONE (the value
+// fe_acc is cleared to), and keys grow with the element's index, so the minimum over the pieces
+// of a resource is its first decisive element whatever waves and workgroups the segment
+// straddles. Lanes past the list's end form pieces with nothing to write. No lane leaves before
+// the wave operations.
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_elem_kernel(FeTables T, uint32_t n_res,
+                                                                            uint32_t* __restrict__ fe_acc) {
+  const uint32_t e = blockIdx.x * KV_WG + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t s = blockIdx.y; s < T.n_sets; s += gridDim.y) {
+    const uint32_t* L = T.lists + 4u * T.sets[4u * s];
+    const uint32_t n_el = L[1], el0 = L[3];
+    if (blockIdx.x * KV_WG >= n_el) continue;  // (workgroup-uniform)
+    const bool valid = e < n_el;
+    uint32_t res = 0xFFFFFFFFu, ord = 0, code = ST_SKIP;
+    if (valid) {
+      res = T.el_res[el0 + e];
+      ord = T.el_ord[el0 + e];
+      code = kv_foreach_elem(T, s, e);
+    }
+    const uint32_t prev = __shfl_up(res, 1);
+    const bool head = lane == 0u || prev != res;
+    const uint64_t heads = __ballot(head);
+    const uint64_t mf = __ballot(code == ST_FAIL), me = __ballot(code == ST_ERROR), mc = __ballot(code == ST_CPU);
+    const uint64_t mp = __ballot(valid && code == ST_PASS);
+    if (head && valid) {
+      // the piece: lanes [lane, next head)
+      const uint64_t above = lane == 63u ? 0ull : heads & (~0ull << (lane + 1u));
+      const uint64_t upto = above ? (1ull << __builtin_ctzll(above)) - 1ull : ~0ull;
+      const uint64_t piece = upto & (~0ull << lane);
+      const uint64_t dec = (mf | me | mc) & piece;
+      uint32_t key = FE_KEY_NONE;
+      if (dec) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(dec);
+        const uint32_t c = (mf >> l) & 1ull ? ST_FAIL : (me >> l) & 1ull ? ST_ERROR : ST_CPU;
+        key = (ord + (l - lane)) << 3 | c;
+      } else if (mp & piece) {
+        key = FE_KEY_PASS;
+      }
+      if (key != FE_KEY_NONE && res < n_res) atomicMin(&fe_acc[(size_t)s * n_res + res], key);
+    }
+  }
+}
+
+// kv_foreach_fin_kernel: one lane per resource, grid.y = foreach sets; the list state and the
+// reduced key into the status byte of row `set` of fe_st (the rows of DevBatch::deny_st after the
+// deny sets'): ST_CPU, ST_SKIP, ST_PASS, or the code of the first decisive element.
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_fin_kernel(FeTables T, uint32_t n_res,
+                                                                           const uint32_t* __restrict__ fe_acc,
+                                                                           uint8_t* __restrict__ fe_st) {
+  const uint64_t r = (uint64_t)blockIdx.x * KV_WG + threadIdx.x;
+  if (r >= n_res) return;
+  for (uint32_t s = blockIdx.y; s < T.n_sets; s += gridDim.y)
+    fe_st[(size_t)s * n_res + r] =
+        (uint8_t)kv_fe_final(T.lstate[(size_t)T.sets[4u * s] * n_res + r], fe_acc[(size_t)s * n_res + r]);
+}
+
+namespace kv {
+hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream) {
+  if (n_res == 0 || T.n_sets == 0) return hipSuccess;
+  const hipError_t e = hipMemsetAsync(fe_acc, 0xFF, (size_t)T.n_sets * n_res * sizeof(uint32_t), stream);
+  if (e != hipSuccess) return e;
+  const uint32_t gy = T.n_sets < KV_PRE_YMAX ? T.n_sets : KV_PRE_YMAX;
+  if (T.max_el)
+    hipLaunchKernelGGL(kv_foreach_elem_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, gy), dim3(KV_WG), 0, stream, T, n_res,
+                       fe_acc);
+  hipLaunchKernelGGL(kv_foreach_fin_kernel, dim3((n_res + KV_WG - 1) / KV_WG, gy), dim3(KV_WG), 0, stream, T, n_res,
+                     (const uint32_t*)fe_acc, fe_st);
   return hipGetLastError();
 }
 }  // namespace kv

@@ -76,6 +76,24 @@ void make_shard(const Batch& b, uint64_t lo, uint64_t hi, Batch* out) {
     s.vout.assign(b.vout.begin() + lo * K, b.vout.begin() + hi * K);
     s.vout_tab = b.vout_tab;
   }
+  if (!b.fout.empty()) {  // foreach element rows of the shard's resources (elements stay contiguous)
+    const size_t L = b.fout.size();
+    s.fstate.assign(b.fstate.begin() + lo * L, b.fstate.begin() + hi * L);
+    s.fcount.assign(b.fcount.begin() + lo * L, b.fcount.begin() + hi * L);
+    s.fout.resize(L);
+    for (size_t l = 0; l < L; l++) {
+      uint64_t e_lo = 0, e_n = 0, e_all = 0;
+      for (uint64_t r = 0; r < b.res.size(); r++) {
+        const uint32_t c = b.fcount[r * L + l];
+        if (r < lo) e_lo += c;
+        else if (r < hi) e_n += c;
+        e_all += c;
+      }
+      const size_t K = e_all ? b.fout[l].size() / e_all : 0;
+      s.fout[l].assign(b.fout[l].begin() + e_lo * K, b.fout[l].begin() + (e_lo + e_n) * K);
+    }
+    if (s.vout_tab.empty()) s.vout_tab = b.vout_tab;
+  }
   s.bytes_referenced = s.cells_used * sizeof(Node) + s.vals.size() * sizeof(Val) + s.res.size() * sizeof(Res) +
                        s.kvs.size() * sizeof(KV) + s.strs.size() + s.nsms.size() * sizeof(StrRef) +
                        (s.lsets.size() + s.asets.size()) * sizeof(KVSet);

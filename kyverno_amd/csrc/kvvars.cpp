@@ -22,6 +22,9 @@
 #include <stdexcept>
 
 #include "kvinternal.hpp"
+#include "kvpre.h"
+#include "kvdeny.h"
+#include "kvforeach.h"
 
 namespace kvh {
 
@@ -149,10 +152,15 @@ struct QStep {
 // The JMESPath subset on the device: request.object followed by field / quoted-field / index
 // steps (pkg/engine/context/evaluate.go:15-50 with kyverno's go-jmespath fork: a missing map key
 // is NotFoundError, a field of a non-map and an index of a non-array are null).
-bool parse_query(const std::string& q, std::vector<QStep>* steps) {
-  static const std::string root = "request.object";
-  if (q.compare(0, root.size(), root) != 0) return false;
-  size_t i = root.size();
+// elem (foreach entries): `element` followed by at least one step is accepted too, *elem tells
+// which root the query has.
+bool parse_query(const std::string& q, std::vector<QStep>* steps, bool* elem = nullptr) {
+  static const std::string root = "request.object", eroot = "element";
+  size_t i = 0;
+  if (elem) *elem = false;
+  if (q.compare(0, root.size(), root) == 0) i = root.size();
+  else if (elem && q.compare(0, eroot.size(), eroot) == 0 && q.size() > eroot.size()) { i = eroot.size(); *elem = true; }
+  else return false;
   steps->clear();
   while (i < q.size()) {
     if (q[i] == '[') {
@@ -199,8 +207,8 @@ bool var_query(const std::string& var, const std::string& path, std::string* q) 
 }
 
 // 0: found (*node, -1 for null), 1: unknown key (*missing)
-int query_doc(const std::vector<QStep>& steps, const JDoc& d, int64_t* node, std::string* missing) {
-  int64_t cur = d.root;
+int query_doc(const std::vector<QStep>& steps, const JDoc& d, int64_t* node, std::string* missing, int64_t from = -1) {
+  int64_t cur = from >= 0 ? from : (int64_t)d.root;
   for (const QStep& s : steps) {
     if (cur < 0) continue;  // null: every further step is null
     const JNode& n = d.at((uint32_t)cur);
@@ -308,16 +316,68 @@ bool var_string_in_scope(const std::string& s, const std::string& path) {
   return true;
 }
 
-bool cond_string_in_scope(const std::string& s) {
+bool cond_string_in_scope(const std::string& s, bool element) {
   std::vector<QStep> steps;
+  bool el = false;
   for (std::string v : find_vars(s)) {
     if (!var_initial(v)) {
       if ((unsigned char)v[0] >= 0x80) return false;
       v = v.substr(1);
     }
-    if (!parse_query(var_name(v), &steps)) return false;
+    if (!parse_query(var_name(v), &steps, element ? &el : nullptr)) return false;
+  }
+  if (element) {
+    // foreach entries: what is left around the variables holds no braces, so no variable is
+    // nested in another one or in a function call (those would only show per resource, as "C")
+    std::string rest = s;
+    for (const std::string& v : find_vars(s)) rest = replace_first(rest, v.compare(0, 2, "{{") == 0 ? v : v.substr(1), "");
+    if (rest.find("{{") != std::string::npos || rest.find("}}") != std::string::npos) return false;
   }
   return true;
+}
+
+bool list_query_in_scope(const std::string& q) {
+  std::vector<QStep> steps;
+  return parse_query(q, &steps);
+}
+
+namespace {
+bool has_null(const JDoc& d, uint32_t node) {
+  const JNode& n = d.at(node);
+  if (n.t == J_NULL) return true;
+  if (n.t == J_MAP || n.t == J_ARR)
+    for (uint32_t c = n.first; c < n.first + n.count; c++)
+      if (has_null(d, c)) return true;
+  return false;
+}
+}  // namespace
+
+uint8_t resolve_foreach_list(const std::string& list, const JDoc& d, std::vector<uint32_t>* elems) {
+  std::vector<QStep> steps;
+  if (!parse_query(list, &steps)) return FE_LIST_OOS;
+  int64_t node = -1;
+  std::string missing;
+  // a missing map key is NotFound: evaluateList fails, the entry is skipped (validation.go:232-236)
+  if (query_doc(steps, d, &node, &missing) == 1) return FE_LIST_EMPTY;
+  if (node < 0) return FE_LIST_OOS;  // a null result (an index past the end, a field of a non-map)
+  const JNode& n = d.at((uint32_t)node);
+  const size_t e0 = elems->size();
+  if (n.t == J_MAP) {  // not a list: a one-element list (validation.go:329-333)
+    elems->push_back((uint32_t)node);
+  } else if (n.t == J_ARR) {
+    if (n.count > FE_MAX_ELEMS) return FE_LIST_OOS;
+    for (uint32_t c = n.first; c < n.first + n.count; c++) elems->push_back(c);
+  } else {
+    return FE_LIST_OOS;
+  }
+  // maps without a null at any depth: the element is merged into the context as a JSON merge
+  // patch, whose treatment of nulls no reference test pins
+  for (size_t i = e0; i < elems->size(); i++)
+    if (d.at((*elems)[i]).t != J_MAP || has_null(d, (*elems)[i])) {
+      elems->resize(e0);
+      return FE_LIST_OOS;
+    }
+  return FE_LIST_OK;
 }
 
 std::string unescape_var_string(const std::string& s) {
@@ -330,7 +390,18 @@ std::string unescape_var_string(const std::string& s) {
 // with request.object = resource `d`. Outcome encoding (interned per batch): "S" + string,
 // "F" + 8 raw bytes of a float64, "B0" / "B1", "N" (null), "E" + the error text, "C" (outside
 // the device scope), "M" (a map or array: a structural pattern, outside the scope).
+namespace {
+std::string resolve_impl(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond, int64_t elem);
+}
 std::string resolve_var_string(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond) {
+  return resolve_impl(tmpl, path, d, precond, -1);
+}
+std::string resolve_elem_string(const std::string& tmpl, const JDoc& d, uint32_t elem, bool precond) {
+  return resolve_impl(tmpl, "", d, precond, (int64_t)elem);
+}
+namespace {
+// elem >= 0: a variable whose query starts at `element` resolves against node `elem` of d
+std::string resolve_impl(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond, int64_t elem) {
   std::string value = tmpl;
   std::vector<QStep> steps;
   auto vars = find_vars(value);
@@ -346,11 +417,12 @@ std::string resolve_var_string(const std::string& tmpl, const std::string& path,
         v = v.substr(1);
       }
       std::string q;
-      if (!var_query(var_name(v), path, &q) || !parse_query(q, &steps)) return "C";
+      bool el = false;
+      if (!var_query(var_name(v), path, &q) || !parse_query(q, &steps, elem >= 0 ? &el : nullptr)) return "C";
       int64_t node = -1;
       std::string missing;
       bool unresolved = false;
-      if (query_doc(steps, d, &node, &missing) == 1) {
+      if (query_doc(steps, d, &node, &missing, el ? elem : -1) == 1) {
         if (!precond) return "EUnknown key \"" + missing + "\" in path";
         unresolved = true;  // newPreconditionsVariableResolver (vars.go:62-74): the value is ""
       }
@@ -382,6 +454,7 @@ std::string resolve_var_string(const std::string& tmpl, const std::string& path,
   }
   return "S" + unescape_var_string(value);
 }
+}  // namespace
 
 PV outcome_value(const std::string& o) {
   PV p;

@@ -15,8 +15,10 @@ Rules the device does not evaluate (context, deny, foreach, pattern variables ot
 status ``"cpu"``: the Go host runs ``processValidationRule`` for them. They are not
 counted. Preconditions of the device forms (``kyverno_amd.batch``) are evaluated with the rule: a
 pair whose preconditions do not hold is ``"skip"`` with the message ``preconditions not met``
-(validation.go:175-184). ``validate.deny`` rules are evaluated on the device only by callers that
-opt in (``batch.PolicySet(deny=True)``, ``cli.evaluate(deny=True)``); here they stay ``"cpu"``.
+(validation.go:175-184). ``validate.deny`` and ``validate.foreach`` rules are evaluated on the
+device only by callers that opt in (``batch.PolicySet(deny=True, foreach=True)``,
+``cli.evaluate(deny=True, foreach=True)``); here they stay ``"cpu"``. Their statuses are counted as
+any other rule's (``report.py``: a foreach ``skip`` is a skip, ``error`` an error).
 """
 from __future__ import annotations
 

@@ -25,7 +25,7 @@ import decimal
 import re
 
 __all__ = ["MessageVariableError", "UnsupportedMessageVariable", "substitute_message", "has_variable",
-           "go_json_marshal", "MessageVariableNotFound"]
+           "go_json_marshal", "MessageVariableNotFound", "query"]
 
 
 class MessageVariableError(ValueError):
@@ -111,6 +111,11 @@ def _query(expr: str, context) -> object:
     return cur
 
 
+def query(expr: str, context) -> object:
+    """``_query`` for callers outside this module (the list of a foreach entry)."""
+    return _query(expr, context)
+
+
 def _operator(p: str) -> str:
     """operator.GetOperatorFromStringPattern (pkg/engine/operator/operator.go:33-67)."""
     if len(p) < 2:
@@ -187,10 +192,14 @@ def go_json_marshal(v) -> str:
     raise MessageVariableError(f"failed to marshal {type(v).__name__}")
 
 
-def substitute_message(msg: str, resource: dict) -> str:
+def substitute_message(msg: str, resource: dict, element: dict | None = None) -> str:
     """The message after SubstituteAll with context ``request.object = resource``: references
-    (vars.go:253-309), then substituteVariablesIfAny (vars.go:319-398), then ``\\{{`` unescaping."""
+    (vars.go:253-309), then substituteVariablesIfAny (vars.go:319-398), then ``\\{{`` unescaping.
+    ``element``: the context also holds it as ``element`` (the deciding element of a foreach rule,
+    validation.go:243-247)."""
     context = {"request": {"object": resource}}
+    if element is not None:
+        context["element"] = element
     # substituteReferencesIfAny on the message document (vars.go:253-309): the first reference
     # decides. resolveReference (vars.go:450-475) looks the path up in the message string itself,
     # whose only leaf sits at path "", so nothing is ever found: an empty path errors (nil element:

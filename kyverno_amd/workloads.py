@@ -155,6 +155,42 @@ def c2_deny_policies() -> list[dict]:
     return pols
 
 
+# Eight deny blocks over the elements of spec.containers of the synthetic Pods (kv_synth: images
+# "<registry>/<name>:<tag>", names c0, c1, ...), of every device form, one mixing both roots.
+C2_FOREACH_SETS = [
+    [{"key": "{{element.image}}", "operator": "Equals", "value": "*:latest"}],
+    {"all": [{"key": "{{element.name}}", "operator": "NotEquals", "value": "c0"}]},
+    {"any": [{"key": "{{element.name}}", "operator": "In", "value": ["c2", "c3"]},
+             {"key": "{{element.image}}", "operator": "Equals", "value": "docker.io/*"}]},
+    {"all": [{"key": "{{element.name}}", "operator": "AnyNotIn", "value": ["c0", "c1"]},
+             {"key": "{{element.image}}", "operator": "NotEquals", "value": ""}]},
+    {"any": [{"key": "{{element.image}}", "operator": "Equals", "value": "*e*"}],
+     "all": [{"key": "{{element.name}}", "operator": "NotEquals", "value": "c1"}]},
+    {"all": [{"key": "{{element.imagePullPolicy}}", "operator": "AllNotIn", "value": ["Always"]}]},
+    {"any": [{"key": "{{element.name}}", "operator": "Equals", "value": ""},
+             {"key": "{{element.name}}", "operator": "Equals", "value": "c3"}]},
+    {"all": [{"key": "{{request.object.metadata.namespace}}/{{element.name}}",
+              "operator": "Equals", "value": "ns-1*/c1"}]},
+]
+
+
+def c2_foreach_policies() -> list[dict]:
+    """The foreach twin of ``c2_deny_policies``: the 100 C2 rules, each rewritten as a single-entry
+    ``validate.foreach`` over ``request.object.spec.containers`` with a ``deny`` block on
+    ``{{element.image}}`` / ``{{element.name}}`` (rule i: block i mod 8), to be compiled with
+    ``PolicySet(..., foreach=True)``: the workload of the foreach fold's measurement (DESIGN.md §3
+    *Foreach*)."""
+    import copy
+
+    pols = c2_policies()
+    for i, r in enumerate(pols[0]["spec"]["rules"]):
+        r["validate"] = {"message": r["validate"].get("message", ""),
+                         "foreach": [{"list": "request.object.spec.containers",
+                                      "deny": {"conditions": copy.deepcopy(C2_FOREACH_SETS[i % len(C2_FOREACH_SETS)])}}]}
+    pols[0]["metadata"]["name"] = "c2-pod-rules-foreach"
+    return pols
+
+
 C3_KIND_MIX = 2  # kv_synth stream of C3: Pods/Deployments/Services 60/25/15 over 1 000 namespaces
 C3_NAMESPACES = 1000
 

@@ -1,0 +1,304 @@
+"""validate.foreach on the device, without a GPU (kvcond.cpp compile_foreach / build_foreach,
+kvforeach.h; reference pkg/engine/validation.go:204-283): the foreach model against the golden
+cases (tests/golden/foreach.json), rule routing with the compile flag on and off, interning, the
+exported symbols, the host fold (`kv_batch_foreach_fold`, the twin of the two kernels) against the
+model in caller order, the element rows through the threaded ingest's merge, and message
+variables with an element root."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import foreach_data as fd
+import foreach_model
+from kyverno_amd import _native, batch, msgvars
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIZES = [1, 63, 65, 257, 513]
+
+
+@pytest.fixture(scope="module")
+def expected(orc):
+    """The expected side of the crafted set at every size (computed once, shared)."""
+    pol = fd.crafted_policy()
+    return pol, {n: fd.Expected(orc, pol, fd.crafted_resources(n)) for n in SIZES}
+
+
+# ------------------------------------------------------------------ the model, pinned
+def test_golden_fixture_shape():
+    names = [c["name"] for c in fd.CASES]
+    assert names[:5] == ["Test_foreach_container_pass", "Test_foreach_container_fail", "Test_foreach_container_deny_fail",
+                         "Test_foreach_container_deny_success", "Test_foreach_container_deny_error"]
+    for c in fd.CASES:
+        assert c["origin"] in ("transcribed", "derived")
+        if c["origin"] == "transcribed":
+            assert c["src"].startswith("pkg/engine/validation_test.go:") and c["device"] == {"route": "cpu", "reason": "foreach"}
+        else:
+            assert c["device"] == {"route": "gpu", "reason": ""}
+    assert sum(c["origin"] == "derived" for c in fd.CASES) >= 4
+
+
+@pytest.mark.parametrize("case", [c for c in fd.CASES if c["origin"] == "derived"], ids=lambda c: c["name"])
+def test_model_matches_derived_cases(orc, case):
+    m = foreach_model.Model(orc)
+    st, el, msgs = m.foreach(case["policy"]["spec"]["rules"][0], case["resource"])
+    assert (st, el, msgs) == (case["status"], case["element"], [case["message"]])
+
+
+@pytest.mark.parametrize("case", fd.CASES, ids=lambda c: c["name"])
+def test_golden_routes(case):
+    """The reference's own cases use regex_match or pattern: CPU-routed with the flag too; the
+    derived ones are device rules with it and CPU-routed without."""
+    on = batch.PolicySet([case["policy"]], foreach=True).rules[0]
+    off = batch.PolicySet([case["policy"]]).rules[0]
+    want = (batch.ROUTE_CPU if case["device"]["route"] == "cpu" else batch.ROUTE_GPU, case["device"]["reason"])
+    assert (on.route, on.route_reason) == want and on.foreach == (want[0] == batch.ROUTE_GPU)
+    assert (off.route, off.route_reason, off.foreach) == (batch.ROUTE_CPU, "foreach", False)
+
+
+@pytest.mark.parametrize("case", [c for c in fd.CASES if c["origin"] == "derived"], ids=lambda c: c["name"])
+def test_host_fold_derived_cases(case):
+    ps = batch.PolicySet([case["policy"]], foreach=True)
+    st, el = ps.foreach_fold(batch.Batch(ps, [case["resource"]]))
+    assert batch.STATUS_NAMES[st[0, 0]] == case["status"]
+    assert el[0, 0] == (fd.NO_ELEM if case["element"] is None else case["element"])
+
+
+# ------------------------------------------------------------------ routing
+def _entry(**kw):
+    e = {"list": fd.LIST, "deny": {"conditions": [{"key": "{{element.image}}", "operator": "Equals", "value": "x"}]}}
+    e.update(kw)
+    return e
+
+
+def _cond(key, op="Equals", value="x"):
+    return {"conditions": {"all": [{"key": key, "operator": op, "value": value}]}}
+
+
+PRE = {"all": [{"key": "{{request.object.metadata.labels.tier}}", "operator": "Equals", "value": "web"}]}
+PRE_OUT = {"all": [{"key": "{{request.operation}}", "operator": "Equals", "value": "CREATE"}]}
+EPRE = {"any": [{"key": "{{element.name}}", "operator": "NotEquals", "value": "c0"}]}
+IN_SCOPE = {
+    "plain": _entry(),
+    "quoted-list": _entry(list='request.object.spec."containers"'),
+    "index-list": _entry(list="request.object.spec.containers[0]"),
+    "template-list": _entry(list="request.object.spec.template.spec.containers"),
+    "entry-preconditions": _entry(preconditions=EPRE),
+    "null-preconditions": _entry(preconditions=None),
+    "mixed": _entry(deny=_cond("{{request.object.metadata.namespace}}/{{element.name}}")),
+    "object-only": _entry(deny=_cond("{{request.object.metadata.name}}")),
+    "value-side": _entry(deny=_cond("x", value="{{element.name}}")),
+    "nested-field": _entry(deny=_cond('{{element.securityContext."run-as".user[0]}}')),
+    "constant": _entry(deny=_cond("a", value="a")),
+}
+OUT_OF_SCOPE = {
+    "whole-element": _entry(deny=_cond("{{element}}")),
+    "nested-variable": _entry(deny=_cond("{{ regex_match('{{element.image}}', 'docker.io') }}", value=False)),
+    "function": _entry(deny=_cond("{{ length(element.name) }}")),
+    "at": _entry(deny=_cond("{{@}}")),
+    "element-wildcard": _entry(deny=_cond("{{element.ports[*].name}}")),
+    "list-with-braces": _entry(list="{{request.object.spec.containers}}"),
+    "list-wildcard": _entry(list="request.object.spec.containers[*]"),
+    "list-other-root": _entry(list="request.operation"),
+    "list-not-string": _entry(list=["a"]),
+    "entry-pattern": {"list": fd.LIST, "pattern": {"name": "c*"}},
+    "entry-any-pattern": _entry(anyPattern=[{"name": "c*"}]),
+    "entry-context": _entry(context=[{"name": "cm", "configMap": {"name": "a", "namespace": "b"}}]),
+    "entry-list-preconditions": _entry(preconditions=EPRE["any"]),
+    "entry-preconditions-out": _entry(preconditions=PRE_OUT),
+    "deny-missing": {"list": fd.LIST},
+    "deny-empty": _entry(deny={}),
+    "map-operand": _entry(deny=_cond("{{element.name}}", value={"a": "b"})),
+}
+
+
+def _routing_policy():
+    def rule(name, validate, **more):
+        return {"name": name, "match": fd.POD, "validate": validate, **more}
+    rules = [rule(n, {"message": "m", "foreach": [json.loads(json.dumps(e))]}) for n, e in list(IN_SCOPE.items()) + list(OUT_OF_SCOPE.items())]
+    rules += [
+        rule("x-two-entries", {"foreach": [_entry(), _entry()]}),
+        rule("x-no-entries", {"foreach": []}),
+        rule("x-behind-preconditions", {"foreach": [_entry()]}, preconditions=PRE),
+        rule("x-preconditions-out", {"foreach": [_entry()]}, preconditions=PRE_OUT),
+        rule("x-context", {"foreach": [_entry()]}, context=[{"name": "cm", "configMap": {"name": "a", "namespace": "b"}}]),
+        rule("x-pattern-beside", {"message": "m", "pattern": {"kind": "Pod"}, "foreach": [_entry()]}),
+        rule("x-deny-beside", {"deny": {"conditions": []}, "foreach": [_entry()]}),
+        rule("x-plain-deny", {"deny": {"conditions": [{"key": "{{request.object.metadata.name}}", "operator": "Equals", "value": "x"}]}}),
+        rule("x-plain-pattern", {"message": "m", "pattern": {"kind": "Pod"}}),
+    ]
+    return fd.pd._policy("foreach-routing", rules)
+
+
+def test_routing_flag_on():
+    ps = batch.PolicySet([_routing_policy()], foreach=True)
+    got = {r.name: (r.route, r.route_reason) for r in ps.rules}
+    sets = dict(zip([r.name for r in ps.rules], ps.foreach_info["rule_sets"]))
+    for name in IN_SCOPE:
+        assert got[name] == (batch.ROUTE_GPU, "") and sets[name] > 0, (name, got[name], sets[name])
+    for name in OUT_OF_SCOPE:
+        assert got[name] == (batch.ROUTE_CPU, "foreach") and sets[name] == 0, (name, got[name])
+    assert got["x-two-entries"] == got["x-no-entries"] == (batch.ROUTE_CPU, "foreach")
+    assert got["x-behind-preconditions"] == (batch.ROUTE_GPU, "") and sets["x-behind-preconditions"] > 0
+    assert got["x-preconditions-out"] == (batch.ROUTE_CPU, "preconditions") and sets["x-preconditions-out"] == 0
+    for name in ("x-context", "x-pattern-beside", "x-deny-beside"):
+        assert got[name] == (batch.ROUTE_CPU, "foreach") and sets[name] == 0, (name, got[name])
+    # independent of KV_COMPILE_DENY: the plain deny rule stays routed, and is no foreach rule
+    assert got["x-plain-deny"] == (batch.ROUTE_CPU, "deny") and got["x-plain-pattern"] == (batch.ROUTE_GPU, "")
+    assert [r.foreach for r in ps.rules] == [s > 0 for s in ps.foreach_info["rule_sets"]]
+    assert not any(r.deny for r in ps.rules) and not any(ps.deny_info["rule_sets"])
+    both = batch.PolicySet([_routing_policy()], foreach=True, deny=True)
+    bi = {r.name: (r.deny, r.foreach) for r in both.rules}
+    assert bi["x-plain-deny"] == (True, False) and bi["plain"] == (False, True)
+    assert both.deny_info["sets"] == 1 and both.foreach_info["rule_sets"] == ps.foreach_info["rule_sets"]
+
+
+def test_routing_flag_off(expected):
+    """Without KV_COMPILE_FOREACH nothing changes: every foreach rule is (CPU, "foreach"), with
+    KV_COMPILE_DENY too; no foreach tables."""
+    for kw in ({}, {"deny": True}):
+        for pol in (_routing_policy(), expected[0]):
+            ps = batch.PolicySet([pol], **kw)
+            for r, src in zip(ps.rules, pol["spec"]["rules"]):
+                if fd.is_foreach(src):
+                    assert (r.route, r.route_reason, r.foreach) == (batch.ROUTE_CPU, "foreach", False), r.name
+            info = ps.foreach_info
+            assert (info["sets"], info["lists"], info["conditions"], info["strings"]) == (0, 0, 0, 0)
+            assert not any(info["rule_sets"])
+
+
+def test_crafted_routes(expected):
+    pol = expected[0]
+    ps = batch.PolicySet([pol], foreach=True)
+    for r, src in zip(ps.rules, pol["spec"]["rules"]):
+        want = (batch.ROUTE_CPU, "foreach") if src["name"] in fd.CPU_RULES else (batch.ROUTE_GPU, "")
+        assert (r.route, r.route_reason) == want, r.name
+        assert r.foreach == fd.on_device(src), r.name
+
+
+def test_interning(expected):
+    """30 rules over 3 distinct entries and 2 lists compile to 3 foreach sets; a string is keyed by
+    list, text and resolver; the precondition and deny tables stay empty."""
+    E = "{{element.image}}"
+    entries = [
+        {"list": fd.LIST, "deny": {"conditions": {"all": [{"key": E, "operator": "Equals", "value": "a"}]}}},
+        {"list": fd.INIT, "deny": {"conditions": {"all": [{"key": E, "operator": "Equals", "value": "a"}]}}},
+        {"list": fd.LIST, "preconditions": {"all": [{"key": E, "operator": "NotEquals", "value": "b"}]},
+         "deny": {"conditions": [{"key": E, "operator": "Equals", "value": "a"},
+                                 {"key": "{{element.name}}", "operator": "In", "value": ["x", "y"]}]}},
+    ]
+    rules = [{"name": f"r{i}", "match": fd.POD, "validate": {"foreach": [json.loads(json.dumps(entries[i % 3]))]}}
+             for i in range(30)]
+    ps = batch.PolicySet([fd.pd._policy("interning", rules)], foreach=True)
+    assert all(r.route == batch.ROUTE_GPU and r.foreach for r in ps.rules)
+    info = ps.foreach_info
+    # strings: image (strict, containers), image (strict, initContainers), image (preconditions,
+    # containers), name (strict, containers); conditions: one per string, the shared one once
+    assert (info["sets"], info["lists"], info["conditions"], info["strings"]) == (3, 2, 4, 4), info
+    assert info["rule_sets"] == [1 + i % 3 for i in range(30)]
+    assert ps.precondition_info == {"sets": 0, "conditions": 0, "strings": 0}
+    assert ps.deny_info["sets"] == 0
+    # the crafted set: the two rules over the same entry share a set
+    pol = expected[0]
+    cs = batch.PolicySet([pol], foreach=True).foreach_info
+    names = [r["name"] for r in pol["spec"]["rules"]]
+    assert cs["rule_sets"][names.index("no-latest")] == cs["rule_sets"][names.index("shared")] == \
+        cs["rule_sets"][names.index("behind-preconditions")] > 0
+    assert cs["lists"] == 3
+
+
+def test_exported_symbols():
+    lib = _native.lib()
+    for s in ("kv_policyset_foreach_sets", "kv_rule_foreach_set", "kv_batch_foreach_fold", "kv_result_foreach_element",
+              "kv_result_foreach_message"):
+        assert s in _native.EXPORTED_SYMBOLS and getattr(lib, s) is not None
+    hdr = open(os.path.join(ROOT, "include", "kvgpu.h")).read()
+    assert "KV_COMPILE_FOREACH = 4" in hdr
+    assert "int kv_rule_foreach_set(const kv_policyset* ps, uint32_t rule, uint32_t* set);" in hdr
+    assert "int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* index);" in hdr
+    assert "int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);" in hdr
+    assert batch.COMPILE_FOREACH == 4
+
+
+def test_workload_twin():
+    from kyverno_amd import workloads
+
+    pols = workloads.c2_foreach_policies()
+    assert len(pols[0]["spec"]["rules"]) == 100
+    ps = batch.PolicySet(pols, foreach=True)
+    assert all(r.route == batch.ROUTE_GPU and r.foreach for r in ps.rules)
+    assert ps.foreach_info["sets"] == 8 and ps.foreach_info["lists"] == 1
+    assert all((r.route, r.route_reason) == (batch.ROUTE_CPU, "foreach") for r in batch.PolicySet(pols).rules)
+
+
+# ------------------------------------------------------------------ the host fold against the model
+def test_check_honest(expected):
+    for n in SIZES:
+        expected[1][n].check_honest(full=n == 513)
+    counts = {len(r["spec"]["containers"]) for r in expected[1][513].resources if isinstance(r["spec"].get("containers"), list)}
+    assert counts >= {0, 1, 2, 3, 5, 64, 70, 300}
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_host_fold_matches_model(expected, n):
+    """kv_batch_foreach_fold per foreach set against the model alone, in caller order (the store
+    order groups the Deployments apart from the Pods): status and deciding element of every
+    resource, whatever match and the rule's preconditions say."""
+    pol, exp = expected[0], expected[1][n]
+    ps = batch.PolicySet([pol], foreach=True)
+    st, el = ps.foreach_fold(batch.Batch(ps, exp.resources))
+    sets = ps.foreach_info["rule_sets"]
+    bad = []
+    for ri, rule in enumerate(pol["spec"]["rules"]):
+        if not fd.on_device(rule):
+            assert sets[ri] == 0
+            continue
+        for k in range(n):
+            got = (int(st[sets[ri] - 1, k]), int(el[sets[ri] - 1, k]))
+            if got != (int(exp.fold[ri, k]), int(exp.fold_elem[ri, k])):
+                bad.append((rule["name"], k, got, (int(exp.fold[ri, k]), int(exp.fold_elem[ri, k]))))
+    assert not bad, bad[:20]
+
+
+def test_merged_batches_carry_element_rows():
+    """The threaded ingest (parts merged, outcome ids re-interned) gives the fold of the serial one."""
+    pol = fd.crafted_policy()
+    data = "\n".join(json.dumps(r) for r in fd.crafted_resources(1100)).encode()
+    assert len(data) >= 1 << 20  # (below that the ingest is serial)
+    ps = batch.PolicySet([pol], foreach=True)
+    got = []
+    for t in ("1", "4"):
+        os.environ["KVGPU_INGEST_THREADS"] = t
+        try:
+            got.append(ps.foreach_fold(batch.Batch(ps, data)))
+        finally:
+            os.environ.pop("KVGPU_INGEST_THREADS", None)
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+    assert len({int(x) for x in np.unique(got[0][0])}) >= 5
+
+
+def test_fold_range_checks():
+    ps = batch.PolicySet([fd.crafted_policy()], foreach=True)
+    b = batch.Batch(ps, fd.crafted_resources(3))
+    out = np.zeros(3, dtype=np.uint8)
+    lib = _native.lib()
+    assert lib.kv_batch_foreach_fold(ps._h, b._h, ps.foreach_info["sets"], out.ctypes.data, None, 3) == -4
+    assert lib.kv_batch_foreach_fold(ps._h, b._h, 0, out.ctypes.data, None, 2) == -4
+    assert lib.kv_batch_foreach_fold(ps._h, b._h, 0, out.ctypes.data, None, 3) == 0
+
+
+# ------------------------------------------------------------------ messages
+def test_msgvars_element_root():
+    res = {"metadata": {"namespace": "ns1"}, "spec": {}}
+    el = {"name": "c1", "image": "nginx:1", "ports": [{"port": 80}]}
+    sub = msgvars.substitute_message
+    assert sub("image {{element.image}} of {{ element.name }} in {{request.object.metadata.namespace}}", res, el) == \
+        "image nginx:1 of c1 in ns1"
+    assert sub("{{element.name}}", res, el) == "c1"
+    assert sub("port {{element.ports[0].port}}", res, el) == "port 80"
+    with pytest.raises(msgvars.MessageVariableNotFound):
+        sub("{{element.missing}}", res, el)
+    with pytest.raises(msgvars.MessageVariableNotFound):  # no element in the context
+        sub("x {{element.name}}", res)
+    assert sub("plain {{request.object.metadata.namespace}}", res) == "plain ns1"
