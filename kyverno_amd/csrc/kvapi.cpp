@@ -23,8 +23,7 @@
 #include "../../include/kvgpu.h"
 #include "kvcond.h"
 #include "kvdev.h"
-#include "kvpre.h"
-#include "kvdeny.h"
+#include "kvblocks.h"
 #include "kvforeach.h"
 #include "kvinternal.hpp"
 #include "kvjit.hpp"
@@ -398,19 +397,12 @@ struct DevBatchRes {
   // families and their per-group element-row prefixes; build time and pool size
   DevBuf pcol, pcold, pfam, perow;
   double pcol_ms = 0;
-  // preconditions (kvcond.h): the gate's tables and the plane kv_precond_kernel wrote; its
-  // HIP-event time
-  DevBuf presets, preents, preoutc, pretruth, preunk, prest;
-  double pre_ms = 0;
-  // validate.deny on the device (kvcond.h): the fold's tables, the plane kv_deny_kernel wrote and
-  // its HIP-event time
-  DevBuf dnsets, dnents, dnoutc, dntruth, dnunk, dnerr, dnoos, dnst;
-  double deny_ms = 0;
-  // validate.foreach on the device (kvcond.h FeHost): its tables (in FeHost's order), the
-  // reduction keys fe_acc[set][res], and the HIP-event time of the two kernels; their status
-  // bytes are the rows of dnst after the deny sets'
-  DevBuf fe[14], feacc;
-  double fe_ms = 0;
+  // condition blocks (kvcond.h): the tables of the gate, of validate.deny and of validate.foreach
+  // (its gate and deny blocks, its own five tables, the reduction keys fe_acc[set][res]), each
+  // list in its host struct's order; the plane kv_precond_kernel wrote, and the one kv_deny_kernel
+  // (rows of the deny sets) and the foreach kernels (rows after them) wrote; HIP-event times
+  DevBuf pre[5], dn[7], feg[2], fed[7], fe[5], feacc, prest, dnst;
+  double pre_ms = 0, deny_ms = 0, fe_ms = 0;
   DevBatch view{};
 };
 
@@ -437,8 +429,8 @@ struct kv_batch {
     return dyn;
   }
   std::once_flag pre_once;
-  PreHost pre;  // precondition tables (build_pre), on first use by the host accessors
-  const PreHost& pre_host(const PolicySet& ps) {
+  CondHost pre;  // precondition tables (build_pre), on first use by the host accessors
+  const CondHost& pre_host(const PolicySet& ps) {
     std::call_once(pre_once, [&]() { build_pre(ps, b, &pre); });
     return pre;
   }
@@ -1154,78 +1146,63 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     v.dleaf = (const uint32_t*)d->dleaf.p;
     v.dyn_st = (const uint8_t*)d->dynst.p;
   }
-  // preconditions: the gate's tables go on the upload stream (no blocking copy; `pre` lives until
-  // the stream is drained below), the kernel behind them
-  PreHost pre;
-  const uint32_t n_sets = (uint32_t)ps.csets.size();
+  // condition blocks: their tables go on the upload stream (no blocking copy; the host structs live
+  // until the stream is drained below), the kernels behind them. The deny plane has a row per deny
+  // set, then per foreach set.
+  auto up = [&](DevBuf* bufs, std::initializer_list<const std::vector<uint32_t>*> src, const uint32_t** dp) {
+    for (const std::vector<uint32_t>* v : src) {
+      bufs->alloc(std::max<size_t>(v->size() * sizeof(uint32_t), 16), device);
+      if (!v->empty()) HIPCHK(hipMemcpyAsync(bufs->p, v->data(), v->size() * sizeof(uint32_t), hipMemcpyHostToDevice, us));
+      *dp++ = (const uint32_t*)(bufs++)->p;
+    }
+  };
+  auto up_blocks = [&](DevBuf* bufs, const CondHost& h, bool strict) {  // (a gate has no err / oos planes)
+    const uint32_t* dp[7] = {};
+    up(bufs, {&h.sets, &h.ents, &h.outc, &h.truth, &h.unk}, dp);
+    if (strict) up(bufs + 5, {&h.err, &h.oos}, dp + 5);
+    return CondBlocks{dp[0], dp[1], dp[2], dp[3], dp[4], dp[5], dp[6], h.words};
+  };
+  struct Timed {
+    hipEvent_t e0, e1;
+    double* ms;
+  };
+  std::vector<Timed> timed;
+  auto timed_launch = [&](double* ms, auto&& launch) {
+    Timed t{nullptr, nullptr, ms};
+    HIPCHK(hipEventCreate(&t.e0));
+    HIPCHK(hipEventCreate(&t.e1));
+    HIPCHK(hipEventRecord(t.e0, us));
+    HIPCHK(launch());
+    HIPCHK(hipEventRecord(t.e1, us));
+    timed.push_back(t);
+  };
+  CondHost pre, dn;
+  FeHost fh;
+  CondBlocks pt{}, dt{};
+  FeTables ft{};
+  const uint32_t n_sets = (uint32_t)ps.csets.size(), n_dsets = (uint32_t)ps.dsets.size(),
+                 n_fsets = (uint32_t)ps.fsets.size();
   if (n_sets && !b.res.empty()) {
     build_pre(ps, b, &pre);
-    auto up = [&](DevBuf& buf, const std::vector<uint32_t>& src) {
-      buf.alloc(std::max<size_t>(src.size() * sizeof(uint32_t), 16), device);
-      if (!src.empty())
-        HIPCHK(hipMemcpyAsync(buf.p, src.data(), src.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us));
-    };
-    up(d->presets, pre.sets);
-    up(d->preents, pre.ents);
-    up(d->preoutc, pre.outc);
-    up(d->pretruth, pre.truth);
-    up(d->preunk, pre.unk);
+    pt = up_blocks(d->pre, pre, false);
     d->prest.alloc((size_t)n_sets * b.res.size(), device);
-    v.pre_sets = (const uint32_t*)d->presets.p;
-    v.pre_ents = (const uint32_t*)d->preents.p;
-    v.pre_outc = (const uint32_t*)d->preoutc.p;
-    v.pre_truth = (const uint32_t*)d->pretruth.p;
-    v.pre_unk = (const uint32_t*)d->preunk.p;
-    v.pre_words = pre.words;
-    v.n_pre_sets = n_sets;
     v.pre_st = (const uint8_t*)d->prest.p;
   }
-  // validate.deny: the fold's tables and its kernel, as the gate's
-  DenyHost dn;
-  const uint32_t n_dsets = (uint32_t)ps.dsets.size();
   if (n_dsets && !b.res.empty()) {
     build_deny(ps, b, &dn);
-    auto up = [&](DevBuf& buf, const std::vector<uint32_t>& src) {
-      buf.alloc(std::max<size_t>(src.size() * sizeof(uint32_t), 16), device);
-      if (!src.empty())
-        HIPCHK(hipMemcpyAsync(buf.p, src.data(), src.size() * sizeof(uint32_t), hipMemcpyHostToDevice, us));
-    };
-    up(d->dnsets, dn.sets);
-    up(d->dnents, dn.ents);
-    up(d->dnoutc, dn.outc);
-    up(d->dntruth, dn.truth);
-    up(d->dnunk, dn.unk);
-    up(d->dnerr, dn.err);
-    up(d->dnoos, dn.oos);
-    v.deny_sets = (const uint32_t*)d->dnsets.p;
-    v.deny_ents = (const uint32_t*)d->dnents.p;
-    v.deny_outc = (const uint32_t*)d->dnoutc.p;
-    v.deny_truth = (const uint32_t*)d->dntruth.p;
-    v.deny_unk = (const uint32_t*)d->dnunk.p;
-    v.deny_err = (const uint32_t*)d->dnerr.p;
-    v.deny_oos = (const uint32_t*)d->dnoos.p;
-    v.deny_words = dn.words;
-    v.n_deny_sets = n_dsets;
+    dt = up_blocks(d->dn, dn, true);
   }
-  // validate.foreach: its tables likewise; the plane has a row per deny set, then per foreach set
-  FeHost fh;
-  FeTables ft{};
-  const uint32_t n_fsets = (uint32_t)ps.fsets.size();
   if (n_fsets && !b.res.empty()) {
     build_foreach(ps, b, &fh);
-    const std::vector<uint32_t>* src[14] = {&fh.sets, &fh.lists, &fh.psets, &fh.pents, &fh.dsets, &fh.dents, &fh.outc,
-                                            &fh.truth, &fh.unk, &fh.err, &fh.oos, &fh.el_res, &fh.el_ord, &fh.lstate};
-    const uint32_t* dp[14];
-    for (int i = 0; i < 14; i++) {
-      d->fe[i].alloc(std::max<size_t>(src[i]->size() * sizeof(uint32_t), 16), device);
-      if (!src[i]->empty())
-        HIPCHK(hipMemcpyAsync(d->fe[i].p, src[i]->data(), src[i]->size() * sizeof(uint32_t), hipMemcpyHostToDevice, us));
-      dp[i] = (const uint32_t*)d->fe[i].p;
-    }
+    // (allocation order matters to what the buffer pool hands the next batch: keep it)
+    const uint32_t *dp[5], *gp[2];
+    up(d->fe, {&fh.sets, &fh.lists}, dp);
+    up(d->feg, {&fh.gate.sets, &fh.gate.ents}, gp);
     ft = fh.view();
-    ft.sets = dp[0]; ft.lists = dp[1]; ft.psets = dp[2]; ft.pents = dp[3]; ft.dsets = dp[4]; ft.dents = dp[5];
-    ft.outc = dp[6]; ft.truth = dp[7]; ft.unk = dp[8]; ft.err = dp[9]; ft.oos = dp[10]; ft.el_res = dp[11];
-    ft.el_ord = dp[12]; ft.lstate = dp[13];
+    ft.gate = ft.deny = up_blocks(d->fed, fh.deny, true);
+    ft.gate.sets = gp[0]; ft.gate.ents = gp[1];
+    up(d->fe + 2, {&fh.el_res, &fh.el_ord, &fh.lstate}, dp + 2);
+    ft.sets = dp[0]; ft.lists = dp[1]; ft.el_res = dp[2]; ft.el_ord = dp[3]; ft.lstate = dp[4];
     d->feacc.alloc((size_t)n_fsets * b.res.size() * sizeof(uint32_t), device);
   }
   if ((n_dsets || n_fsets) && !b.res.empty()) {
@@ -1233,49 +1210,20 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     v.deny_st = (const uint8_t*)d->dnst.p;
   }
   d->view_dev.upload_raw(&d->view, sizeof(DevBatch), device);
-  hipEvent_t pe0 = nullptr, pe1 = nullptr, de0 = nullptr, de1 = nullptr, fe0 = nullptr, fe1 = nullptr;
-  if (v.pre_st) {
-    HIPCHK(hipEventCreate(&pe0));
-    HIPCHK(hipEventCreate(&pe1));
-    HIPCHK(hipEventRecord(pe0, us));
-    HIPCHK(launch_precond((const DevBatch*)d->view_dev.p, v.n_res, n_sets, (uint8_t*)d->prest.p, us));
-    HIPCHK(hipEventRecord(pe1, us));
-  }
-  if (v.deny_st && n_dsets) {
-    HIPCHK(hipEventCreate(&de0));
-    HIPCHK(hipEventCreate(&de1));
-    HIPCHK(hipEventRecord(de0, us));
-    HIPCHK(launch_deny((const DevBatch*)d->view_dev.p, v.n_res, n_dsets, (uint8_t*)d->dnst.p, us));
-    HIPCHK(hipEventRecord(de1, us));
-  }
-  if (v.deny_st && n_fsets) {
-    HIPCHK(hipEventCreate(&fe0));
-    HIPCHK(hipEventCreate(&fe1));
-    HIPCHK(hipEventRecord(fe0, us));
-    HIPCHK(launch_foreach(ft, v.n_res, (uint32_t*)d->feacc.p, (uint8_t*)d->dnst.p + (size_t)n_dsets * v.n_res, us));
-    HIPCHK(hipEventRecord(fe1, us));
-  }
+  if (v.pre_st) timed_launch(&d->pre_ms, [&]() { return launch_cond(false, pt, v.n_res, n_sets, (uint8_t*)d->prest.p, us); });
+  if (v.deny_st && n_dsets)
+    timed_launch(&d->deny_ms, [&]() { return launch_cond(true, dt, v.n_res, n_dsets, (uint8_t*)d->dnst.p, us); });
+  if (v.deny_st && n_fsets)
+    timed_launch(&d->fe_ms, [&]() {
+      return launch_foreach(ft, v.n_res, (uint32_t*)d->feacc.p, (uint8_t*)d->dnst.p + (size_t)n_dsets * v.n_res, us);
+    });
   HIPCHK(hipStreamSynchronize(us));
-  if (fe0) {
+  for (const Timed& t : timed) {
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, fe0, fe1));
-    d->fe_ms = ms;
-    (void)hipEventDestroy(fe0);
-    (void)hipEventDestroy(fe1);
-  }
-  if (de0) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, de0, de1));
-    d->deny_ms = ms;
-    (void)hipEventDestroy(de0);
-    (void)hipEventDestroy(de1);
-  }
-  if (pe0) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, pe0, pe1));
-    d->pre_ms = ms;
-    (void)hipEventDestroy(pe0);
-    (void)hipEventDestroy(pe1);
+    HIPCHK(hipEventElapsedTime(&ms, t.e0, t.e1));
+    *t.ms = ms;
+    (void)hipEventDestroy(t.e0);
+    (void)hipEventDestroy(t.e1);
   }
   StreamPool::get().give(device, hipStreamNonBlocking, us);
   pc.release();
@@ -2813,6 +2761,18 @@ int kv_result_error(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* k
   return 0;
 }
 
+namespace {
+// a message into the caller's buffer (truncated to cap - 1 bytes); returns its full length
+int put_message(const std::string& m, char* buf, size_t cap) {
+  if (buf && cap) {
+    size_t n = std::min(cap - 1, m.size());
+    memcpy(buf, m.data(), n);
+    buf[n] = 0;
+  }
+  return (int)m.size();
+}
+}  // namespace
+
 int kv_result_error_message(const kv_result* r, uint32_t rule, uint64_t res, const char* resource_json, size_t len,
                             char* buf, size_t cap) {
   if (!r || !r->has_err() || !resource_json) return KV_E_INVALID;
@@ -2845,12 +2805,7 @@ int kv_result_error_message(const kv_result* r, uint32_t rule, uint64_t res, con
     return KV_E_PARSE;
   }
   if (m.empty()) return KV_E_INVALID;  // a compile-time constant status: no pattern error record
-  if (buf && cap) {
-    size_t n = std::min(cap - 1, m.size());
-    memcpy(buf, m.data(), n);
-    buf[n] = 0;
-  }
-  return (int)m.size();
+  return put_message(m, buf, cap);
 }
 
 int kv_result_subst_error(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
@@ -2870,13 +2825,7 @@ int kv_result_subst_error(const kv_result* r, uint32_t rule, uint64_t res, char*
     const size_t q = (size_t)(rr.dyn - 1) * nl + local;
     if (h.dyn_st[q] != ST_ERROR) return 0;
     // ruleError(rule, Validation, "variable substitution failed", err) (validation.go:186-188)
-    const std::string m = "variable substitution failed: " + kb->b.vout_tab[h.dyn_msg[q]].substr(1);
-    if (buf && cap) {
-      size_t n = std::min(cap - 1, m.size());
-      memcpy(buf, m.data(), n);
-      buf[n] = 0;
-    }
-    return (int)m.size();
+    return put_message("variable substitution failed: " + kb->b.vout_tab[h.dyn_msg[q]].substr(1), buf, cap);
   } catch (const std::exception&) {
     return KV_E_INVALID;
   }
@@ -2894,18 +2843,12 @@ int kv_result_precond_message(const kv_result* r, uint32_t rule, uint64_t res, c
     const ResultPart* p = r->part_of(s);
     if (!p) return 0;
     kv_batch* kb = p->shard ? p->shard.get() : const_cast<kv_batch*>(r->b);
-    const PreHost& h = kb->pre_host(r->ps->ps);
+    const CondHost& h = kb->pre_host(r->ps->ps);
     // the pair recomputed from the batch's tables: a SKIP of the pattern's condition anchors has
     // another cause
     if (pre_status_host(h, rr.pre - 1, kb->b.res.size(), s - p->lo) != ST_SKIP) return 0;
     // ruleResponse(rule, Validation, "preconditions not met", RuleStatusSkip) (validation.go:183-184)
-    static const std::string m = "preconditions not met";
-    if (buf && cap) {
-      size_t n = std::min(cap - 1, m.size());
-      memcpy(buf, m.data(), n);
-      buf[n] = 0;
-    }
-    return (int)m.size();
+    return put_message("preconditions not met", buf, cap);
   } catch (const std::exception&) {
     return KV_E_INVALID;
   }
@@ -2929,13 +2872,7 @@ int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char
     if (e.empty()) return 0;
     // ruleError(rule, Validation, "failed to substitute variables in deny conditions", err)
     // (validation.go:301-304)
-    const std::string m = "failed to substitute variables in deny conditions: " + e;
-    if (buf && cap) {
-      size_t n = std::min(cap - 1, m.size());
-      memcpy(buf, m.data(), n);
-      buf[n] = 0;
-    }
-    return (int)m.size();
+    return put_message("failed to substitute variables in deny conditions: " + e, buf, cap);
   } catch (const std::bad_alloc&) {  // (the lazily built store-order status matrix)
     return KV_E_NOMEM;
   } catch (const std::exception&) {
@@ -2946,8 +2883,8 @@ int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char
 int kv_policyset_deny_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings) {
   if (!ps) return KV_E_INVALID;
   if (sets) *sets = (uint32_t)ps->ps.dsets.size();
-  if (conditions) *conditions = (uint32_t)ps->ps.dconds.size();
-  if (strings) *strings = (uint32_t)ps->ps.dkeys.size();
+  if (conditions) *conditions = (uint32_t)ps->ps.deny.conds.size();
+  if (strings) *strings = (uint32_t)ps->ps.deny.keys.size();
   return 0;
 }
 
@@ -2955,7 +2892,7 @@ int kv_batch_deny_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, 
   if (!ps || !b || !status) return KV_E_INVALID;
   if (set >= ps->ps.dsets.size() || n != b->b.res.size()) return KV_E_RANGE;
   try {
-    DenyHost h;
+    CondHost h;
     build_deny(ps->ps, b->b, &h);
     const std::vector<uint32_t>& order = b->b.order;  // store index -> caller index (empty: identity)
     for (uint64_t s = 0; s < n; s++) status[order.empty() ? s : order[s]] = deny_status_host(h, set, n, s);
@@ -2980,7 +2917,7 @@ int kv_policyset_foreach_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* 
   if (!ps) return KV_E_INVALID;
   if (sets) *sets = (uint32_t)ps->ps.fsets.size();
   if (lists) *lists = (uint32_t)ps->ps.flists.size();
-  if (conditions) *conditions = (uint32_t)ps->ps.fconds.size();
+  if (conditions) *conditions = (uint32_t)ps->ps.elem.conds.size();
   if (strings) *strings = (uint32_t)ps->ps.fkeys.size();
   return 0;
 }
@@ -3024,14 +2961,6 @@ bool fe_pair(const kv_result* r, uint32_t rule, uint64_t s, kv_batch** kb, uint6
   *kb = p->shard ? p->shard.get() : const_cast<kv_batch*>(r->b);
   *local = s - p->lo;
   return true;
-}
-int put_message(const std::string& m, char* buf, size_t cap) {
-  if (buf && cap) {
-    size_t n = std::min(cap - 1, m.size());
-    memcpy(buf, m.data(), n);
-    buf[n] = 0;
-  }
-  return (int)m.size();
 }
 }  // namespace
 
@@ -3120,8 +3049,8 @@ int kv_condition_eval(const char* condition_json, size_t len, int* result) {
 int kv_policyset_cond_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings) {
   if (!ps) return KV_E_INVALID;
   if (sets) *sets = (uint32_t)ps->ps.csets.size();
-  if (conditions) *conditions = (uint32_t)ps->ps.conds.size();
-  if (strings) *strings = (uint32_t)ps->ps.ckeys.size();
+  if (conditions) *conditions = (uint32_t)ps->ps.gate.conds.size();
+  if (strings) *strings = (uint32_t)ps->ps.gate.keys.size();
   return 0;
 }
 

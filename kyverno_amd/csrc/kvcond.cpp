@@ -6,8 +6,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "kvpre.h"
-#include "kvdeny.h"
+#include "kvblocks.h"
 #include "kvforeach.h"
 
 namespace kvh {
@@ -370,18 +369,14 @@ std::string pv_key(const PV& p) {  // interning key of a constant operand
   }
 }
 
-// The interning tables a block compiles into: the preconditions' (PolicySet::ckeys / conds) or
-// the deny blocks' (dkeys / dconds). strs (deny): every condition string of the block, those of
-// conditions folded to a constant included.
+// The interning tables a block compiles into (PolicySet::gate, deny or elem). strs (deny): every
+// condition string of the block, those of conditions folded to a constant included.
 struct CondSpace {
-  std::vector<std::string>& keys;
-  std::vector<CondRec>& conds;
-  std::unordered_map<std::string, uint32_t>& key_id;
-  std::unordered_map<std::string, uint32_t>& cond_id;
+  CondIntern& in;
   std::vector<uint32_t>* strs;
   size_t any_strs = 0;  // how many of them the `any` list gave (it is compiled first)
   // foreach entries: `element` is a variable root too, and the strings are interned under
-  // tag + text (the list and the resolver mode: PolicySet::ftags)
+  // tag + text (the list and the resolver mode: PolicySet::elem.keys)
   bool element = false;
   std::string tag;
 };
@@ -423,10 +418,10 @@ int compile_condition(CondSpace& sp, const JDoc& d, uint32_t node, uint32_t* rec
   }
   if (op == CD_UNKNOWN && !sp.strs) return 0;
   const std::string text = sp.tag + (kv ? key.s : value.s);
-  auto ck = sp.key_id.find(text);
-  if (ck == sp.key_id.end()) {
-    ck = sp.key_id.emplace(text, (uint32_t)sp.keys.size()).first;
-    sp.keys.push_back(text);
+  auto ck = sp.in.key_id.find(text);
+  if (ck == sp.in.key_id.end()) {
+    ck = sp.in.key_id.emplace(text, (uint32_t)sp.in.keys.size()).first;
+    sp.in.keys.push_back(text);
   }
   if (sp.strs) sp.strs->push_back(ck->second);
   if (op == CD_UNKNOWN) return 0;  // (deny: the string still has to resolve)
@@ -436,10 +431,10 @@ int compile_condition(CondSpace& sp, const JDoc& d, uint32_t node, uint32_t* rec
   c.cstr = ck->second;
   c.other = kv ? value : key;
   const std::string id = std::to_string(op) + (kv ? "k" : "v") + std::to_string(c.cstr) + "|" + pv_key(c.other);
-  auto it = sp.cond_id.find(id);
-  if (it == sp.cond_id.end()) {
-    it = sp.cond_id.emplace(id, (uint32_t)sp.conds.size()).first;
-    sp.conds.push_back(std::move(c));
+  auto it = sp.in.cond_id.find(id);
+  if (it == sp.in.cond_id.end()) {
+    it = sp.in.cond_id.emplace(id, (uint32_t)sp.in.conds.size()).first;
+    sp.in.conds.push_back(std::move(c));
   }
   *rec = it->second;
   return 2;
@@ -465,13 +460,9 @@ bool compile_block(CondSpace& sp, const JDoc& d, uint32_t node, CondSet* out, bo
     return false;
   }
   // checkpoint of the interning tables: a block outside the scope leaves nothing behind
-  const size_t ck0 = sp.keys.size(), cd0 = sp.conds.size();
+  const size_t ck0 = sp.in.keys.size(), cd0 = sp.in.conds.size();
   auto rollback = [&]() {
-    for (size_t i = ck0; i < sp.keys.size(); i++) sp.key_id.erase(sp.keys[i]);
-    sp.keys.resize(ck0);
-    for (auto it = sp.cond_id.begin(); it != sp.cond_id.end();)
-      it = it->second >= cd0 ? sp.cond_id.erase(it) : std::next(it);
-    sp.conds.resize(cd0);
+    sp.in.truncate(ck0, cd0);
     if (sp.strs) sp.strs->clear();
     return false;
   };
@@ -523,7 +514,7 @@ bool compile_block(CondSpace& sp, const JDoc& d, uint32_t node, CondSet* out, bo
   *always = !s.const_false && !s.any_present && s.all.empty();
   // a lane loads each condition string once: its conditions follow each other
   auto by_str = [&](uint32_t a, uint32_t b) {
-    return sp.conds[a].cstr != sp.conds[b].cstr ? sp.conds[a].cstr < sp.conds[b].cstr : a < b;
+    return sp.in.conds[a].cstr != sp.in.conds[b].cstr ? sp.in.conds[a].cstr < sp.in.conds[b].cstr : a < b;
   };
   std::sort(s.any.begin(), s.any.end(), by_str);
   std::sort(s.all.begin(), s.all.end(), by_str);
@@ -540,10 +531,40 @@ std::string set_key(const CondSet& s) {  // interning key of a folded block
   return id;
 }
 
+// The `conditions` node of a deny map {conditions: <any / all block | old list>} (kyverno.Deny), -1
+// for anything else: `deny: {}` and a missing or null `conditions` stay on the CPU route
+int64_t deny_conditions(const JDoc& d, uint32_t node) {
+  if (d.at(node).t != J_MAP) return -1;
+  const JNode& n = d.at(node);
+  int64_t cn = -1;
+  for (uint32_t c = n.first; c < n.first + n.count; c++) {
+    if (d.key(d.at(c)) != "conditions") return -1;
+    cn = c;
+  }
+  return cn >= 0 && d.at((uint32_t)cn).t != J_NULL ? cn : -1;
+}
+
+// A deny block under the strict resolver into *out; *id: its interning key. False: outside the scope.
+bool compile_deny_block(CondSpace sp, const JDoc& d, uint32_t node, DenySet* out, std::string* id) {
+  DenySet& s = *out;
+  sp.strs = &s.strs;
+  bool always = false;
+  if (!compile_block(sp, d, node, &s.fold, &always)) return false;
+  // the strings in the order of the substitution's traversal with canonical key order, as for
+  // pattern strings (kvvars.cpp): `all` before `any`, each list by index
+  for (size_t i = sp.any_strs; i < s.strs.size(); i++) s.order.push_back(s.strs[i]);
+  for (size_t i = 0; i < sp.any_strs; i++) s.order.push_back(s.strs[i]);
+  std::sort(s.strs.begin(), s.strs.end());
+  s.strs.erase(std::unique(s.strs.begin(), s.strs.end()), s.strs.end());
+  *id = set_key(s.fold) + "#";
+  for (uint32_t k : s.order) *id += std::to_string(k) + ",";
+  return true;
+}
+
 }  // namespace
 
 uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
-  CondSpace sp{ps.ckeys, ps.conds, ps.ckey_id, ps.cond_id, nullptr};
+  CondSpace sp{ps.gate, nullptr};
   CondSet s;
   bool always = false;
   if (!compile_block(sp, d, node, &s, &always)) return 0;
@@ -558,28 +579,11 @@ uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node) {
 }
 
 uint32_t compile_deny(PolicySet& ps, const JDoc& d, uint32_t node) {
-  // validate.deny: {conditions: <any / all block | old list>} (kyverno.Deny); `deny: {}` and a
-  // missing or null `conditions` stay on the CPU route
-  if (d.at(node).t != J_MAP) return 0;
-  const JNode& n = d.at(node);
-  int64_t cn = -1;
-  for (uint32_t c = n.first; c < n.first + n.count; c++) {
-    if (d.key(d.at(c)) != "conditions") return 0;
-    cn = c;
-  }
-  if (cn < 0 || d.at((uint32_t)cn).t == J_NULL) return 0;
+  const int64_t cn = deny_conditions(d, node);
+  if (cn < 0) return 0;
   DenySet s;
-  CondSpace sp{ps.dkeys, ps.dconds, ps.dkey_id, ps.dcond_id, &s.strs};
-  bool always = false;
-  if (!compile_block(sp, d, (uint32_t)cn, &s.fold, &always)) return 0;
-  // the strings in the order of the substitution's traversal with canonical key order, as for
-  // pattern strings (kvvars.cpp): `all` before `any`, each list by index
-  for (size_t i = sp.any_strs; i < s.strs.size(); i++) s.order.push_back(s.strs[i]);
-  for (size_t i = 0; i < sp.any_strs; i++) s.order.push_back(s.strs[i]);
-  std::sort(s.strs.begin(), s.strs.end());
-  s.strs.erase(std::unique(s.strs.begin(), s.strs.end()), s.strs.end());
-  std::string id = set_key(s.fold) + "#";
-  for (uint32_t k : s.order) id += std::to_string(k) + ",";
+  std::string id;
+  if (!compile_deny_block(CondSpace{ps.deny, nullptr}, d, (uint32_t)cn, &s, &id)) return 0;
   auto it = ps.dset_id.find(id);
   if (it == ps.dset_id.end()) {
     it = ps.dset_id.emplace(id, (uint32_t)ps.dsets.size()).first;
@@ -602,27 +606,19 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node) {
     else if (k == "deny") dn = c;
     else return 0;  // pattern, anyPattern, context, ...
   }
-  if (ln < 0 || dn < 0 || d.at((uint32_t)ln).t != J_STR || d.at((uint32_t)dn).t != J_MAP) return 0;
+  if (ln < 0 || dn < 0 || d.at((uint32_t)ln).t != J_STR) return 0;
   const std::string list(d.sval(d.at((uint32_t)ln)));
   if (!list_query_in_scope(list)) return 0;
   if (pn >= 0 && d.at((uint32_t)pn).t == J_NULL) pn = -1;
   // the old list form of an entry's preconditions fails common.ToMap and is dropped by the
   // reference (validation.go:260-266): left to it
   if (pn >= 0 && d.at((uint32_t)pn).t != J_MAP) return 0;
-  int64_t cn = -1;
-  for (uint32_t c = d.at((uint32_t)dn).first; c < d.at((uint32_t)dn).first + d.at((uint32_t)dn).count; c++) {
-    if (d.key(d.at(c)) != "conditions") return 0;
-    cn = c;
-  }
-  if (cn < 0 || d.at((uint32_t)cn).t == J_NULL) return 0;
+  const int64_t cn = deny_conditions(d, (uint32_t)dn);
+  if (cn < 0) return 0;
   // checkpoint: an entry outside the scope leaves nothing behind
-  const size_t l0 = ps.flists.size(), k0 = ps.ftags.size(), c0 = ps.fconds.size();
+  const size_t l0 = ps.flists.size(), k0 = ps.elem.keys.size(), c0 = ps.elem.conds.size();
   auto rollback = [&]() {
-    for (size_t i = k0; i < ps.ftags.size(); i++) ps.ftag_id.erase(ps.ftags[i]);
-    ps.ftags.resize(k0);
-    for (auto it = ps.fcond_id.begin(); it != ps.fcond_id.end();)
-      it = it->second >= c0 ? ps.fcond_id.erase(it) : std::next(it);
-    ps.fconds.resize(c0);
+    ps.elem.truncate(k0, c0);
     if (ps.flists.size() > l0) {
       ps.flist_id.erase(ps.flists.back());
       ps.flists.pop_back();
@@ -638,26 +634,21 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node) {
   }
   FeSet s;
   s.list = li->second;
-  bool always = false;
+  CondSpace sp{ps.elem, nullptr};
+  sp.element = true;
   if (pn >= 0) {
-    CondSpace sp{ps.ftags, ps.fconds, ps.ftag_id, ps.fcond_id, nullptr};
-    sp.element = true;
+    bool always = false;
     sp.tag = "p" + std::to_string(s.list) + ":";
     if (!compile_block(sp, d, (uint32_t)pn, &s.pre, &always)) return rollback();
     s.has_pre = !always;
     if (always) s.pre = CondSet();
   }
-  CondSpace sp{ps.ftags, ps.fconds, ps.ftag_id, ps.fcond_id, &s.deny.strs};
-  sp.element = true;
   sp.tag = "d" + std::to_string(s.list) + ":";
-  if (!compile_block(sp, d, (uint32_t)cn, &s.deny.fold, &always)) return rollback();
-  for (size_t i = sp.any_strs; i < s.deny.strs.size(); i++) s.deny.order.push_back(s.deny.strs[i]);
-  for (size_t i = 0; i < sp.any_strs; i++) s.deny.order.push_back(s.deny.strs[i]);
-  std::sort(s.deny.strs.begin(), s.deny.strs.end());
-  s.deny.strs.erase(std::unique(s.deny.strs.begin(), s.deny.strs.end()), s.deny.strs.end());
+  std::string did;
+  if (!compile_deny_block(sp, d, (uint32_t)cn, &s.deny, &did)) return rollback();
   // the strings this entry added: their list, resolver mode and column in the list's element rows
-  for (size_t i = ps.fkeys.size(); i < ps.ftags.size(); i++) {
-    const std::string& t = ps.ftags[i];
+  for (size_t i = ps.fkeys.size(); i < ps.elem.keys.size(); i++) {
+    const std::string& t = ps.elem.keys[i];
     FeKey k;
     k.list = s.list;
     k.precond = t[0] == 'p';
@@ -666,9 +657,7 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node) {
     ps.flist_keys[s.list].push_back((uint32_t)i);
     ps.fkeys.push_back(std::move(k));
   }
-  std::string id = std::to_string(s.list) + "|" + (s.has_pre ? set_key(s.pre) : std::string("none")) + "|" +
-                   set_key(s.deny.fold) + "#";
-  for (uint32_t k : s.deny.order) id += std::to_string(k) + ",";
+  const std::string id = std::to_string(s.list) + "|" + (s.has_pre ? set_key(s.pre) : std::string("none")) + "|" + did;
   auto it = ps.fset_id.find(id);
   if (it == ps.fset_id.end()) {
     it = ps.fset_id.emplace(id, (uint32_t)ps.fsets.size()).first;
@@ -680,113 +669,163 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node) {
 // ------------------------------------------------------------------ per batch
 namespace {
 
-// Outcome ids per [condition string][res] of the C condition strings at column k0 of the
-// outcome rows, and per condition the truth / unknown planes over the outcomes its string takes
-// in this batch. err / oos (deny): per string, the outcomes that are a substitution error /
-// outside the device scope.
-void fill_planes(const PolicySet& ps, const Batch& b, const std::vector<CondRec>& conds, size_t k0, size_t C,
-                 std::vector<uint32_t>* outc, std::vector<uint32_t>* truth, std::vector<uint32_t>* unk, uint32_t* words,
-                 std::vector<uint32_t>* err, std::vector<uint32_t>* oos, const char* who) {
-  const uint64_t n = b.res.size();
-  const size_t K = ps.vout_width();
-  // outcome ids, [condition string][res] (a lane's load is coalesced)
-  outc->resize(C * n);
-  if (b.vout.size() != K * n) throw std::runtime_error(std::string(who) + ": outcome rows do not match the policy set");
-  for (uint64_t r = 0; r < n; r++)
-    for (size_t c = 0; c < C; c++) (*outc)[c * n + r] = b.vout[r * K + k0 + c];
-  // the outcomes each condition string takes in this batch
+// One string row of a space's planes: its outcome ids are outc[at .. at + n); strict: resolved
+// under the strict resolver (its error and out-of-scope planes are filled)
+struct StrRow {
+  size_t at, n;
+  bool strict;
+};
+
+// One block to pack: its fold and (deny) every string of it, sorted; without strs the strings
+// are those of the fold's conditions
+struct BlockRef {
+  const CondSet* fold;
+  const std::vector<uint32_t>* strs;
+};
+
+// dst[c * n + i] = src[i * stride + col0 + c]: outcome rows to [string][item] (a lane's load is coalesced)
+void transpose(const uint32_t* src, size_t stride, size_t col0, size_t cols, size_t n, uint32_t* dst) {
+  for (size_t i = 0; i < n; i++)
+    for (size_t c = 0; c < cols; c++) dst[c * n + i] = src[i * stride + col0 + c];
+}
+
+// The sets and entries of `blocks` into h: per block one run of entries per string, in string
+// order: the string's `any` conditions, its `all` conditions, or a bare entry where no condition of
+// the string is left to evaluate. key_col: the string row an entry names, per string of the space.
+void pack_sets(const std::vector<CondRec>& conds, const std::vector<BlockRef>& blocks, const std::vector<uint32_t>& key_col,
+               CondHost* h) {
+  std::vector<uint32_t> own;
+  for (const BlockRef& b : blocks) {
+    const CondSet& s = *b.fold;
+    if (!b.strs) {
+      own.clear();
+      for (uint32_t c : s.any) own.push_back(conds[c].cstr);
+      for (uint32_t c : s.all) own.push_back(conds[c].cstr);
+      std::sort(own.begin(), own.end());
+      own.erase(std::unique(own.begin(), own.end()), own.end());
+    }
+    const size_t e0 = h->ents.size();
+    for (uint32_t k : b.strs ? *b.strs : own) {
+      const size_t e1 = h->ents.size();
+      for (uint32_t c : s.any)
+        if (conds[c].cstr == k) h->ents.insert(h->ents.end(), {key_col[k], c});
+      for (uint32_t c : s.all)
+        if (conds[c].cstr == k) h->ents.insert(h->ents.end(), {key_col[k], c | KV_ENT_ALL});
+      if (h->ents.size() == e1) h->ents.insert(h->ents.end(), {key_col[k], KV_ENT_NOCOND});
+    }
+    h->sets.insert(h->sets.end(), {(uint32_t)(e0 / 2), (uint32_t)((h->ents.size() - e0) / 2),
+                                   (s.any_present ? KV_SET_ANY : 0u) | (s.const_false ? KV_SET_FALSE : 0u), 0u});
+  }
+}
+
+// The planes of h over the outcome ids already in h->outc: per condition the truth / unknown
+// planes over the outcomes its string (row key_row[cstr]) takes in this batch, and per strict
+// string row the outcomes that are a substitution error / outside the device scope (no such
+// planes when no row is strict).
+void fill_planes(const Batch& b, const std::vector<CondRec>& conds, const std::vector<uint32_t>& key_row,
+                 const std::vector<StrRow>& rows, CondHost* h) {
   const size_t T = b.vout_tab.size();
   const uint32_t W = (uint32_t)std::max<size_t>((T + 31) / 32, 1);
-  *words = W;
-  std::vector<uint32_t> seen(C * W, 0);
-  for (size_t c = 0; c < C; c++)
-    for (uint64_t r = 0; r < n; r++) {
-      const uint32_t o = (*outc)[c * n + r];
-      seen[c * W + o / 32] |= 1u << (o % 32);
-    }
-  if (err) {
-    err->assign(C * W, 0);
-    oos->assign(C * W, 0);
-    for (size_t c = 0; c < C; c++)
-      for (size_t o = 0; o < T; o++) {
-        if (!((seen[c * W + o / 32] >> (o % 32)) & 1u)) continue;
-        const char t = b.vout_tab[o].empty() ? 'C' : b.vout_tab[o][0];
-        if (t == 'E') (*err)[c * W + o / 32] |= 1u << (o % 32);
-        else if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N' || t == 'M')) (*oos)[c * W + o / 32] |= 1u << (o % 32);
+  h->words = W;
+  auto set = [&](std::vector<uint32_t>& plane, size_t row, size_t o) { plane[row * W + o / 32] |= 1u << (o % 32); };
+  // the outcomes each string takes in this batch
+  std::vector<uint32_t> seen(rows.size() * W, 0);
+  bool strict = false;
+  for (size_t r = 0; r < rows.size(); r++) {
+    for (size_t i = 0; i < rows[r].n; i++) set(seen, r, h->outc[rows[r].at + i]);
+    strict |= rows[r].strict;
+  }
+  auto taken = [&](size_t row, size_t o) { return ((seen[row * W + o / 32] >> (o % 32)) & 1u) != 0u; };
+  auto tag = [&](size_t o) { return b.vout_tab[o].empty() ? 'C' : b.vout_tab[o][0]; };
+  if (strict) {
+    h->err.assign(rows.size() * W, 0);
+    h->oos.assign(rows.size() * W, 0);
+    for (size_t r = 0; r < rows.size(); r++)
+      for (size_t o = 0; o < T && rows[r].strict; o++) {
+        if (!taken(r, o)) continue;
+        const char t = tag(o);
+        if (t == 'E') set(h->err, r, o);
+        else if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N' || t == 'M')) set(h->oos, r, o);
       }
   }
-  truth->assign(conds.size() * W, 0);
-  unk->assign(conds.size() * W, 0);
+  h->truth.assign(conds.size() * W, 0);
+  h->unk.assign(conds.size() * W, 0);
   for (size_t ci = 0; ci < conds.size(); ci++) {
     const CondRec& c = conds[ci];
     for (size_t o = 0; o < T; o++) {
-      if (!((seen[c.cstr * W + o / 32] >> (o % 32)) & 1u)) continue;
-      const std::string& oc = b.vout_tab[o];
-      const char t = oc.empty() ? 'C' : oc[0];
-      if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N')) {  // a map / array, outside the scope
-        (*unk)[ci * W + o / 32] |= 1u << (o % 32);
-        continue;
+      if (!taken(key_row[c.cstr], o)) continue;
+      const char t = tag(o);
+      bool range = !(t == 'S' || t == 'F' || t == 'B' || t == 'N');  // a map / array, an error: outside the scope
+      bool r = false;
+      if (!range) {
+        const PV v = outcome_value(b.vout_tab[o]);
+        r = c.var_is_key ? cond_eval(c.op, v, c.other, &range) : cond_eval(c.op, c.other, v, &range);
       }
-      const PV v = outcome_value(oc);
-      bool range = false;
-      const bool r = c.var_is_key ? cond_eval(c.op, v, c.other, &range) : cond_eval(c.op, c.other, v, &range);
-      if (range) (*unk)[ci * W + o / 32] |= 1u << (o % 32);
-      else if (r) (*truth)[ci * W + o / 32] |= 1u << (o % 32);
+      if (range) set(h->unk, ci, o);
+      else if (r) set(h->truth, ci, o);
     }
   }
+}
+
+// The blocks of a space whose strings resolve per resource into columns [k0, k0 + keys) of the
+// outcome rows (the preconditions, the deny blocks): string row = string.
+void build_blocks(const PolicySet& ps, const Batch& b, const CondIntern& in, size_t k0, bool strict,
+                  const std::vector<BlockRef>& blocks, CondHost* h) {
+  *h = CondHost();
+  if (blocks.empty()) return;
+  const size_t n = b.res.size(), K = ps.vout_width(), C = in.keys.size();
+  if (b.vout.size() != K * n) throw std::runtime_error("condition blocks: outcome rows do not match the policy set");
+  h->outc.resize(C * n);
+  transpose(b.vout.data(), K, k0, C, n, h->outc.data());
+  std::vector<uint32_t> ident(C);
+  std::vector<StrRow> rows(C);
+  for (size_t c = 0; c < C; c++) {
+    ident[c] = (uint32_t)c;
+    rows[c] = {c * n, n, strict};
+  }
+  pack_sets(in.conds, blocks, ident, h);
+  fill_planes(b, in.conds, ident, rows, h);
+}
+
+// the error of the first string of `order` whose outcome (outcome_of(string)) is a substitution error
+template <class F>
+std::string first_error(const Batch& b, const std::vector<uint32_t>& order, F outcome_of) {
+  for (uint32_t k : order) {
+    const std::string& o = b.vout_tab[outcome_of(k)];
+    if (!o.empty() && o[0] == 'E') return o.substr(1);
+  }
+  return std::string();
 }
 
 }  // namespace
 
-void build_pre(const PolicySet& ps, const Batch& b, PreHost* out) {
-  PreHost& h = *out;
-  h = PreHost();
-  if (ps.csets.empty()) return;
-  const size_t k0 = ps.vkeys.size(), C = ps.ckeys.size();
-  for (const CondSet& s : ps.csets) {
-    h.sets.push_back((uint32_t)(h.ents.size() / 2));
-    h.sets.push_back((uint32_t)s.any.size() | (s.any_present ? 0x80000000u : 0u));
-    h.sets.push_back((uint32_t)s.all.size());
-    h.sets.push_back(s.const_false ? 1u : 0u);
-    for (uint32_t c : s.any) { h.ents.push_back(ps.conds[c].cstr); h.ents.push_back(c); }
-    for (uint32_t c : s.all) { h.ents.push_back(ps.conds[c].cstr); h.ents.push_back(c); }
-  }
-  fill_planes(ps, b, ps.conds, k0, C, &h.outc, &h.truth, &h.unk, &h.words, nullptr, nullptr, "build_pre");
+CondBlocks CondHost::view() const {
+  return CondBlocks{sets.data(), ents.data(), outc.data(), truth.data(), unk.data(), err.data(), oos.data(), words};
 }
 
-void build_deny(const PolicySet& ps, const Batch& b, DenyHost* out) {
-  DenyHost& h = *out;
-  h = DenyHost();
-  if (ps.dsets.empty()) return;
-  for (const DenySet& s : ps.dsets) {
-    h.sets.push_back((uint32_t)(h.ents.size() / 2));
-    const size_t e0 = h.ents.size();
-    // one run of entries per string of the block, in string order: its `any` conditions, its
-    // `all` conditions, or a bare entry where no condition of the string is left to evaluate
-    for (uint32_t k : s.strs) {
-      const size_t e1 = h.ents.size();
-      for (uint32_t c : s.fold.any)
-        if (ps.dconds[c].cstr == k) { h.ents.push_back(k); h.ents.push_back(c); }
-      for (uint32_t c : s.fold.all)
-        if (ps.dconds[c].cstr == k) { h.ents.push_back(k); h.ents.push_back(c | KV_DENY_ALL); }
-      if (h.ents.size() == e1) { h.ents.push_back(k); h.ents.push_back(KV_DENY_NOCOND); }
-    }
-    h.sets.push_back((uint32_t)((h.ents.size() - e0) / 2));
-    h.sets.push_back(s.fold.any_present ? 1u : 0u);
-    h.sets.push_back(s.fold.const_false ? 1u : 0u);
-  }
-  fill_planes(ps, b, ps.dconds, ps.vkeys.size() + ps.ckeys.size(), ps.dkeys.size(), &h.outc, &h.truth, &h.unk, &h.words,
-              &h.err, &h.oos, "build_deny");
+void build_pre(const PolicySet& ps, const Batch& b, CondHost* out) {
+  std::vector<BlockRef> blocks;
+  for (const CondSet& s : ps.csets) blocks.push_back({&s, nullptr});
+  build_blocks(ps, b, ps.gate, ps.vkeys.size(), false, blocks, out);
 }
 
-uint8_t pre_status_host(const PreHost& h, uint32_t set, uint64_t n_res, uint64_t r) {
-  return (uint8_t)kv_pre_lane(h.sets.data(), h.ents.data(), h.outc.data(), h.truth.data(), h.unk.data(), h.words, set,
-                              n_res, r);
+void build_deny(const PolicySet& ps, const Batch& b, CondHost* out) {
+  std::vector<BlockRef> blocks;
+  for (const DenySet& s : ps.dsets) blocks.push_back({&s.fold, &s.strs});
+  build_blocks(ps, b, ps.deny, ps.vkeys.size() + ps.gate.keys.size(), true, blocks, out);
 }
 
-uint8_t deny_status_host(const DenyHost& h, uint32_t set, uint64_t n_res, uint64_t r) {
-  return (uint8_t)kv_deny_lane(h.sets.data(), h.ents.data(), h.outc.data(), h.truth.data(), h.unk.data(), h.err.data(),
-                               h.oos.data(), h.words, set, n_res, r);
+uint8_t pre_status_host(const CondHost& h, uint32_t set, uint64_t n_res, uint64_t r) {
+  return (uint8_t)kv_gate_status(kv_cond_fold<false>(h.view(), set, n_res, r));
+}
+
+uint8_t deny_status_host(const CondHost& h, uint32_t set, uint64_t n_res, uint64_t r) {
+  return (uint8_t)kv_deny_status(kv_cond_fold<true>(h.view(), set, n_res, r));
+}
+
+std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, uint64_t r) {
+  const size_t K = ps.vout_width(), k0 = ps.vkeys.size() + ps.gate.keys.size();
+  return first_error(b, ps.dsets[set].order, [&](uint32_t k) { return b.vout[r * K + k0 + k]; });
 }
 
 // ------------------------------------------------------------------ foreach
@@ -798,11 +837,12 @@ void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out) {
   const size_t L = ps.flists.size();
   if (b.fstate.size() != L * n || b.fcount.size() != L * n || b.fout.size() != L)
     throw std::runtime_error("build_foreach: element rows do not match the policy set");
-  // per list: the element blocks, [string][element] outcome ids, the per-resource state
+  // per list: the element blocks, [string][element] outcome ids, the per-resource state; a string
+  // row per (list, string of the list)
   h.lstate.resize(L * n);
   h.first.resize(L * n);
-  std::vector<uint32_t> plane0(L, 0);
-  uint32_t rows = 0;
+  std::vector<StrRow> rows;
+  std::vector<uint32_t> key_col(ps.fkeys.size()), key_row(ps.fkeys.size());
   for (size_t l = 0; l < L; l++) {
     const size_t K = ps.flist_keys[l].size();
     const uint32_t el0 = (uint32_t)h.el_res.size();
@@ -816,93 +856,41 @@ void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out) {
     }
     const uint32_t n_el = (uint32_t)h.el_res.size() - el0;
     if (b.fout[l].size() != (size_t)n_el * K) throw std::runtime_error("build_foreach: element rows misaligned");
-    const uint32_t o0 = (uint32_t)h.outc.size();
-    h.outc.resize(o0 + (size_t)n_el * K);
-    for (uint32_t e = 0; e < n_el; e++)
-      for (size_t c = 0; c < K; c++) h.outc[o0 + c * n_el + e] = b.fout[l][(size_t)e * K + c];
-    plane0[l] = rows;
-    h.lists.insert(h.lists.end(), {o0, n_el, rows, el0});
-    rows += (uint32_t)K;
+    const uint32_t o0 = (uint32_t)h.deny.outc.size();
+    h.deny.outc.resize(o0 + (size_t)n_el * K);
+    transpose(b.fout[l].data(), K, 0, K, n_el, h.deny.outc.data() + o0);
+    h.lists.insert(h.lists.end(), {o0, n_el, (uint32_t)rows.size(), el0});
+    for (size_t c = 0; c < K; c++) {
+      const uint32_t k = ps.flist_keys[l][c];
+      key_col[k] = (uint32_t)c;
+      key_row[k] = (uint32_t)rows.size();
+      // (the gate's strings have no error: unresolved is "")
+      rows.push_back({o0 + c * n_el, n_el, !ps.fkeys[k].precond});
+    }
     h.max_el = std::max(h.max_el, n_el);
   }
-  // the outcomes each string takes in this batch, then the planes over them
-  const size_t T = b.vout_tab.size();
-  const uint32_t W = (uint32_t)std::max<size_t>((T + 31) / 32, 1);
-  h.words = W;
-  std::vector<uint32_t> seen((size_t)rows * W, 0);
-  auto row_of = [&](uint32_t key) { return plane0[ps.fkeys[key].list] + ps.fkeys[key].col; };
-  for (size_t l = 0; l < L; l++) {
-    const uint32_t o0 = h.lists[4 * l], n_el = h.lists[4 * l + 1];
-    for (size_t c = 0; c < ps.flist_keys[l].size(); c++)
-      for (uint32_t e = 0; e < n_el; e++) {
-        const uint32_t o = h.outc[o0 + c * n_el + e];
-        seen[(size_t)(plane0[l] + c) * W + o / 32] |= 1u << (o % 32);
-      }
-  }
-  h.err.assign((size_t)rows * W, 0);
-  h.oos.assign((size_t)rows * W, 0);
-  for (size_t k = 0; k < ps.fkeys.size(); k++) {
-    if (ps.fkeys[k].precond) continue;  // (the gate's strings have no error: unresolved is "")
-    const size_t row = row_of((uint32_t)k);
-    for (size_t o = 0; o < T; o++) {
-      if (!((seen[row * W + o / 32] >> (o % 32)) & 1u)) continue;
-      const char t = b.vout_tab[o].empty() ? 'C' : b.vout_tab[o][0];
-      if (t == 'E') h.err[row * W + o / 32] |= 1u << (o % 32);
-      else if (!(t == 'S' || t == 'F' || t == 'B' || t == 'N' || t == 'M')) h.oos[row * W + o / 32] |= 1u << (o % 32);
-    }
-  }
-  h.truth.assign(ps.fconds.size() * W, 0);
-  h.unk.assign(ps.fconds.size() * W, 0);
-  for (size_t ci = 0; ci < ps.fconds.size(); ci++) {
-    const CondRec& c = ps.fconds[ci];
-    const size_t row = row_of(c.cstr);
-    for (size_t o = 0; o < T; o++) {
-      if (!((seen[row * W + o / 32] >> (o % 32)) & 1u)) continue;
-      const std::string& oc = b.vout_tab[o];
-      const char t = oc.empty() ? 'C' : oc[0];
-      bool range = !(t == 'S' || t == 'F' || t == 'B' || t == 'N');  // a map / array, an error: outside the scope
-      bool r = false;
-      if (!range) {
-        const PV v = outcome_value(oc);
-        r = c.var_is_key ? cond_eval(c.op, v, c.other, &range) : cond_eval(c.op, c.other, v, &range);
-      }
-      if (range) h.unk[ci * W + o / 32] |= 1u << (o % 32);
-      else if (r) h.truth[ci * W + o / 32] |= 1u << (o % 32);
-    }
-  }
-  // the sets: row s of psets / dsets is foreach set s; entries carry the string's column
-  auto col = [&](uint32_t c) { return ps.fkeys[ps.fconds[c].cstr].col; };
+  fill_planes(b, ps.elem.conds, key_row, rows, &h.deny);
+  h.deny.err.resize(rows.size() * h.deny.words);  // (a row per string even where none is strict:
+  h.deny.oos.resize(rows.size() * h.deny.words);  // kv_foreach_elem offsets the planes by list)
+  // the sets: row s of gate / deny is foreach set s; entries carry the string's column
+  std::vector<BlockRef> gate, deny;
   for (const FeSet& s : ps.fsets) {
     h.sets.insert(h.sets.end(), {s.list, s.has_pre ? 1u : 0u, 0u, 0u});
-    h.psets.push_back((uint32_t)(h.pents.size() / 2));
-    h.psets.push_back((uint32_t)s.pre.any.size() | (s.pre.any_present ? 0x80000000u : 0u));
-    h.psets.push_back((uint32_t)s.pre.all.size());
-    h.psets.push_back(s.pre.const_false ? 1u : 0u);
-    for (uint32_t c : s.pre.any) { h.pents.push_back(col(c)); h.pents.push_back(c); }
-    for (uint32_t c : s.pre.all) { h.pents.push_back(col(c)); h.pents.push_back(c); }
-    h.dsets.push_back((uint32_t)(h.dents.size() / 2));
-    const size_t e0 = h.dents.size();
-    for (uint32_t k : s.deny.strs) {
-      const size_t e1 = h.dents.size();
-      for (uint32_t c : s.deny.fold.any)
-        if (ps.fconds[c].cstr == k) { h.dents.push_back(ps.fkeys[k].col); h.dents.push_back(c); }
-      for (uint32_t c : s.deny.fold.all)
-        if (ps.fconds[c].cstr == k) { h.dents.push_back(ps.fkeys[k].col); h.dents.push_back(c | KV_DENY_ALL); }
-      if (h.dents.size() == e1) { h.dents.push_back(ps.fkeys[k].col); h.dents.push_back(KV_DENY_NOCOND); }
-    }
-    h.dsets.push_back((uint32_t)((h.dents.size() - e0) / 2));
-    h.dsets.push_back(s.deny.fold.any_present ? 1u : 0u);
-    h.dsets.push_back(s.deny.fold.const_false ? 1u : 0u);
+    gate.push_back({&s.pre, nullptr});
+    deny.push_back({&s.deny.fold, &s.deny.strs});
   }
+  pack_sets(ps.elem.conds, gate, key_col, &h.gate);
+  pack_sets(ps.elem.conds, deny, key_col, &h.deny);
 }
 
 FeTables FeHost::view() const {
   FeTables t{};
-  t.sets = sets.data(); t.lists = lists.data(); t.psets = psets.data(); t.pents = pents.data();
-  t.dsets = dsets.data(); t.dents = dents.data(); t.outc = outc.data(); t.truth = truth.data();
-  t.unk = unk.data(); t.err = err.data(); t.oos = oos.data(); t.el_res = el_res.data();
-  t.el_ord = el_ord.data(); t.lstate = lstate.data();
-  t.words = words;
+  t.sets = sets.data(); t.lists = lists.data(); t.el_res = el_res.data(); t.el_ord = el_ord.data();
+  t.lstate = lstate.data();
+  t.deny = deny.view();
+  t.gate = t.deny;
+  t.gate.sets = gate.sets.data();
+  t.gate.ents = gate.ents.data();
   t.n_sets = (uint32_t)(sets.size() / 4);
   t.n_lists = (uint32_t)(lists.size() / 4);
   t.max_el = max_el;
@@ -927,20 +915,7 @@ std::string foreach_error_host(const PolicySet& ps, const Batch& b, const FeHost
   const FeSet& s = ps.fsets[set];
   const size_t K = ps.flist_keys[s.list].size();
   const size_t e = (size_t)h.first[(size_t)s.list * b.res.size() + r] + elem;
-  for (uint32_t k : s.deny.order) {
-    const std::string& o = b.vout_tab[b.fout[s.list][e * K + ps.fkeys[k].col]];
-    if (!o.empty() && o[0] == 'E') return o.substr(1);
-  }
-  return std::string();
-}
-
-std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, uint64_t r) {
-  const size_t K = ps.vout_width(), k0 = ps.vkeys.size() + ps.ckeys.size();
-  for (uint32_t k : ps.dsets[set].order) {
-    const std::string& o = b.vout_tab[b.vout[r * K + k0 + k]];
-    if (!o.empty() && o[0] == 'E') return o.substr(1);
-  }
-  return std::string();
+  return first_error(b, s.deny.order, [&](uint32_t k) { return b.fout[s.list][e * K + ps.fkeys[k].col]; });
 }
 
 }  // namespace kvh

@@ -13,8 +13,11 @@
 //    table (Batch::vout columns after the pattern variables', kvvars.cpp resolver mode);
 //  * per batch (build_pre): every condition is evaluated once per *distinct* outcome its string
 //    takes, into two bit planes indexed by outcome id (truth, unknown);
-//  * device (kvpre.h kv_pre_lane, kv_precond_kernel): one lane per resource folds its set's
+//  * device (kvblocks.h kv_cond_fold, kv_precond_kernel): one lane per resource folds its set's
 //    conditions with three-valued logic into DevBatch::pre_st[set][res].
+// validate.deny and the two blocks of a validate.foreach entry (below) are the same machinery with
+// another resolver and another verdict: one table form (CondHost, kvblocks.h CondBlocks), one
+// entry packer, one plane filler and one fold serve all three.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -23,7 +26,8 @@
 #include "kvinternal.hpp"
 
 namespace kv {
-struct FeTables;  // kvforeach.h
+struct CondBlocks;  // kvblocks.h
+struct FeTables;    // kvforeach.h
 }
 
 namespace kvh {
@@ -49,17 +53,21 @@ bool cond_eval(uint32_t op, const PV& key, const PV& value, bool* range);
 // 0xFFFFFFFF when the block always passes (no gate).
 uint32_t compile_preconditions(PolicySet& ps, const JDoc& d, uint32_t node);
 
-// Per-batch tables of the gate (device layout, DevBatch::pre_*).
-struct PreHost {
-  std::vector<uint32_t> sets;   // 4 words per set: first entry, n_any | any_present << 31, n_all, const_false
-  std::vector<uint32_t> ents;   // 2 words per entry: condition string, condition (plane row); any then all
-  std::vector<uint32_t> outc;   // outcome id per [condition string][res]
+// Per-batch tables of the condition blocks of one space (the device layout: kvblocks.h CondBlocks).
+struct CondHost {
+  std::vector<uint32_t> sets;   // 4 words per set: first entry, entries, KV_SET_* flags, 0
+  std::vector<uint32_t> ents;   // 2 words per entry: string row, condition | KV_ENT_ALL, or KV_ENT_NOCOND; by string
+  std::vector<uint32_t> outc;   // outcome id per [string row][item]
   std::vector<uint32_t> truth, unk;  // [condition][words] bit planes over outcome ids
+  std::vector<uint32_t> err, oos;    // [string row][words]: the outcome is an error / outside the device scope
+                                     // (rows of strings under the preconditions resolver stay empty; no such
+                                     // planes at all for the gate)
   uint32_t words = 1;
+  kv::CondBlocks view() const;
 };
-void build_pre(const PolicySet& ps, const Batch& b, PreHost* out);
-// the gate of one (set, resource) on the host: 0 pass, ST_SKIP, ST_CPU (as kv_pre_lane)
-uint8_t pre_status_host(const PreHost& h, uint32_t set, uint64_t n_res, uint64_t r);
+void build_pre(const PolicySet& ps, const Batch& b, CondHost* out);
+// the gate of one (set, resource) on the host: 0 pass, ST_SKIP, ST_CPU (as kv_precond_kernel)
+uint8_t pre_status_host(const CondHost& h, uint32_t set, uint64_t n_res, uint64_t r);
 
 // validate.deny on the device (KV_COMPILE_DENY; pkg/engine/validation.go:299-339 validateDeny).
 // The reference substitutes the deny conditions per (rule, resource) with the default resolver
@@ -68,30 +76,23 @@ uint8_t pre_status_host(const PreHost& h, uint32_t set, uint64_t n_res, uint64_t
 // (utils.go:392-406) and evaluates the same any / all fold: true is FAIL, false is PASS. Here the
 // preconditions' machinery runs with another resolver and another verdict, and no pattern walk:
 //  * compile (compile_deny): blocks, conditions and strings are interned in tables of their own
-//    (PolicySet::dsets / dconds / dkeys). A block whose conditions fold to a constant is still a
+//    (PolicySet::dsets / deny). A block whose conditions fold to a constant is still a
 //    deny set, so preconditions compose with it. The strings are keyed by their text alone: the
 //    string's path inside the conditions document shows only in the reference's non-NotFound
 //    errors, all of which are outside the device scope here (outcome "C");
 //  * ingest: deny strings resolve with the strict resolver into further columns of Batch::vout;
 //  * per batch (build_deny): truth / unknown planes per condition as for the preconditions, and
 //    per string an error plane (the outcome is a substitution error) and an out-of-scope plane;
-//  * device (kvdeny.h kv_deny_lane, kv_deny_kernel): DevBatch::deny_st[set][res], the final
-//    status of the pair once match / exclude and the preconditions let it through.
+//  * device (kvblocks.h kv_cond_fold<strict> + kv_deny_status, kv_deny_kernel):
+//    DevBatch::deny_st[set][res], the final status of the pair once match / exclude and the
+//    preconditions let it through.
 // Parses the `deny` node of a rule: 0 when it is outside the device scope (the rule stays
 // CPU-routed, reason "deny"), else 1 + the interned deny set's index.
 uint32_t compile_deny(PolicySet& ps, const JDoc& d, uint32_t node);
 
-struct DenyHost {
-  std::vector<uint32_t> sets;   // 4 words per set: first entry, entries, any_present, const_false
-  std::vector<uint32_t> ents;   // 2 words per entry: string, condition | KV_DENY_ALL, or KV_DENY_NOCOND; by string
-  std::vector<uint32_t> outc;   // outcome id per [deny string][res]
-  std::vector<uint32_t> truth, unk;  // [condition][words] bit planes over outcome ids
-  std::vector<uint32_t> err, oos;    // [string][words]: the outcome is an error / outside the device scope
-  uint32_t words = 1;
-};
-void build_deny(const PolicySet& ps, const Batch& b, DenyHost* out);
-// one (deny set, resource) on the host: ST_PASS, ST_FAIL, ST_ERROR or ST_CPU (as kv_deny_lane)
-uint8_t deny_status_host(const DenyHost& h, uint32_t set, uint64_t n_res, uint64_t r);
+void build_deny(const PolicySet& ps, const Batch& b, CondHost* out);
+// one (deny set, resource) on the host: ST_PASS, ST_FAIL, ST_ERROR or ST_CPU (as kv_deny_kernel)
+uint8_t deny_status_host(const CondHost& h, uint32_t set, uint64_t n_res, uint64_t r);
 // the error of the first unresolved string of the set on store resource r, in the order of the
 // reference's traversal with canonical key order ("" when every string resolves)
 std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, uint64_t r);
@@ -107,11 +108,12 @@ std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, u
 // variables `{{element<chain>}}` / `{{request.object<chain>}}`. DESIGN.md §3 *Foreach*.
 //  * compile (compile_foreach): lists, element-scoped strings (per list and resolver mode; a
 //    string with request.object variables only is an element-scoped string too: one key space,
-//    one resolver call site), conditions and foreach sets are interned in PolicySet::f*;
+//    one resolver call site), conditions and foreach sets are interned in PolicySet::f* / elem;
 //  * ingest: per (resource, list) the list state and element count, per (element, string) an
 //    outcome id of the batch's outcome table, element-major (Batch::fstate / fcount / fout);
-//  * per batch (build_foreach): the planes of build_deny / build_pre over the element strings,
-//    the outcome ids transposed to [string][element], el_res / el_ord per element;
+//  * per batch (build_foreach): the entries and planes of build_deny / build_pre over the element
+//    strings (a string row per (list, string)), the outcome ids transposed to [string][element],
+//    el_res / el_ord per element;
 //  * device (kvforeach.h, kv_foreach_elem_kernel, kv_foreach_fin_kernel): a lane per element, a
 //    segmented first-decisive-element reduction into 32-bit keys, a byte per (set, resource) in
 //    the rows of DevBatch::deny_st after the deny sets'.
@@ -120,10 +122,12 @@ std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, u
 uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node);
 
 struct FeHost {
-  std::vector<uint32_t> sets, lists, psets, pents, dsets, dents;  // kvforeach.h FeTables
-  std::vector<uint32_t> outc, truth, unk, err, oos, el_res, el_ord, lstate;
+  // row s of gate / deny: the entry preconditions / the deny block of foreach set s. deny holds the
+  // outcome ids and every plane; gate only sets and entries (its view reads deny's outc, truth, unk)
+  CondHost gate, deny;
+  std::vector<uint32_t> sets, lists, el_res, el_ord, lstate;  // kvforeach.h FeTables
   std::vector<uint32_t> first;  // [list][res]: the resource's first element in the list's block (host only)
-  uint32_t words = 1, max_el = 0;
+  uint32_t max_el = 0;
   kv::FeTables view() const;
 };
 void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out);

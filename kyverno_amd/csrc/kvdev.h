@@ -15,13 +15,12 @@ namespace kv {
 hipError_t launch_validate(const DevPS* P, const DevBatch* B, uint32_t n_res, const DevOut& O, uint32_t rule_begin,
                            uint32_t rule_end, hipStream_t stream);
 
-// The precondition gate of a batch (kvpre.h): pre_st[set][res] for every condition set of B
-// (DevBatch::pre_*), once per (policy set, batch) with the batch's other device preparation.
-hipError_t launch_precond(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* pre_st, hipStream_t stream);
-
-// The deny fold of a batch (kvdeny.h): deny_st[set][res] for every deny set of B (DevBatch::deny_*),
-// with the precondition gate.
-hipError_t launch_deny(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* deny_st, hipStream_t stream);
+// The condition blocks of a batch (kvblocks.h; T holds device pointers): st[set][res] for every set
+// of T, once per (policy set, batch) with the batch's other device preparation. strict = false: the
+// precondition gate (kv_precond_kernel, DevBatch::pre_st); true: the deny fold (kv_deny_kernel,
+// the first rows of DevBatch::deny_st).
+struct CondBlocks;
+hipError_t launch_cond(bool strict, const CondBlocks& T, uint32_t n_res, uint32_t n_sets, uint8_t* st, hipStream_t stream);
 
 // The foreach fold of a batch (kvforeach.h): clears fe_acc[set][res] (32-bit keys), reduces every
 // set's elements into it and writes fe_st[set][res], with the deny fold. T holds device pointers.

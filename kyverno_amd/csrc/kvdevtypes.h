@@ -135,32 +135,14 @@ struct DevBatch {
   // words, every row of a family laid out by cell format (below), so a lookup loads only the
   // words its consumers read (4 bytes for a narrow cell, 12 or 16 for a wide one)
   const uint32_t* pcol;
-  // preconditions (kvcond.h PreHost, kvpre.h): the policy set's condition sets (4 words each) and
-  // their entries (condition string, condition), the outcome id per [condition string][res], the
-  // truth / unknown bit planes per [condition][pre_words] over outcome ids, and the gate
-  // kv_precond_kernel writes once per batch: pre_st[set * n_res + res] = 0 (evaluate the
+  // condition blocks (kvcond.h, kvblocks.h; their tables go to the kernels below by value):
+  // the gate kv_precond_kernel writes once per batch, pre_st[set * n_res + res] = 0 (evaluate the
   // pattern), ST_SKIP ("preconditions not met") or ST_CPU (undecided on the device)
-  const uint32_t* pre_sets;
-  const uint32_t* pre_ents;
-  const uint32_t* pre_outc;
-  const uint32_t* pre_truth;
-  const uint32_t* pre_unk;
-  uint32_t pre_words, n_pre_sets;
   const uint8_t* pre_st;
-  // validate.deny on the device (kvcond.h DenyHost, kvdeny.h): the deny sets (4 words each),
-  // their entries ordered by string (string, condition | flags), the outcome id per
-  // [deny string][res], the truth / unknown planes per [condition][deny_words], the error and
-  // out-of-scope planes per [string][deny_words], and the plane kv_deny_kernel writes once per
-  // batch: deny_st[set * n_res + res] = ST_PASS, ST_FAIL, ST_ERROR or ST_CPU, the final status
-  // of a deny rule's pair that match / exclude and the preconditions let through
-  const uint32_t* deny_sets;
-  const uint32_t* deny_ents;
-  const uint32_t* deny_outc;
-  const uint32_t* deny_truth;
-  const uint32_t* deny_unk;
-  const uint32_t* deny_err;
-  const uint32_t* deny_oos;
-  uint32_t deny_words, n_deny_sets;
+  // validate.deny / validate.foreach on the device: the plane kv_deny_kernel (rows of the deny sets)
+  // and kv_foreach_fin_kernel (rows of the foreach sets, after them) write once per batch,
+  // deny_st[set * n_res + res] = ST_PASS, ST_FAIL, ST_ERROR, ST_CPU or (foreach) ST_SKIP, the final
+  // status of the rule's pair that match / exclude and the preconditions let through
   const uint8_t* deny_st;
 };
 

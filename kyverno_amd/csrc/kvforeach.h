@@ -1,7 +1,7 @@
-// validate.foreach on the device (kvcond.h): the per-element verdict and the reduction keys,
-// shared by kv_foreach_elem_kernel / kv_foreach_fin_kernel (kvkernel.hip) and the host fold
-// (kvcond.cpp foreach_fold_host). Plain code over the tables of kvcond.h FeHost; needs
-// kv_layout.h, kvpre.h and kvdeny.h.
+// validate.foreach on the device (kvcond.h): the list states, the per-element verdict and the
+// reduction keys, shared by kv_foreach_elem_kernel / kv_foreach_fin_kernel (kvkernel.hip) and the
+// host fold (kvcond.cpp foreach_fold_host). Plain code over the tables of kvcond.h FeHost; needs
+// kv_layout.h and kvblocks.h.
 #pragma once
 
 namespace kv {
@@ -18,39 +18,39 @@ constexpr uint32_t FE_MAX_ELEMS = 0x10000u;
 constexpr uint32_t FE_KEY_PASS = 0x80000000u;
 constexpr uint32_t FE_KEY_NONE = 0xFFFFFFFFu;
 
-// The device view of FeHost (32-bit words throughout).
+// The device view of FeHost (32-bit words throughout). Row s of gate / deny is foreach set s; the
+// two share outc and the truth / unknown planes, and their string rows are columns of the set's list.
 struct FeTables {
   const uint32_t* sets;    // 4 words per foreach set: list, has_pre, 0, 0
   const uint32_t* lists;   // 4 words per list: first word of its outc block, elements, first plane row, first element
-  const uint32_t* psets;   // the entry preconditions of every set, as PreHost::sets / ents (row = set)
-  const uint32_t* pents;
-  const uint32_t* dsets;   // the deny block of every set, as DenyHost::sets / ents (row = set)
-  const uint32_t* dents;
-  const uint32_t* outc;    // per list a block [string of the list][element of the list]
-  const uint32_t* truth;   // [condition][words]
-  const uint32_t* unk;
-  const uint32_t* err;     // [plane row of the list + string][words]
-  const uint32_t* oos;
+  CondBlocks gate;         // the entry preconditions of every set (preconditions resolver: no err / oos)
+  CondBlocks deny;         // the deny block of every set; outc: per list a block [string of the list][element
+                           // of the list]; err / oos: [plane row of the list + string][words]
   const uint32_t* el_res;  // per list block: the element's store resource
   const uint32_t* el_ord;  // per list block: the element's index in its list
   const uint32_t* lstate;  // [list][res]: FE_LIST_*
-  uint32_t words, n_sets, n_lists, max_el;
+  uint32_t n_sets, n_lists, max_el;
 };
 
 // One element of foreach set `set`: element e of the set's list (e < its element count).
 // validate() on the element's context (validation.go:156-202): the entry's preconditions under
 // the preconditions resolver (not met: ST_SKIP, undecided: ST_CPU), then the deny block under the
-// strict one (kv_deny_lane: ST_CPU, ST_ERROR, ST_FAIL or ST_PASS).
+// strict one (kv_deny_status: ST_CPU, ST_ERROR, ST_FAIL or ST_PASS).
 KV_HD inline uint32_t kv_foreach_elem(const FeTables& T, uint32_t set, uint32_t e) {
   const uint32_t* L = T.lists + 4u * T.sets[4u * set];
   const uint32_t n_el = L[1];
-  const uint32_t* outc = T.outc + L[0];
   if (T.sets[4u * set + 1u]) {
-    const uint32_t g = kv_pre_lane(T.psets, T.pents, outc, T.truth, T.unk, T.words, set, n_el, e);
+    CondBlocks G = T.gate;
+    G.outc += L[0];
+    const uint32_t g = kv_gate_status(kv_cond_fold<false>(G, set, n_el, e));
     if (g) return g;
   }
-  const uint64_t row = (uint64_t)L[2] * T.words;
-  return kv_deny_lane(T.dsets, T.dents, outc, T.truth, T.unk, T.err + row, T.oos + row, T.words, set, n_el, e);
+  const uint64_t row = (uint64_t)L[2] * T.deny.words;
+  CondBlocks D = T.deny;
+  D.outc += L[0];
+  D.err += row;
+  D.oos += row;
+  return kv_deny_status(kv_cond_fold<true>(D, set, n_el, e));
 }
 
 KV_HD inline bool kv_fe_decisive(uint32_t code) { return code == ST_FAIL || code == ST_ERROR || code == ST_CPU; }

@@ -718,11 +718,11 @@ struct Ingest {
     // pattern variables: every distinct (string, path) resolved on this resource (kvvars.cpp)
     // (then every distinct precondition string, under the preconditions resolver)
     // (then every distinct deny string, under the default resolver: unresolved is an error)
-    const size_t nvk = ps.vkeys.size(), nck = ps.ckeys.size(), ndk = ps.dkeys.size();
+    const size_t nvk = ps.vkeys.size(), nck = ps.gate.keys.size(), ndk = ps.deny.keys.size();
     for (size_t k = 0; k < nvk + nck + ndk; k++) {
       std::string o = k < nvk         ? resolve_var_string(ps.vkeys[k].first, ps.vkeys[k].second, d)
-                      : k < nvk + nck ? resolve_var_string(ps.ckeys[k - nvk], "", d, true)
-                                      : resolve_var_string(ps.dkeys[k - nvk - nck], "", d, false);
+                      : k < nvk + nck ? resolve_var_string(ps.gate.keys[k - nvk], "", d, true)
+                                      : resolve_var_string(ps.deny.keys[k - nvk - nck], "", d, false);
       auto it = b.vout_id.find(o);
       if (it == b.vout_id.end()) {
         it = b.vout_id.emplace(o, (uint32_t)b.vout_tab.size()).first;

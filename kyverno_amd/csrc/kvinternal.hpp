@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdlib>
+#include <iterator>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -64,8 +65,21 @@ struct VarStr {
 struct CondRec {
   uint32_t op = 0;         // CondOp
   bool var_is_key = true;  // the variable string is `key` (else `value`)
-  uint32_t cstr = 0;       // PolicySet::ckeys index
+  uint32_t cstr = 0;       // index of its string in the key space (CondIntern::keys)
   PV other;                // the constant operand
+};
+// One key space of condition strings and the conditions interned over it (PolicySet::gate, deny, elem)
+struct CondIntern {
+  std::vector<std::string> keys;
+  std::vector<CondRec> conds;
+  std::unordered_map<std::string, uint32_t> key_id, cond_id;
+  // drops the strings from k0 and the conditions from c0 on (a block outside the scope leaves nothing behind)
+  void truncate(size_t k0, size_t c0) {
+    for (size_t i = k0; i < keys.size(); i++) key_id.erase(keys[i]);
+    keys.resize(k0);
+    for (auto it = cond_id.begin(); it != cond_id.end();) it = it->second >= c0 ? cond_id.erase(it) : std::next(it);
+    conds.resize(c0);
+  }
 };
 // One interned condition set, constants folded: the conditions left of `any` (any_present: the
 // list exists and no constant member is true) and of `all`; const_false: a constant decides SKIP.
@@ -73,9 +87,9 @@ struct CondSet {
   bool any_present = false, const_false = false;
   std::vector<uint32_t> any, all;  // CondRec indices, ordered by condition string
 };
-// One interned deny block: its fold (CondRec indices into PolicySet::dconds; no conditions left
+// One interned deny block: its fold (CondRec indices into PolicySet::deny.conds; no conditions left
 // and not const_false: the block always holds) and every condition string of the block
-// (PolicySet::dkeys indices, sorted), those of folded-away conditions included: an unresolved
+// (PolicySet::deny.keys indices, sorted), those of folded-away conditions included: an unresolved
 // variable anywhere in the block is an error before anything is evaluated (vars.go:315-317).
 struct DenySet {
   CondSet fold;
@@ -92,7 +106,7 @@ struct FeKey {
   std::string text;
 };
 // One interned foreach set: the list, the entry's preconditions (has_pre: a gate is left after
-// constant folding) and its deny block; CondRec indices into PolicySet::fconds, string indices
+// constant folding) and its deny block; CondRec indices into PolicySet::elem.conds, string indices
 // into PolicySet::fkeys.
 struct FeSet {
   uint32_t list = 0;
@@ -221,33 +235,31 @@ struct PolicySet {
   std::vector<uint32_t> dleaf_vstr;
   std::vector<std::pair<uint32_t, uint32_t>> dyn_rules;
   // preconditions (kvcond.cpp): the distinct condition strings holding variables (a key space of
-  // their own: the preconditions resolver substitutes "" where the pattern resolver fails), the
-  // interned conditions and condition sets (RuleRec::pre - 1)
-  std::vector<std::string> ckeys;
-  std::vector<CondRec> conds;
+  // their own: the preconditions resolver substitutes "" where the pattern resolver fails) with
+  // the conditions interned over them, and the interned condition sets (RuleRec::pre - 1)
+  CondIntern gate;
   std::vector<CondSet> csets;
-  std::unordered_map<std::string, uint32_t> ckey_id, cond_id, cset_id;
-  // validate.deny on the device (KV_COMPILE_DENY, kvcond.cpp compile_deny): the same three
-  // tables for the deny blocks (RuleRec::deny - 1), in a key space of their own: deny strings
-  // resolve under the strict resolver (an unresolved variable is an error, not "")
-  std::vector<std::string> dkeys;
-  std::vector<CondRec> dconds;
+  std::unordered_map<std::string, uint32_t> cset_id;
+  // validate.deny on the device (KV_COMPILE_DENY, kvcond.cpp compile_deny): the same for the deny
+  // blocks (RuleRec::deny - 1), in a key space of their own: deny strings resolve under the
+  // strict resolver (an unresolved variable is an error, not "")
+  CondIntern deny;
   std::vector<DenySet> dsets;
-  std::unordered_map<std::string, uint32_t> dkey_id, dcond_id, dset_id;
+  std::unordered_map<std::string, uint32_t> dset_id;
   // validate.foreach on the device (KV_COMPILE_FOREACH, kvcond.cpp compile_foreach): the list
-  // queries (text after `request.object`-rooted JMESPath), the element-scoped strings (ftags: the
-  // interning text of each, "<p|d><list>:" + text), the conditions over them and the foreach sets
-  // (RuleRec::deny - 1 - dsets.size()); flist_keys: the strings of each list in column order
+  // queries (text after `request.object`-rooted JMESPath), the element-scoped strings (elem.keys:
+  // the interning text of each, "<p|d><list>:" + text; fkeys: the same strings taken apart), the
+  // conditions over them and the foreach sets (RuleRec::deny - 1 - dsets.size()); flist_keys: the
+  // strings of each list in column order
   std::vector<std::string> flists;
   std::vector<FeKey> fkeys;
-  std::vector<std::string> ftags;
+  CondIntern elem;
   std::vector<std::vector<uint32_t>> flist_keys;
-  std::vector<CondRec> fconds;
   std::vector<FeSet> fsets;
-  std::unordered_map<std::string, uint32_t> flist_id, ftag_id, fcond_id, fset_id;
+  std::unordered_map<std::string, uint32_t> flist_id, fset_id;
   // columns of a Batch::vout row: the pattern-variable keys, then the condition strings of the
   // preconditions, then those of the deny blocks
-  size_t vout_width() const { return vkeys.size() + ckeys.size() + dkeys.size(); }
+  size_t vout_width() const { return vkeys.size() + gate.keys.size() + deny.keys.size(); }
 };
 
 // Compiles a JSON list of (already autogen-expanded) ClusterPolicy/Policy
@@ -409,7 +421,7 @@ struct Batch {
   uint32_t ns_words = 1;
   uint64_t bytes_referenced = 0;     // algorithmic bytes of the projected store
   // pattern variables and precondition strings: outcome id per (resource, PolicySet::vkeys
-  // entry, then PolicySet::ckeys entry), resource-major, and the distinct outcomes (kvvars.cpp
+  // entry, then PolicySet::gate.keys entry), resource-major, and the distinct outcomes (kvvars.cpp
   // resolve_var_string encoding)
   std::vector<uint32_t> vout;
   std::vector<std::string> vout_tab;

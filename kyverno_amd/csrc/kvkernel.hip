@@ -33,8 +33,7 @@ using namespace kv;
 #include "kvdevfn.h"
 #include "kvfac.h"
 #include "kvcol.h"
-#include "kvpre.h"
-#include "kvdeny.h"
+#include "kvblocks.h"
 #include "kvforeach.h"
 
 // ------------------------------------------------------------------ kernel
@@ -359,53 +358,41 @@ hipError_t launch_validate(const DevPS* P, const DevBatch* B, uint32_t n_res, co
 }  // namespace kv
 
 // ---------------------------------------------------------------------------
-// Precondition gate (kvcond.h, kvpre.h): one lane per resource, grid.x = workgroups of 256
-// resources, grid.y = condition sets (a workgroup walks sets blockIdx.y, + gridDim.y, ...). The
-// set's entry list is wave-uniform (scalar loads); per condition string one coalesced 32-bit load
-// of the lane's outcome id, then two gathers into the bit planes (small: they stay in L2). One
-// byte per (set, resource): 0 pass, ST_SKIP, ST_CPU; lanes past n_res write nothing.
+// Condition blocks of a batch (kvcond.h, kvblocks.h): the precondition gate and the deny fold are
+// one body. One lane per resource, grid.x = workgroups of 256 resources, grid.y = sets (a
+// workgroup walks sets blockIdx.y, + gridDim.y, ...). The set's entry list is wave-uniform (scalar
+// loads); per string one coalesced 32-bit load of the lane's outcome id (STRICT: and two bit tests
+// in the string's error / out-of-scope planes), per condition two gathers into the bit planes
+// (small: they stay in L2). One byte per (set, resource); lanes past n_res write nothing.
+//   kv_precond_kernel: 0 pass, ST_SKIP, ST_CPU
+//   kv_deny_kernel:    ST_PASS, ST_FAIL, ST_ERROR or ST_CPU
 constexpr uint32_t KV_PRE_YMAX = 1024u;
-extern "C" __global__ __launch_bounds__(KV_WG) void kv_precond_kernel(const DevBatch* __restrict__ Bp, uint32_t n_res,
-                                                                       uint32_t n_sets, uint8_t* __restrict__ pre_st) {
-  const DevBatch& B = *Bp;
+template <bool STRICT>
+__device__ __forceinline__ void kv_cond_body(const CondBlocks& T, uint32_t n_res, uint32_t n_sets,
+                                             uint8_t* __restrict__ st) {
   const uint64_t r = (uint64_t)blockIdx.x * KV_WG + threadIdx.x;
   if (r >= n_res) return;
-  for (uint32_t s = blockIdx.y; s < n_sets; s += gridDim.y)
-    pre_st[(size_t)s * n_res + r] =
-        (uint8_t)kv_pre_lane(B.pre_sets, B.pre_ents, B.pre_outc, B.pre_truth, B.pre_unk, B.pre_words, s, n_res, r);
+  for (uint32_t s = blockIdx.y; s < n_sets; s += gridDim.y) {
+    const uint32_t f = kv_cond_fold<STRICT>(T, s, n_res, r);
+    st[(size_t)s * n_res + r] = (uint8_t)(STRICT ? kv_deny_status(f) : kv_gate_status(f));
+  }
+}
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_precond_kernel(CondBlocks T, uint32_t n_res, uint32_t n_sets,
+                                                                       uint8_t* __restrict__ pre_st) {
+  kv_cond_body<false>(T, n_res, n_sets, pre_st);
+}
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_deny_kernel(CondBlocks T, uint32_t n_res, uint32_t n_sets,
+                                                                    uint8_t* __restrict__ deny_st) {
+  kv_cond_body<true>(T, n_res, n_sets, deny_st);
 }
 
 namespace kv {
-hipError_t launch_precond(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* pre_st, hipStream_t stream) {
+hipError_t launch_cond(bool strict, const CondBlocks& T, uint32_t n_res, uint32_t n_sets, uint8_t* st,
+                       hipStream_t stream) {
   if (n_res == 0 || n_sets == 0) return hipSuccess;
-  hipLaunchKernelGGL(kv_precond_kernel, dim3((n_res + KV_WG - 1) / KV_WG, n_sets < KV_PRE_YMAX ? n_sets : KV_PRE_YMAX),
-                     dim3(KV_WG), 0, stream, B, n_res, n_sets, pre_st);
-  return hipGetLastError();
-}
-}  // namespace kv
-
-// ---------------------------------------------------------------------------
-// Deny fold (kvcond.h, kvdeny.h): the same launch shape as the precondition gate: one lane per
-// resource, grid.x = workgroups of 256 resources, grid.y = deny sets (a workgroup walks sets
-// blockIdx.y, + gridDim.y, ...). The set's entry list is wave-uniform; per string one coalesced
-// 32-bit load of the lane's outcome id and two bit tests in the string's planes, per condition two
-// more. One byte per (set, resource): ST_PASS, ST_FAIL, ST_ERROR or ST_CPU; lanes past n_res
-// write nothing.
-extern "C" __global__ __launch_bounds__(KV_WG) void kv_deny_kernel(const DevBatch* __restrict__ Bp, uint32_t n_res,
-                                                                    uint32_t n_sets, uint8_t* __restrict__ deny_st) {
-  const DevBatch& B = *Bp;
-  const uint64_t r = (uint64_t)blockIdx.x * KV_WG + threadIdx.x;
-  if (r >= n_res) return;
-  for (uint32_t s = blockIdx.y; s < n_sets; s += gridDim.y)
-    deny_st[(size_t)s * n_res + r] = (uint8_t)kv_deny_lane(B.deny_sets, B.deny_ents, B.deny_outc, B.deny_truth, B.deny_unk,
-                                                           B.deny_err, B.deny_oos, B.deny_words, s, n_res, r);
-}
-
-namespace kv {
-hipError_t launch_deny(const DevBatch* B, uint32_t n_res, uint32_t n_sets, uint8_t* deny_st, hipStream_t stream) {
-  if (n_res == 0 || n_sets == 0) return hipSuccess;
-  hipLaunchKernelGGL(kv_deny_kernel, dim3((n_res + KV_WG - 1) / KV_WG, n_sets < KV_PRE_YMAX ? n_sets : KV_PRE_YMAX),
-                     dim3(KV_WG), 0, stream, B, n_res, n_sets, deny_st);
+  hipLaunchKernelGGL(strict ? kv_deny_kernel : kv_precond_kernel,
+                     dim3((n_res + KV_WG - 1) / KV_WG, n_sets < KV_PRE_YMAX ? n_sets : KV_PRE_YMAX), dim3(KV_WG), 0, stream,
+                     T, n_res, n_sets, st);
   return hipGetLastError();
 }
 }  // namespace kv

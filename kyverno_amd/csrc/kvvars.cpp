@@ -22,8 +22,7 @@
 #include <stdexcept>
 
 #include "kvinternal.hpp"
-#include "kvpre.h"
-#include "kvdeny.h"
+#include "kvblocks.h"
 #include "kvforeach.h"
 
 namespace kvh {

@@ -53,8 +53,10 @@ def _with_env(env: dict, fn):
                 os.environ[k] = v
 
 
-def build(policies, workdir: str, env: dict | None = None, opt: str = "-O1", extra: tuple = ()) -> str:
-    """Generate the specialized source of `policies` and build the emulator binary for it."""
+def build(policies, workdir: str, env: dict | None = None, opt: str = "-O1", extra: tuple = (),
+          deny: bool = False, foreach: bool = False) -> str:
+    """Generate the specialized source of `policies` (compiled with the deny / foreach flags) and
+    build the emulator binary for it."""
     from kyverno_amd import batch
 
     build_host()
@@ -62,7 +64,7 @@ def build(policies, workdir: str, env: dict | None = None, opt: str = "-O1", ext
     src = os.path.join(workdir, "gen.cpp")
     genv = dict(env or {})
     genv.update(KVGPU_JIT_DUMP=src, KVGPU_JIT_SKIP_COMPILE="1")
-    _with_env(genv, lambda: batch.PolicySet(policies, specialize=True))
+    _with_env(genv, lambda: batch.PolicySet(policies, specialize=True, deny=deny, foreach=foreach))
     data = open(src, "rb").read()
     host = hashlib.sha1(open(HOSTLIB, "rb").read()).hexdigest()  # the driver / host objects it links
     tag = hashlib.sha1(data + json.dumps(env or {}, sort_keys=True).encode() + opt.encode() +
@@ -81,8 +83,11 @@ def build(policies, workdir: str, env: dict | None = None, opt: str = "-O1", ext
 
 
 def run(exe: str, resources: bytes, workdir: str, env: dict | None = None, ctx: dict | None = None,
-        timeout: int = 1800):
-    """Runs the emulator; returns (status [rules][res] u8, records [rules][res][8] u32)."""
+        timeout: int = 1800, deny: bool = False, foreach: bool = False):
+    """Runs the emulator (with the compile flags its binary was built with); returns
+    (status [rules][res] u8, records [rules][res][8] u32)."""
+    from kyverno_amd import batch
+
     rpath = os.path.join(workdir, "resources.ndjson")
     with open(rpath, "wb") as f:
         f.write(resources)
@@ -94,6 +99,7 @@ def run(exe: str, resources: bytes, workdir: str, env: dict | None = None, ctx: 
     out = os.path.join(workdir, "out")
     e = dict(os.environ)
     e.update({k: str(v) for k, v in (env or {}).items()})
+    e["KVEMU_COMPILE_FLAGS"] = str((batch.COMPILE_DENY if deny else 0) | (batch.COMPILE_FOREACH if foreach else 0))
     e["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=0"
     e["UBSAN_OPTIONS"] = "print_stacktrace=1"
     p = subprocess.run([exe, os.path.join(workdir, "policies.json"), rpath, cpath, out], env=e, capture_output=True,

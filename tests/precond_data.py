@@ -131,6 +131,12 @@ def crafted_policy():
              {"message": "tagged", "pattern": IMAGE_TAG}),
         rule("array-in-all", {"all": [{"key": ZONES, "operator": "NotEquals", "value": "z0"}]},
              {"message": "tagged", "pattern": IMAGE_TAG}),
+        # one string in both lists, another string's condition between them in list order: the
+        # gate's entries go by string across `any` and `all` together
+        rule("one-string-any-and-all", {"any": [{"key": TIER, "operator": "In", "value": ["t2*", "t30"]},
+                                                {"key": APP, "operator": "Equals", "value": "db"}],
+                                        "all": [{"key": TIER, "operator": "NotEquals", "value": "t21"}]},
+             {"message": "tagged", "pattern": IMAGE_TAG}),
         rule("no-preconditions", None, {"message": "tagged", "pattern": IMAGE_TAG}),
     ]
     return _policy("crafted-preconditions", rules)

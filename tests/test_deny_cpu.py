@@ -1,4 +1,4 @@
-"""validate.deny on the device, without a GPU (kvcond.cpp compile_deny / build_deny, kvdeny.h;
+"""validate.deny on the device, without a GPU (kvcond.cpp compile_deny / build_deny, kvblocks.h;
 reference pkg/engine/validation.go:299-339): the deny model against the reference's own test cases
 (tests/golden/deny.json, the duration-test rules of tests/golden/cli.json), rule routing with the
 compile flag on and off, interning of deny sets, the exported symbols, and the host fold
@@ -242,7 +242,7 @@ def test_crafted_expected_covers_the_cases(orc):
 
 @pytest.mark.parametrize("n", [1, 65, 513])
 def test_host_fold_matches_model(orc, n):
-    """kv_batch_deny_fold (kv_deny_lane on the host, over the tables the device gets) per deny set,
+    """kv_batch_deny_fold (the fold and verdict of kv_deny_kernel on the host, over the tables the device gets) per deny set,
     against the deny model alone: ERROR / CPU / FAIL / PASS of the block on every resource,
     whatever match and the preconditions say."""
     pol, ress = dd.crafted_policy(), dd.crafted_resources(n)
@@ -264,3 +264,18 @@ def test_host_fold_matches_model(orc, n):
             if fold[sets[ri] - 1, k] != want:
                 bad.append((rule["name"], k, int(fold[sets[ri] - 1, k]), want))
     assert not bad, bad[:20]
+
+
+def test_specialized_kernels_on_the_emulator(orc):
+    """The crafted set at 257 resources through the specialized kernels compiled for the host
+    (tests/kvemu.py; the driver fills the deny plane with the per-lane function the device kernel
+    runs), against the decomposition."""
+    import kvemu
+
+    pol, ress = dd.crafted_policy(), dd.crafted_resources(257)
+    e = dd.Expected(orc, pol, ress)
+    work = os.path.join(ROOT, "build", "kvemu_tests", "deny")
+    exe = kvemu.build([pol], work, deny=True)
+    st, _ = kvemu.run(exe, b"\n".join(json.dumps(r).encode() for r in ress), work, deny=True)
+    bad = np.argwhere(st != e.status)
+    assert not len(bad), [(pol["spec"]["rules"][a]["name"], int(b), int(st[a, b]), int(e.status[a, b])) for a, b in bad[:20]]

@@ -288,6 +288,20 @@ def test_fold_range_checks():
     assert lib.kv_batch_foreach_fold(ps._h, b._h, 0, out.ctypes.data, None, 3) == 0
 
 
+def test_specialized_kernels_on_the_emulator(expected):
+    """The crafted set at 257 resources through the specialized kernels compiled for the host
+    (tests/kvemu.py; the driver fills the foreach rows of the deny plane with the host fold), against
+    the decomposition."""
+    import kvemu
+
+    pol, exp = expected[0], expected[1][257]
+    work = os.path.join(ROOT, "build", "kvemu_tests", "foreach")
+    exe = kvemu.build([pol], work, foreach=True)
+    st, _ = kvemu.run(exe, b"\n".join(json.dumps(r).encode() for r in exp.resources), work, foreach=True)
+    bad = np.argwhere(st != exp.status)
+    assert not len(bad), [(pol["spec"]["rules"][a]["name"], int(b), int(st[a, b]), int(exp.status[a, b])) for a, b in bad[:20]]
+
+
 # ------------------------------------------------------------------ messages
 def test_msgvars_element_root():
     res = {"metadata": {"namespace": "ns1"}, "spec": {}}

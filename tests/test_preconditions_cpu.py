@@ -1,4 +1,4 @@
-"""Rule preconditions without a GPU (kvcond.cpp, kvpre.h; reference pkg/engine/variables/operator/*.go,
+"""Rule preconditions without a GPU (kvcond.cpp, kvblocks.h; reference pkg/engine/variables/operator/*.go,
 evaluate.go:42-78, validation.go:175-193): the model and the library's host evaluator
 (`kv_condition_eval`) against the reference's own test table (tests/golden/conditions.json), the
 evaluator against the model on a seeded fuzz, rule routing, interning of condition sets, and the

@@ -28,8 +28,6 @@
 #include "../../kyverno_amd/csrc/kvinternal.hpp"
 #include "../../kyverno_amd/csrc/kvjit.hpp"
 #include "../../kyverno_amd/csrc/kvcond.h"
-#include "../../kyverno_amd/csrc/kvpre.h"
-#include "../../kyverno_amd/csrc/kvdeny.h"
 
 using namespace kv;
 using namespace kvh;
@@ -98,7 +96,7 @@ int main(int argc, char** argv) {
     const std::string pol = slurp(argv[1]), res = slurp(argv[2]);
     std::string ctx = strcmp(argv[3], "-") ? slurp(argv[3]) : std::string();
     PolicySet ps;
-    // KVEMU_COMPILE_FLAGS: kv_compile's flags (2: KV_COMPILE_DENY), as the binary's source was generated
+    // KVEMU_COMPILE_FLAGS: kv_compile's flags (2: KV_COMPILE_DENY, 4: KV_COMPILE_FOREACH), as the binary's source was generated
     compile_policies(pol.data(), pol.size(), &ps, getenv("KVEMU_COMPILE_FLAGS") ? (uint32_t)atoi(getenv("KVEMU_COMPILE_FLAGS")) : 0u);
     Batch whole;
     ingest_resources(ps, res.data(), res.size(), nullptr, &whole);
@@ -225,47 +223,29 @@ int main(int argc, char** argv) {
     B.dps = &PD;
     B.dleaf = dyn.dleaf.data();
     B.dyn_st = dyn.dyn_st.data();
-    // preconditions (as dev_batch): the gate's tables, then every (set, resource) through the
-    // per-lane function kv_precond_kernel runs (kvpre.h)
-    PreHost pre;
-    std::vector<uint8_t> pre_st;
-    if (!ps.csets.empty() && !b.res.empty()) {
+    // condition blocks (as dev_batch): the tables, then every (set, resource) through the host
+    // twins of kv_precond_kernel, kv_deny_kernel and the foreach kernels (kvcond.h: the per-lane
+    // functions the kernels run); the deny plane has the deny sets' rows, then the foreach sets'
+    CondHost pre, dn;
+    FeHost fe;
+    std::vector<uint8_t> pre_st, deny_st;
+    const size_t n_pre = ps.csets.size(), n_dn = ps.dsets.size(), n_fe = ps.fsets.size();
+    if (n_pre && !b.res.empty()) {
       build_pre(ps, b, &pre);
-      B.pre_sets = pre.sets.data();
-      B.pre_ents = pre.ents.data();
-      B.pre_outc = pre.outc.data();
-      B.pre_truth = pre.truth.data();
-      B.pre_unk = pre.unk.data();
-      B.pre_words = pre.words;
-      B.n_pre_sets = (uint32_t)ps.csets.size();
-      pre_st.assign((size_t)B.n_pre_sets * B.n_res, 0xEE);
-      for (uint32_t s = 0; s < B.n_pre_sets; s++)
-        for (uint32_t r = 0; r < B.n_res; r++)
-          pre_st[(size_t)s * B.n_res + r] = (uint8_t)kv_pre_lane(B.pre_sets, B.pre_ents, B.pre_outc, B.pre_truth,
-                                                                 B.pre_unk, B.pre_words, s, B.n_res, r);
+      pre_st.assign(n_pre * B.n_res, 0xEE);
+      for (size_t s = 0; s < n_pre; s++)
+        for (uint32_t r = 0; r < B.n_res; r++) pre_st[s * B.n_res + r] = pre_status_host(pre, (uint32_t)s, B.n_res, r);
       B.pre_st = pre_st.data();
     }
-    // validate.deny (as dev_batch): the fold's tables, then every (set, resource) through the
-    // per-lane function kv_deny_kernel runs (kvdeny.h)
-    DenyHost dn;
-    std::vector<uint8_t> deny_st;
-    if (!ps.dsets.empty() && !b.res.empty()) {
+    if ((n_dn || n_fe) && !b.res.empty()) {
       build_deny(ps, b, &dn);
-      B.deny_sets = dn.sets.data();
-      B.deny_ents = dn.ents.data();
-      B.deny_outc = dn.outc.data();
-      B.deny_truth = dn.truth.data();
-      B.deny_unk = dn.unk.data();
-      B.deny_err = dn.err.data();
-      B.deny_oos = dn.oos.data();
-      B.deny_words = dn.words;
-      B.n_deny_sets = (uint32_t)ps.dsets.size();
-      deny_st.assign((size_t)B.n_deny_sets * B.n_res, 0xEE);
-      for (uint32_t s = 0; s < B.n_deny_sets; s++)
+      build_foreach(ps, b, &fe);
+      deny_st.assign((n_dn + n_fe) * B.n_res, 0xEE);
+      for (size_t s = 0; s < n_dn; s++)
+        for (uint32_t r = 0; r < B.n_res; r++) deny_st[s * B.n_res + r] = deny_status_host(dn, (uint32_t)s, B.n_res, r);
+      for (size_t s = 0; s < n_fe; s++)
         for (uint32_t r = 0; r < B.n_res; r++)
-          deny_st[(size_t)s * B.n_res + r] = (uint8_t)kv_deny_lane(B.deny_sets, B.deny_ents, B.deny_outc, B.deny_truth,
-                                                                   B.deny_unk, B.deny_err, B.deny_oos, B.deny_words, s,
-                                                                   B.n_res, r);
+          deny_st[(n_dn + s) * B.n_res + r] = foreach_fold_host(fe, (uint32_t)s, B.n_res, r, nullptr);
       B.deny_st = deny_st.data();
     }
     // path columns of the image (as dev_batch: built once per batch)
