@@ -327,29 +327,32 @@ class Result:
             self._status_read = True
         return self._status
 
+    def _text(self, fn, rule: int, res: int, *extra, errors: str = "strict", empty_ok: bool = False) -> str | None:
+        """A text accessor ``fn(handle, rule, res, [extra...], buf, cap)`` of the library: its text
+        (the buffer regrown while the returned length does not fit), None for a negative return
+        and, unless the empty string is an answer of its own (``empty_ok``), for 0."""
+        cap = 256
+        while True:
+            buf = ctypes.create_string_buffer(cap)
+            n = fn(self._h, rule, res, *extra, buf, cap)
+            if n < 0 or (n == 0 and not empty_ok):
+                return None
+            if n < cap:
+                return buf.raw[:n].decode("utf-8", errors)
+            cap = n + 1
+
     def path(self, rule: int, res: int) -> str | None:
-        buf = ctypes.create_string_buffer(4096)
-        n = lib().kv_result_path(self._h, rule, res, buf, 4096)
-        if n < 0:
-            return None
-        return buf.value.decode("utf-8")
+        return self._text(lib().kv_result_path, rule, res, empty_ok=True)
 
     def precond_message(self, rule: int, res: int) -> str | None:
         """"preconditions not met" for a SKIP pair decided by the rule's preconditions
         (``kv_result_precond_message``), else None (a conditional-anchor SKIP of the pattern)."""
-        buf = ctypes.create_string_buffer(64)
-        n = lib().kv_result_precond_message(self._h, rule, res, buf, 64)
-        return buf.raw[:n].decode("utf-8") if n > 0 else None
+        return self._text(lib().kv_result_precond_message, rule, res)
 
     def deny_message(self, rule: int, res: int) -> str | None:
         """"failed to substitute variables in deny conditions: ..." for an ERROR pair of a device
         deny rule (``kv_result_deny_message``), else None."""
-        n = lib().kv_result_deny_message(self._h, rule, res, None, 0)
-        if n <= 0:
-            return None
-        buf = ctypes.create_string_buffer(n + 1)
-        lib().kv_result_deny_message(self._h, rule, res, buf, n + 1)
-        return buf.raw[:n].decode("utf-8")
+        return self._text(lib().kv_result_deny_message, rule, res)
 
     def foreach_element(self, rule: int, res: int) -> int | None:
         """The index in its list of the element that decided a FAIL / ERROR pair of a device foreach
@@ -362,25 +365,12 @@ class Result:
         """"validation failed in foreach rule for failed to substitute ..." for an ERROR pair of a
         device foreach rule, "rule skipped" for a SKIP the fold decided
         (``kv_result_foreach_message``), else None."""
-        n = lib().kv_result_foreach_message(self._h, rule, res, None, 0)
-        if n <= 0:
-            return None
-        buf = ctypes.create_string_buffer(n + 1)
-        lib().kv_result_foreach_message(self._h, rule, res, buf, n + 1)
-        return buf.raw[:n].decode("utf-8")
+        return self._text(lib().kv_result_foreach_message, rule, res)
 
     def subst_error(self, rule: int, res: int) -> str | None:
         """The RuleResponse message of an ERROR pair caused by the pattern's variables failing to
         substitute ("variable substitution failed: ...", ``kv_result_subst_error``), else None."""
-        cap = 1 << 12
-        while True:
-            buf = ctypes.create_string_buffer(cap)
-            n = lib().kv_result_subst_error(self._h, rule, res, buf, cap)
-            if n <= 0:
-                return None
-            if n < cap:
-                return buf.raw[:n].decode("utf-8", "replace")
-            cap = n + 1
+        return self._text(lib().kv_result_subst_error, rule, res, errors="replace")
 
     def error_message(self, rule: int, res: int, resource) -> str | None:
         """err.Error() of the pattern error behind a FAIL / ERROR / SKIP pair (``kv_result_error_message``):
@@ -389,15 +379,7 @@ class Result:
         doc = resource if isinstance(resource, (bytes, str)) else _dumps(resource)
         if isinstance(doc, str):
             doc = doc.encode("utf-8")
-        cap = 1 << 16
-        while True:
-            buf = ctypes.create_string_buffer(cap)
-            n = lib().kv_result_error_message(self._h, rule, res, doc, len(doc), buf, cap)
-            if n < 0:
-                return None
-            if n < cap:
-                return buf.raw[:n].decode("utf-8", "replace")
-            cap = n + 1
+        return self._text(lib().kv_result_error_message, rule, res, doc, len(doc), errors="replace", empty_ok=True)
 
     def failures(self):
         """Every FAIL / ERROR / SKIP pair (``kv_result_failures``), rule-major in resource order:

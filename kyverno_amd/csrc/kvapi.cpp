@@ -1,352 +1,18 @@
 // C ABI (include/kvgpu.h) + device runtime: HBM residency of compiled policy
 // sets and ingested batches, launch-time folding of batch-constant user info,
-// result decoding (failing paths) on the host.
+// sessions. (Pools: kvmem.cpp; host-side reading of a fetched result: kvresult.cpp.)
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include <algorithm>
-#include <emmintrin.h>
 #include <chrono>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <tuple>
-#include <stdexcept>
-#include <thread>
-#include <string>
-#include <unordered_map>
-#include <vector>
 
-#include "../../include/kvgpu.h"
-#include "kvcond.h"
+#define KVRT_DEVICE 1
+#include "kvrt.hpp"
 #include "kvdev.h"
-#include "kvblocks.h"
-#include "kvforeach.h"
-#include "kvinternal.hpp"
-#include "kvjit.hpp"
 
-using namespace kv;
-using namespace kvh;
-
-namespace {
-
-struct HipError : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess) throw HipError(std::string(#x) + ": " + hipGetErrorString(e_));      \
-  } while (0)
-
-bool pinned_src(const void* src, size_t bytes);  // page-locked store array (PinnedStore)
-
-// HIP streams cost milliseconds to create and to destroy on this runtime (hipStreamCreate* 2.3-3.8
-// ms, hipStreamDestroy 1.8-2.6 ms per call in the rocprofv3 HIP API trace of a C2 kv_validate: 15 of
-// its 44 ms), so sessions and staged uploads take idle streams from a per-(device, flags) pool and
-// give them back instead. The pool also knows every stream it ever created per device (`all`): a
-// released device buffer becomes reusable once an event recorded on each of them has completed
-// (DevPool below).
-struct StreamPool {
-  std::mutex mu;
-  std::map<std::tuple<int, unsigned, int>, std::vector<hipStream_t>> free;
-  std::map<int, std::vector<hipStream_t>> all;
-  static StreamPool& get() {
-    static StreamPool* p = new StreamPool();  // never destroyed (streams die with the process)
-    return *p;
-  }
-  std::vector<hipStream_t> streams_of(int dev) {
-    std::lock_guard<std::mutex> g(mu);
-    return all[dev];
-  }
-  // a stream of the current device `dev`; low: the lowest scheduling priority (its workgroups are
-  // dispatched when the other queues' kernels leave slots free)
-  hipStream_t take(int dev, unsigned flags, bool low = false) {
-    const int prio = low ? lowest() : 0;
-    {
-      std::lock_guard<std::mutex> g(mu);
-      auto& v = free[{dev, flags, prio}];
-      if (!v.empty()) {
-        hipStream_t s = v.back();
-        v.pop_back();
-        return s;
-      }
-    }
-    hipStream_t s = nullptr;
-    if (low) HIPCHK(hipStreamCreateWithPriority(&s, flags, prio));
-    else HIPCHK(hipStreamCreateWithFlags(&s, flags));
-    std::lock_guard<std::mutex> g(mu);
-    all[dev].push_back(s);
-    return s;
-  }
-  void give(int dev, unsigned flags, hipStream_t s, bool low = false) {
-    if (!s) return;
-    (void)hipStreamSynchronize(s);
-    const int prio = low ? lowest() : 0;
-    std::lock_guard<std::mutex> g(mu);
-    free[{dev, flags, prio}].push_back(s);
-  }
-  static int lowest() {
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) {
-      (void)hipGetLastError();
-      return 0;
-    }
-    return least;
-  }
-};
-
-// Device allocations are expensive to create and to free (hipMalloc maps pages, hipFree also
-// waits for the device), and a host that validates batch after batch allocates the same store,
-// column and result buffers for every batch. Released buffers are therefore kept per device and
-// handed to the next allocation of a similar size. A released block is reusable once the work
-// queued before its release has finished (hipFree's own guarantee, without blocking the releasing
-// thread or any other session on the device): give() records an event on every stream the library
-// created on the device and on the null stream, and take() hands the block out only when all of
-// them have completed. At most kv_device_pool_limit() bytes are kept (default 32 GiB of the 288 GiB
-// HBM); when a hipMalloc fails the device's kept buffers are freed and the allocation retried, and
-// kv_device_trim() returns them to the device for co-resident allocators (e.g. torch).
-// KVGPU_DEVPOOL=0: plain hipMalloc / hipFree.
-struct DevPool {
-  struct Pending {
-    void* p;
-    size_t cap;
-    std::vector<hipEvent_t> ev;
-  };
-  std::mutex mu;
-  std::map<int, std::multimap<size_t, void*>> free;  // device -> capacity -> block
-  std::map<int, std::vector<Pending>> pending;        // released, maybe still in use by queued work
-  std::map<int, size_t> held;                         // free + pending bytes
-  std::map<int, std::vector<hipEvent_t>> evs;         // idle events per device
-  size_t hold = 32ull << 30;
-  static DevPool& get() {
-    static DevPool* p = new DevPool();  // never destroyed: buffers may be released during static teardown
-    return *p;
-  }
-  static bool enabled() {
-    static const bool on = !(getenv("KVGPU_DEVPOOL") && getenv("KVGPU_DEVPOOL")[0] == '0');
-    return on;
-  }
-  // (mu held) pending blocks whose events have all completed move to the free list
-  void settle(int dev) {
-    auto& pv = pending[dev];
-    for (size_t i = 0; i < pv.size();) {
-      bool done = true;
-      for (hipEvent_t e : pv[i].ev) {
-        const hipError_t q = hipEventQuery(e);
-        if (q == hipErrorNotReady) {
-          done = false;
-          break;
-        }
-        if (q != hipSuccess) (void)hipGetLastError();
-      }
-      if (!done) {
-        i++;
-        continue;
-      }
-      for (hipEvent_t e : pv[i].ev) evs[dev].push_back(e);
-      free[dev].emplace(pv[i].cap, pv[i].p);
-      pv[i] = std::move(pv.back());
-      pv.pop_back();
-    }
-  }
-  // a block of at least `bytes` on the current device `dev` (its capacity in *cap)
-  void* take(int dev, size_t bytes, size_t* cap) {
-    if (enabled()) {
-      std::lock_guard<std::mutex> g(mu);
-      settle(dev);
-      auto& f = free[dev];
-      auto it = f.lower_bound(bytes);
-      if (it != f.end() && it->first <= bytes + bytes / 4 + (2u << 20)) {
-        void* p = it->second;
-        *cap = it->first;
-        held[dev] -= it->first;
-        f.erase(it);
-        return p;
-      }
-    }
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      trim(dev);
-      HIPCHK(hipMalloc(&p, bytes));
-    }
-    *cap = bytes;
-    return p;
-  }
-  // `dev` is the current device
-  void give(int dev, void* p, size_t cap) {
-    if (enabled()) {
-      std::vector<hipStream_t> st = StreamPool::get().streams_of(dev);
-      st.push_back(nullptr);  // (the null stream: synchronous copies, RCCL setup)
-      std::lock_guard<std::mutex> g(mu);
-      if (held[dev] + cap <= hold) {
-        Pending pe{p, cap, {}};
-        bool ok = true;
-        for (hipStream_t s : st) {
-          hipEvent_t e = nullptr;
-          auto& idle = evs[dev];
-          if (!idle.empty()) {
-            e = idle.back();
-            idle.pop_back();
-          } else if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            ok = false;
-            break;
-          }
-          pe.ev.push_back(e);
-          if (hipEventRecord(e, s) != hipSuccess) {
-            (void)hipGetLastError();
-            ok = false;
-            break;
-          }
-        }
-        if (ok) {
-          pending[dev].push_back(std::move(pe));
-          held[dev] += cap;
-          return;
-        }
-        for (hipEvent_t e : pe.ev) evs[dev].push_back(e);
-      }
-    }
-    (void)hipDeviceSynchronize();  // (hipFree waits for the device anyway)
-    (void)hipFree(p);
-  }
-  size_t held_on(int dev) {
-    std::lock_guard<std::mutex> g(mu);
-    return held[dev];
-  }
-  // free every kept block of `dev` (the current device): waits for the device first
-  void trim(int dev) {
-    std::multimap<size_t, void*> f;
-    std::vector<Pending> pv;
-    {
-      std::lock_guard<std::mutex> g(mu);
-      f.swap(free[dev]);
-      pv.swap(pending[dev]);
-      held[dev] = 0;
-    }
-    if (f.empty() && pv.empty()) return;
-    (void)hipDeviceSynchronize();
-    for (auto& [c, p] : f) (void)hipFree(p);
-    std::lock_guard<std::mutex> g(mu);
-    for (Pending& pe : pv) {
-      (void)hipFree(pe.p);
-      for (hipEvent_t e : pe.ev) evs[dev].push_back(e);
-    }
-  }
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t n = 0, cap = 0;
-  int dev = -1;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  template <class T, class A>
-  void upload(const std::vector<T, A>& v, int device) {
-    upload_raw(v.data(), v.size() * sizeof(T), device);
-  }
-  void upload_raw(const void* src, size_t bytes, int device) {
-    alloc(bytes, device);
-    if (bytes) upload_h2d(p, src, bytes);
-  }
-  // a page-locked source is copied asynchronously on `st` (the caller synchronizes `st` before
-  // the source may change or the buffer is read elsewhere); a pageable one as upload_raw
-  template <class T, class A>
-  void upload_async(const std::vector<T, A>& v, int device, hipStream_t st) {
-    const size_t bytes = v.size() * sizeof(T);
-    alloc(bytes, device);
-    if (!bytes) return;
-    if (pinned_src(v.data(), bytes))
-      HIPCHK(hipMemcpyAsync(p, v.data(), bytes, hipMemcpyHostToDevice, st));
-    else
-      upload_h2d(p, v.data(), bytes);
-  }
-  // Host-to-device copy of a (pageable) host range. Large ranges go through a pinned staging
-  // ring: host threads copy chunk i into a page-locked buffer while the DMA engine moves chunk
-  // i-1 (32 MB chunks, 4 buffers, up to 16 copy threads).
-  static void upload_h2d(void* dst, const void* src, size_t bytes) {
-    constexpr size_t kChunk = 32u << 20;
-    constexpr size_t kMin = 16u << 20;
-    constexpr int kRing = 4;
-    if (bytes < kMin || pinned_src(src, bytes)) {
-      HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-      return;
-    }
-    static std::mutex mu;  // one staged upload at a time per process (the ring is shared)
-    static char* ring[kRing] = {};
-    std::lock_guard<std::mutex> g(mu);
-    if (!ring[0]) {
-      for (int i = 0; i < kRing; i++) {
-        if (hipHostMalloc((void**)&ring[i], kChunk, hipHostMallocPortable) != hipSuccess) {
-          (void)hipGetLastError();
-          for (int j = 0; j < i; j++) (void)hipHostFree(ring[j]);
-          ring[0] = nullptr;
-          HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-          return;
-        }
-      }
-    }
-    int sdev = 0;
-    HIPCHK(hipGetDevice(&sdev));
-    hipStream_t st = StreamPool::get().take(sdev, hipStreamNonBlocking);
-    hipEvent_t ev[kRing];
-    for (int i = 0; i < kRing; i++) HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    bool used[kRing] = {};
-    static const unsigned T = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    size_t k = 0;
-    for (size_t off = 0; off < bytes; off += kChunk, k++) {
-      const int i = (int)(k % kRing);
-      const size_t len = std::min(kChunk, bytes - off);
-      if (used[i]) HIPCHK(hipEventSynchronize(ev[i]));  // the DMA out of this buffer is done
-      const char* s = (const char*)src + off;
-      std::vector<std::thread> th;
-      const size_t part = (len + T - 1) / T;
-      for (unsigned t = 0; t < T; t++) {
-        const size_t a = std::min(len, t * part), e = std::min(len, a + part);
-        if (a < e) th.emplace_back([=]() { memcpy(ring[i] + a, s + a, e - a); });
-      }
-      for (auto& x : th) x.join();
-      HIPCHK(hipMemcpyAsync((char*)dst + off, ring[i], len, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(ev[i], st));
-      used[i] = true;
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < kRing; i++) (void)hipEventDestroy(ev[i]);
-    StreamPool::get().give(sdev, hipStreamNonBlocking, st);
-  }
-  void swap(DevBuf& o) {
-    std::swap(p, o.p);
-    std::swap(n, o.n);
-    std::swap(cap, o.cap);
-    std::swap(dev, o.dev);
-  }
-  void alloc(size_t bytes, int device) {  // (a buffer allocated before is released first)
-    release();
-    dev = device;
-    n = bytes;
-    p = DevPool::get().take(device, std::max<size_t>(bytes, 16), &cap);
-  }
-  void release() {
-    if (!p) return;
-    int cur;
-    if (hipGetDevice(&cur) == hipSuccess) {
-      (void)hipSetDevice(dev);
-      DevPool::get().give(dev, p, cap);
-      (void)hipSetDevice(cur);
-    }
-    p = nullptr;
-    n = 0;
-    cap = 0;
-  }
-};
+namespace kvh {
 
 struct DevPolicySet {
   DevBuf prog, preds, alts, conjs, atoms, rules, filters, kinds, strrefs, strpairs, sels, sellabels, selexprs, kgs,
@@ -405,471 +71,12 @@ struct DevBatchRes {
   double pre_ms = 0, deny_ms = 0, fe_ms = 0;
   DevBatch view{};
 };
+}  // namespace kvh
 
-}  // namespace
-
-struct kv_policyset {
-  PolicySet ps;
-  std::unique_ptr<JitImage> jit;  // KV_COMPILE_SPECIALIZE
-  std::mutex mu;
-  std::map<int, std::unique_ptr<DevPolicySet>> dev;
-};
-
-struct kv_batch {
-  Batch b;
-  const kv_policyset* owner = nullptr;
-  std::mutex mu;
-  // device copies, shared with the sessions that use them (a session keeps its copy alive when
-  // the batch drops it: kv_batch_free, a parts session's detach)
-  std::map<int, std::shared_ptr<DevBatchRes>> dev;
-  std::once_flag dyn_once;
-  DynHost dyn;  // pattern-variable tables (build_dyn), on first use
-  const DynHost& dyn_host(const PolicySet& ps) {
-    std::call_once(dyn_once, [&]() { build_dyn(ps, b, &dyn); });
-    return dyn;
-  }
-  std::once_flag pre_once;
-  CondHost pre;  // precondition tables (build_pre), on first use by the host accessors
-  const CondHost& pre_host(const PolicySet& ps) {
-    std::call_once(pre_once, [&]() { build_pre(ps, b, &pre); });
-    return pre;
-  }
-  std::once_flag fe_once;
-  FeHost fe;  // foreach tables (build_foreach), on first use by the host accessors
-  const FeHost& fe_host(const PolicySet& ps) {
-    std::call_once(fe_once, [&]() { build_foreach(ps, b, &fe); });
-    return fe;
-  }
-  // caller index -> store index (the inverse of Batch::order), on first use; null: identity
-  std::once_flag inv_once;
-  std::vector<uint32_t> inv;
-  const uint32_t* inverse() {
-    if (b.order.empty()) return nullptr;
-    std::call_once(inv_once, [&]() {
-      inv.assign(b.order.size(), 0);
-      for (size_t i = 0; i < b.order.size(); i++) inv[b.order[i]] = (uint32_t)i;
-    });
-    return inv.data();
-  }
-};
+kv_policyset::kv_policyset() = default;
+kv_policyset::~kv_policyset() = default;
 
 namespace {
-
-// Page-locked host blocks are expensive to create (pinning), so released result
-// buffers are kept for the next result of the process (up to 8 GiB): a host that
-// validates batch after batch pays the pinning once.
-// A caller that knows its batches' size can page-lock an arena up front (kv_host_reserve, outside
-// ingest): blocks are then carved from it (first fit, 2 MiB granules, freed ranges coalesce) before
-// any new block is page-locked, so even a process's first batch ingests into page-locked memory
-// that is already there.
-struct PinnedPool {
-  std::mutex mu;
-  std::multimap<size_t, void*> free;  // capacity -> block
-  size_t held = 0;
-  char* arena = nullptr;
-  size_t arena_bytes = 0;
-  std::map<size_t, size_t> arena_free;  // offset -> bytes
-  static constexpr size_t kGran = 2u << 20;
-  static PinnedPool& get() {
-    static PinnedPool* p = new PinnedPool();  // never destroyed: blocks may outlive static teardown
-    return *p;
-  }
-  bool reserve(size_t bytes) {
-    std::lock_guard<std::mutex> g(mu);
-    if (arena) return arena_bytes >= bytes;
-    bytes = (bytes + kGran - 1) / kGran * kGran;
-    void* p = nullptr;
-    if (!bytes || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return false;
-    }
-    arena = (char*)p;
-    arena_bytes = bytes;
-    arena_free[0] = bytes;
-    return true;
-  }
-  bool in_arena(const void* p) const { return arena && (const char*)p >= arena && (const char*)p < arena + arena_bytes; }
-  void* take(size_t bytes, size_t* cap) {
-    {
-      std::lock_guard<std::mutex> g(mu);
-      auto it = free.lower_bound(bytes);
-      if (it != free.end() && it->first <= 2 * bytes + (1u << 20)) {
-        void* p = it->second;
-        *cap = it->first;
-        held -= it->first;
-        free.erase(it);
-        return p;
-      }
-      if (arena) {
-        const size_t want = (bytes + kGran - 1) / kGran * kGran;
-        for (auto a = arena_free.begin(); a != arena_free.end(); ++a)
-          if (a->second >= want) {
-            const size_t off = a->first, left = a->second - want;
-            arena_free.erase(a);
-            if (left) arena_free[off + want] = left;
-            *cap = want;
-            return arena + off;
-          }
-      }
-    }
-    // headroom (+1/8, 16 MiB granules) so the next batch's slightly larger result fits the block
-    const size_t want = bytes < (16u << 20) ? bytes : ((bytes + bytes / 8 + (16u << 20) - 1) & ~(size_t)((16u << 20) - 1));
-    void* p = nullptr;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    *cap = want;
-    return p;
-  }
-  void give(void* p, size_t cap) {
-    std::lock_guard<std::mutex> g(mu);
-    if (in_arena(p)) {  // back into the arena, merged with its free neighbours
-      size_t off = (size_t)((char*)p - arena), len = cap;
-      auto nx = arena_free.lower_bound(off);
-      if (nx != arena_free.end() && nx->first == off + len) {
-        len += nx->second;
-        nx = arena_free.erase(nx);
-      }
-      if (nx != arena_free.begin()) {
-        auto pv = std::prev(nx);
-        if (pv->first + pv->second == off) {
-          off = pv->first;
-          len += pv->second;
-          arena_free.erase(pv);
-        }
-      }
-      arena_free[off] = len;
-      return;
-    }
-    if (held + cap > (8ull << 30)) {
-      (void)hipHostFree(p);
-      return;
-    }
-    free.emplace(cap, p);
-    held += cap;
-  }
-};
-
-// Page-locked store arrays of ingested batches (kvinternal.hpp HostMem): blocks from the
-// pool, registered by address so the upload can tell a page-locked source (direct DMA)
-// from a pageable one (staging ring), and so a block returns to the pool when freed.
-struct PinnedStore {
-  std::mutex mu;
-  std::map<uintptr_t, size_t> live;  // block -> capacity
-  static PinnedStore& get() {
-    static PinnedStore* p = new PinnedStore();
-    return *p;
-  }
-  static bool enabled() {
-    static const bool on = []() {
-      if (getenv("KVGPU_PINNED") && getenv("KVGPU_PINNED")[0] == '0') return false;
-      int n = 0;  // no device (host-only use of the library): plain memory
-      if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        (void)hipGetLastError();
-        return false;
-      }
-      return true;
-    }();
-    return on;
-  }
-  static void* take(size_t bytes) {
-    if (!enabled()) return nullptr;
-    size_t cap = 0;
-    void* p = PinnedPool::get().take(bytes, &cap);
-    if (!p) return nullptr;
-    std::lock_guard<std::mutex> g(get().mu);
-    get().live[(uintptr_t)p] = cap;
-    return p;
-  }
-  static bool give(void* p) {
-    size_t cap = 0;
-    {
-      std::lock_guard<std::mutex> g(get().mu);
-      auto it = get().live.find((uintptr_t)p);
-      if (it == get().live.end()) return false;
-      cap = it->second;
-      get().live.erase(it);
-    }
-    PinnedPool::get().give(p, cap);
-    return true;
-  }
-  // [src, src + bytes) inside one live page-locked block
-  static bool contains(const void* src, size_t bytes) {
-    std::lock_guard<std::mutex> g(get().mu);
-    auto& m = get().live;
-    auto it = m.upper_bound((uintptr_t)src);
-    if (it == m.begin()) return false;
-    --it;
-    return (uintptr_t)src + bytes <= it->first + it->second;
-  }
-};
-struct InstallHostMem {
-  InstallHostMem() {
-    g_hostmem.take = &PinnedStore::take;
-    g_hostmem.give = &PinnedStore::give;
-  }
-} install_host_mem_;
-
-bool pinned_src(const void* src, size_t bytes) { return PinnedStore::contains(src, bytes); }
-
-// Host array without value-initialisation; page-locked (pooled hipHostMalloc) unless
-// KVGPU_PINNED=0, so device-to-host copies of results are direct DMA.
-template <class T>
-struct HostArray {
-  T* p = nullptr;
-  size_t n = 0, cap = 0;
-  bool pinned = false;
-  HostArray() = default;
-  HostArray(const HostArray&) = delete;
-  HostArray& operator=(const HostArray&) = delete;
-  HostArray(HostArray&& o) noexcept : p(o.p), n(o.n), cap(o.cap), pinned(o.pinned) { o.p = nullptr; o.n = 0; }
-  ~HostArray() { release(); }
-  void alloc(size_t count) {
-    release();
-    n = count;
-    if (!count) return;
-    static const bool use_pinned = !(getenv("KVGPU_PINNED") && getenv("KVGPU_PINNED")[0] == '0');
-    if (use_pinned && (p = (T*)PinnedPool::get().take(count * sizeof(T), &cap)) != nullptr) {
-      pinned = true;
-      return;
-    }
-    p = (T*)malloc(count * sizeof(T));
-    if (!p) throw std::bad_alloc();
-  }
-  void release() {
-    if (p) {
-      if (pinned) PinnedPool::get().give(p, cap);
-      else free(p);
-    }
-    p = nullptr;
-    n = 0;
-    cap = 0;
-    pinned = false;
-  }
-  T* data() const { return p; }
-  size_t size() const { return n; }
-  bool empty() const { return n == 0; }
-  T& operator[](size_t i) const { return p[i]; }
-};
-
-}  // namespace
-
-// Records of one device shard: FAIL / ERROR / SKIP pairs, rule-major and in
-// resource order (kv_rec_* kernels). Record of (rule, local res): base[rule] +
-// offs[rule][tile] + the record pairs before it in its tile (from the statuses).
-struct ResultPart {
-  std::shared_ptr<kv_batch> shard;  // the shard's batch (null: the result's own batch)
-  uint64_t lo = 0, n = 0;           // resources [lo, lo + n) of the result
-  uint32_t tiles = 0;
-  HostArray<uint32_t> offs;         // [rule][tile] exclusive record offsets within the rule (page-locked:
-                                    // C3's 38 MB crossed PCIe through a staging copy at ~1 GB/s)
-  std::vector<uint64_t> base;       // [rule + 1] record offsets of the rules
-  HostArray<ErrRec8> rec;           // compact records (with `uni`: only the rules that are not uniform)
-  HostArray<ErrRec> recw;           // full records, parallel to rec (only when some record is wide)
-  // Record codes (kv_rec_code_kernel): record i of a coded rule is its rule's table entry
-  // tab[rule * KV_REC_CODES + code[i]] (the lane field left out); a raw rule's records are
-  // rec[nbase[rule] ...). Empty `raw`: rec holds every record.
-  std::vector<uint8_t> raw;
-  std::vector<ErrRec8> tab;
-  HostArray<uint8_t> code;
-  std::vector<uint64_t> nbase;
-  // Status transfer form (kv_status_pack_kernel): the flags of the (rule, KV_RWG-status segment)s
-  // the pass wrote, their statuses at 4 bits (KV_RWG / 2 bytes a segment, rule-major), the first
-  // packed segment of each rule; the other segments are NOMATCH. Empty sflag: the part's statuses
-  // crossed as dense rows of kv_result::status.
-  HostArray<uint8_t> sflag, spack;
-  std::vector<uint64_t> sbase;
-  uint64_t nwg = 0;
-  // statuses [lo, lo + n) of rule `rule` from the transfer form into dst[0, n)
-  void unpack_row(uint32_t rule, uint8_t* dst) const {
-    if (!n || sbase.empty()) return;  // (a part without resources packs nothing)
-    const uint8_t* f = sflag.data() + (size_t)rule * nwg;
-    const uint8_t* src = spack.data() + sbase[rule] * (KV_RWG / 2);
-    const __m128i lo4 = _mm_set1_epi8(0x0F);
-    for (uint64_t g = 0; g < nwg; g++) {
-      const uint64_t q0 = g * KV_RWG, m = std::min<uint64_t>(KV_RWG, n - q0);
-      uint8_t* d = dst + q0;
-      if (!f[g]) {
-        memset(d, ST_NOMATCH, m);
-        continue;
-      }
-      uint64_t i = 0;
-      for (; i + 32 <= m; i += 32) {
-        const __m128i b = _mm_loadu_si128((const __m128i*)(src + i / 2));
-        const __m128i l = _mm_and_si128(b, lo4), h = _mm_and_si128(_mm_srli_epi16(b, 4), lo4);
-        _mm_storeu_si128((__m128i*)(d + i), _mm_unpacklo_epi8(l, h));
-        _mm_storeu_si128((__m128i*)(d + i + 16), _mm_unpackhi_epi8(l, h));
-      }
-      for (; i < m; i++) d[i] = (src[i / 2] >> (4 * (i & 1))) & 15u;
-      src += KV_RWG / 2;
-    }
-  }
-  uint64_t n_rec() const { return base.empty() ? 0 : base.back(); }
-  // record i of rule `rule` (base[rule] <= i < base[rule + 1])
-  ErrRec8 r8(uint32_t rule, uint64_t i) const {
-    if (raw.empty()) return rec[i];
-    return raw[rule] ? rec[nbase[rule] + (i - base[rule])] : tab[(size_t)rule * KV_REC_CODES + code[i]];
-  }
-};
-
-struct kv_result {
-  const kv_policyset* ps = nullptr;
-  const kv_batch* b = nullptr;
-  uint64_t n_rules = 0, n_res = 0;
-  // [rule][res] in the batch's store order (Batch::order), or in the caller's order with
-  // caller_order; `res` below is an index into it unless named a caller index.
-  // kv_result_status returns the caller order (status_c, a host permutation, when they differ).
-  HostArray<uint8_t> status;
-  std::once_flag sc_once;
-  HostArray<uint8_t> status_c;
-  // the parts hold their statuses in the transfer form (ResultPart::sflag) until an accessor
-  // materialises `status` (st_store) or the caller-order copy (status_caller)
-  bool sparse = false;
-  std::once_flag st_once;
-  // statuses and records were fetched in the caller's order (a permuted batch fetched whole:
-  // DevSession::fetch); `status` is then the caller order and `res` below a caller index
-  bool caller_order = false;
-  std::vector<ResultPart> parts;    // by resource range
-  bool errors = false;              // KV_MODE_ERRORS: records fetched
-  std::vector<int64_t> counts;
-  std::vector<int64_t> scope_counts;  // [scope][rule][KV_HIST] (KV_MODE_SCOPES)
-  double kernel_ms = 0;
-  uint32_t mode = 0;
-  // wall-clock phases of the kv_validate that made this result (kv_result_phase): upload, setup,
-  // pass, then the fetch's device work and copies, each ended by a stream synchronize
-  std::vector<std::pair<std::string, double>> phases;
-  // bulk failure export (kv_result_failures), built on first use
-  std::once_flag fail_once;
-  std::vector<uint32_t> f_rule, f_path;
-  std::vector<uint64_t> f_res;
-  std::vector<std::string> f_paths;
-
-  bool has_err() const { return errors; }
-  // store index of caller index `res`
-  uint64_t sidx(uint64_t res) const { return caller_order ? res : store_of(res); }
-  // the batch's store slot of caller index `res` (indexes the batch-side tables: dynamic leaves)
-  uint64_t store_of(uint64_t res) const {
-    const uint32_t* iv = const_cast<kv_batch*>(b)->inverse();
-    return iv ? iv[res] : res;
-  }
-  // caller index of status / record index `s`
-  uint64_t cidx(uint64_t s) const { return caller_order || b->b.order.empty() ? s : b->b.order[s]; }
-  bool has_status() const { return sparse || !status.empty(); }
-  static unsigned host_threads() { return std::max(1u, std::min<unsigned>(16u, std::thread::hardware_concurrency())); }
-  // out[c] = row[inv[c]] (a gather: sequential 8-byte stores, reads from a row that stays in the
-  // core's cache; 2.5x the rate of the scatter out[ord[q]] = row[q] on this host's cores)
-  static void gather_row(const uint8_t* row, const uint32_t* inv, uint64_t n, uint8_t* out) {
-    uint64_t c = 0;
-    for (; c + 8 <= n; c += 8) {
-      uint64_t v = 0;
-      for (int k = 0; k < 8; k++) v |= (uint64_t)row[inv[c + k]] << (8 * k);
-      memcpy(out + c, &v, 8);
-    }
-    for (; c < n; c++) out[c] = row[inv[c]];
-  }
-  // rows [rule][0, n_res) of dst from the parts' transfer form, rules split over host threads;
-  // with `inv` (caller index -> store index) each row is unpacked in store order and gathered
-  void unpack_rows(uint8_t* dst, const uint32_t* inv) const {
-    const unsigned T = host_threads();
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < T; t++)
-      th.emplace_back([&, t]() {
-        std::vector<uint8_t> tmp(inv ? n_res : 0);
-        for (uint64_t rl = t; rl < n_rules; rl += T) {
-          uint8_t* row = inv ? tmp.data() : dst + rl * n_res;
-          for (const ResultPart& p : parts) p.unpack_row((uint32_t)rl, row + p.lo);
-          if (inv) gather_row(row, inv, n_res, dst + rl * n_res);
-        }
-      });
-    for (auto& x : th) x.join();
-  }
-  // the status matrix in the records' order (store order unless caller_order), materialised from
-  // the transfer form on first use
-  const uint8_t* st_store() {
-    if (sparse)
-      std::call_once(st_once, [this]() {
-        status.alloc(n_rules * n_res);
-        unpack_rows(status.data(), nullptr);
-      });
-    return status.empty() ? nullptr : status.data();
-  }
-  // the statuses in caller order: rows of the store-order matrix gathered through the batch's
-  // inverse order, rules split over host threads (a permuted batch only); from the transfer form directly
-  // when the store-order matrix was not materialised
-  const uint8_t* status_caller() {
-    if (b->b.order.empty() || !has_status() || caller_order) return st_store();
-    std::call_once(sc_once, [this]() {
-      status_c.alloc(n_rules * n_res);
-      const uint32_t* inv = const_cast<kv_batch*>(b)->inverse();
-      if (status.empty()) {
-        unpack_rows(status_c.data(), inv);
-        return;
-      }
-      const unsigned T = host_threads();
-      std::vector<std::thread> th;
-      for (unsigned t = 0; t < T; t++)
-        th.emplace_back([&, t]() {
-          for (uint64_t rl = t; rl < n_rules; rl += T)
-            gather_row(status.data() + rl * n_res, inv, n_res, status_c.data() + rl * n_res);
-        });
-      for (auto& x : th) x.join();
-    });
-    return status_c.data();
-  }
-  const Batch& batch_of(const ResultPart& p) const { return p.shard ? p.shard->b : b->b; }
-  const ResultPart* part_of(uint64_t res) const {
-    for (const ResultPart& p : parts)
-      if (res >= p.lo && res < p.lo + p.n) return &p;
-    return nullptr;
-  }
-  static ErrRec decode(const ErrRec8& c) {
-    ErrRec e{};
-    e.kind_flags = (c.w0 & 15u) | (((c.w0 >> 4) & 3u) << 16);
-    e.pnode = c.w0 >> 7;
-    e.keynode = ABSENT;
-    e.resnode = ABSENT;
-    e.idx[0] = c.w1 & 1023u;
-    e.idx[1] = (c.w1 >> 10) & 255u;
-    e.idx[2] = (c.w1 >> 18) & 255u;
-    e.idx[3] = 0;
-    return e;
-  }
-  // record index of pair (rule, res) within its part
-  uint64_t rec_index(const ResultPart& p, uint32_t rule, uint64_t res) const {
-    const uint64_t local = res - p.lo;
-    const uint64_t tile = local / KV_WG;
-    uint64_t idx = p.base[rule] + p.offs[(size_t)rule * p.tiles + tile];
-    const uint8_t* row = const_cast<kv_result*>(this)->st_store() + (size_t)rule * n_res;
-    for (uint64_t q = p.lo + tile * KV_WG; q < res; q++) {
-      const uint8_t s = row[q];
-      idx += s == ST_FAIL || s == ST_ERROR || s == ST_SKIP;
-    }
-    return idx;
-  }
-  // error record of a FAIL / ERROR / SKIP pair, and the batch its node ids refer to
-  bool err(uint32_t rule, uint64_t res, ErrRec* e, const Batch** bt) const {
-    const ResultPart* p = part_of(res);
-    if (!p || !errors) return false;
-    const uint64_t i = rec_index(*p, rule, res);
-    if (i >= p->n_rec() || i < p->base[rule] || i >= p->base[rule + 1]) return false;
-    const ErrRec8 c = p->r8(rule, i);
-    *e = (c.w0 & ERR8_WIDE) && !p->recw.empty() ? p->recw[i] : decode(c);
-    *bt = &batch_of(*p);
-    return true;
-  }
-};
-
-namespace {
-
-int fail(kv_error** err, int code, const std::string& msg) {
-  if (err) {
-    *err = (kv_error*)malloc(sizeof(kv_error));
-    (*err)->code = code;
-    (*err)->message = strdup(msg.c_str());
-  }
-  return code;
-}
 
 DevPolicySet& dev_ps(kv_policyset* s, int device) {
   std::lock_guard<std::mutex> g(s->mu);
@@ -1237,186 +444,6 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
   bt->dev[device] = d;
   return d;
 }
-
-// Path segments from the pattern root to pnode p: keys (resolved wildcard keys
-// from the record's key node) and array indices (loop counters of the record).
-struct PathSeg {
-  bool index;
-  std::string key;
-};
-std::vector<PathSeg> path_segs(const PolicySet& ps, const Batch& b, const ErrRec& e, uint32_t p) {
-  std::vector<PathSeg> segs;
-  while (p != 0xFFFFFFFFu && p < ps.pnodes.size()) {
-    const PNodeInfo& n = ps.pnodes[p];
-    switch (n.seg) {
-      case SEG_ROOT: break;
-      case SEG_KEY: segs.push_back({false, n.key}); break;
-      case SEG_LOOP: segs.push_back({true, std::to_string(e.idx[n.level & 3])}); break;
-      case SEG_CONST_INDEX: segs.push_back({true, std::to_string(n.level)}); break;
-      case SEG_RESOLVED: {
-        if (e.keynode != ABSENT && e.keynode < b.n_cells()) {
-          uint32_t k = node_key(b.cell(e.keynode).kt);
-          segs.push_back({false, k < ps.keys.size() ? ps.keys[k] : b.dyn_keys[k - ps.keys.size()]});
-        } else {
-          segs.push_back({false, n.key});
-        }
-        break;
-      }
-    }
-    p = n.parent;
-  }
-  std::reverse(segs.begin(), segs.end());
-  return segs;
-}
-
-std::string join_path(const std::vector<PathSeg>& segs) {
-  std::string out = "/";
-  for (const PathSeg& s : segs) out += s.key + "/";
-  return out;
-}
-
-uint32_t err_kind(const ErrRec& e) { return e.kind_flags & 0xFFFF; }
-
-// pnode whose path is the PatternError path: the "*" shortcut reports its parent
-// map (anchor.go:139), every other form the node it was raised at
-uint32_t path_pnode(const PolicySet& ps, const ErrRec& e) {
-  if (err_kind(e) == E_STAR && e.pnode < ps.pnodes.size()) return ps.pnodes[e.pnode].parent;
-  return e.pnode;
-}
-
-std::string render_path(const PolicySet& ps, const Batch& b, const ErrRec& e) {
-  return join_path(path_segs(ps, b, e, path_pnode(ps, e)));
-}
-
-// ---- Go fmt of resource values (unstructured typing: int64 / float64 / string /
-// bool / nil / map[string]interface{} / []interface{}), for '%v' and %T operands
-std::string res_T(const JDoc& d, int64_t n) {
-  if (n < 0) return "<nil>";
-  switch (d.at((uint32_t)n).t) {
-    case J_MAP: return "map[string]interface {}";
-    case J_ARR: return "[]interface {}";
-    case J_STR: return "string";
-    case J_BOOL: return "bool";
-    case J_INT: return "int64";
-    case J_FLOAT: return "float64";
-    default: return "<nil>";
-  }
-}
-
-std::string res_v(const JDoc& d, int64_t n) {
-  if (n < 0) return "<nil>";
-  const JNode& x = d.at((uint32_t)n);
-  switch (x.t) {
-    case J_MAP: {  // fmt prints maps with sorted keys
-      std::vector<uint32_t> ix;
-      for (uint32_t c = x.first; c < x.first + x.count; c++) ix.push_back(c);
-      std::sort(ix.begin(), ix.end(), [&](uint32_t a, uint32_t b) { return d.key(d.at(a)) < d.key(d.at(b)); });
-      std::string o = "map[";
-      for (size_t k = 0; k < ix.size(); k++) {
-        if (k) o += ' ';
-        o += d.key(d.at(ix[k]));
-        o += ':';
-        o += res_v(d, ix[k]);
-      }
-      return o + "]";
-    }
-    case J_ARR: {
-      std::string o = "[";
-      for (uint32_t c = x.first; c < x.first + x.count; c++) {
-        if (c > x.first) o += ' ';
-        o += res_v(d, c);
-      }
-      return o + "]";
-    }
-    case J_STR: return std::string(d.sval(x));
-    case J_BOOL: return x.b ? "true" : "false";
-    case J_INT: return std::to_string(x.i);
-    case J_FLOAT: return go_format_g(x.f);
-    default: return "<nil>";
-  }
-}
-
-// resource element at a pattern path (-1 when absent)
-int64_t res_at(const JDoc& d, const std::vector<PathSeg>& segs) {
-  int64_t n = d.root;
-  for (const PathSeg& s : segs) {
-    if (n < 0) return -1;
-    const JNode& x = d.at((uint32_t)n);
-    if (x.t == J_MAP) {
-      n = d.get((uint32_t)n, s.key);
-    } else if (x.t == J_ARR && s.index) {
-      uint64_t i = std::stoull(s.key);
-      n = i < x.count ? (int64_t)(x.first + i) : -1;
-    } else {
-      return -1;
-    }
-  }
-  return n;
-}
-
-// err.Error() of the PatternError behind a FAIL / ERROR / SKIP record
-// (pkg/engine/validate/validate.go:62-172, pkg/engine/anchor/anchor.go:61-261;
-// condition / global anchor handlers wrap what propagates through them,
-// anchor.go:72-95 with common/anchorKey.go:21-40)
-std::string error_message(const PolicySet& ps, const Batch& b, const ErrRec& e, const JDoc& doc,
-                          const std::string* dyn_pat_v = nullptr) {
-  const uint32_t kind = err_kind(e);
-  if (e.pnode >= ps.pnodes.size()) return "";
-  PNodeInfo P = ps.pnodes[e.pnode];
-  if (P.dleaf >= 0 && dyn_pat_v) P.pat_v = *dyn_pat_v;  // the resource's substituted pattern value
-  const std::vector<PathSeg> segs = path_segs(ps, b, e, e.pnode);
-  const std::string path = join_path(segs);
-  std::string m;
-  switch (kind) {
-    case E_TYPE_MAP:
-      m = "pattern and resource have different structures. Path: " + path + ". Expected " + P.pat_t + ", found " +
-          res_T(doc, res_at(doc, segs));
-      break;
-    case E_TYPE_ARR:
-      m = "validation rule Failed at path " + path + ", resource does not satisfy the expected overlay pattern";
-      break;
-    case E_VALUE:
-      m = "resource value '" + res_v(doc, res_at(doc, segs)) + "' does not match '" + P.pat_v + "' at path " + path;
-      break;
-    case E_EMPTY_PATARR: m = "pattern Array empty"; break;
-    case E_LEN: {
-      int64_t n = res_at(doc, segs);
-      uint32_t rl = n >= 0 && doc.at((uint32_t)n).t == J_ARR ? doc.at((uint32_t)n).count : 0;
-      m = "validate Array failed, array length mismatch, resource Array len is " + std::to_string(rl) +
-          " and pattern Array len is " + std::to_string(P.pat_len);
-      break;
-    }
-    case E_NEG: m = path + "/" + (segs.empty() ? std::string() : segs.back().key) + " is not allowed"; break;
-    case E_STAR: {
-      std::vector<PathSeg> ps_ = segs;
-      std::string key = ps_.empty() ? std::string() : ps_.back().key;
-      if (!ps_.empty()) ps_.pop_back();
-      m = join_path(ps_) + "/" + key + " not found";
-      break;
-    }
-    case E_EXIST_PATLIST:
-      m = "invalid pattern type " + P.pat_t + ": Pattern has to be of list to compare against resource";
-      break;
-    case E_EXIST_PATMAP:
-      m = "invalid pattern type " + P.pat_t + ": Pattern has to be of type map to compare against items in resource";
-      break;
-    case E_EXIST_RESTYPE:
-      m = "invalid resource type " + res_T(doc, res_at(doc, segs)) +
-          ": Existence ^ () anchor can be used only on list/array type resource";
-      break;
-    case E_EXIST_FAIL: m = "existence anchor validation failed at path " + path; break;
-    default: return "";
-  }
-  for (uint32_t q = e.pnode; q != 0xFFFFFFFFu && q < ps.pnodes.size(); q = ps.pnodes[q].parent) {
-    if (ps.pnodes[q].wrap == 1) m = "conditional anchor mismatch: " + m;
-    else if (ps.pnodes[q].wrap == 2) m = "global anchor mismatch: " + m;
-  }
-  return m;
-}
-
-}  // namespace
-
-namespace {
 
 // A launch configuration on one device over one batch (a whole batch or a
 // shard): device-resident inputs and output buffers.
@@ -1971,7 +998,7 @@ struct DevSession {
     if (caller && !stc.p) {  // the gathered copy is a second status matrix: only with room to spare
       size_t fr = 0, tot = 0;
       if (hipMemGetInfo(&fr, &tot) != hipSuccess) caller = false;
-      fr += DevPool::get().held_on(device);  // (kept buffers are freed when an allocation needs them)
+      fr += dev_pool_held(device);  // (kept buffers are freed when an allocation needs them)
       if (fr < nrules * nres + nres * 8u + (512ull << 20)) caller = false;
     }
     if (caller) {
@@ -2352,7 +1379,7 @@ struct SessionSet {
   }
   void fetch(kv_result* out, double ms) {
     if (parts_mode) throw std::runtime_error("kv_session_fetch: a parts session keeps no host batch");
-    out->ps = ps;
+    out->ps = &ps->ps;
     out->b = bt;
     out->n_rules = nrules;
     out->n_res = nres;
@@ -2436,81 +1463,99 @@ struct kv_session {
   kv_session(kv_policyset* p, const char* ctx_json, uint32_t m, uint32_t n) : set(p, ctx_json, m, n) {}
 };
 
+namespace {
+
+// kv_validate / kv_validate_devices: one pass over the devices, fetched
+int validate_on(const kv_policyset* ps, const kv_batch* b, const char* ctx_json, const std::vector<int>& devices,
+                uint32_t mode, kv_result** out, kv_error** err) {
+  if (!ps || !b || !out) return fail(err, KV_E_INVALID, "null argument");
+  if (b->owner != ps) return fail(err, KV_E_INVALID, "batch was ingested for a different policy set");
+  auto r = std::make_unique<kv_result>();
+  run(const_cast<kv_policyset*>(ps), const_cast<kv_batch*>(b), ctx_json, devices, mode, r.get(), 0, 1, nullptr);
+  *out = r.release();
+  return 0;
+}
+
+// kv_session_create / kv_session_create_devices
+int session_on(const kv_policyset* ps, const kv_batch* b, const char* ctx_json, const std::vector<int>& devices,
+               uint32_t mode, kv_session** out, kv_error** err) {
+  if (!ps || !b || !out) return fail(err, KV_E_INVALID, "null argument");
+  if (b->owner != ps) return fail(err, KV_E_INVALID, "batch was ingested for a different policy set");
+  if (devices.empty()) return fail(err, KV_E_INVALID, "empty device mask");
+  *out = new kv_session(const_cast<kv_policyset*>(ps), const_cast<kv_batch*>(b), ctx_json, devices, mode);
+  return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int kv_compile(const char* policies_json, size_t len, uint32_t flags, kv_policyset** out, kv_error** err) {
   if (!policies_json || !out) return fail(err, KV_E_INVALID, "null argument");
-  try {
-    auto* s = new kv_policyset();
-    try {
-      compile_policies(policies_json, len, &s->ps, flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH));
-      if (flags & KV_COMPILE_SPECIALIZE) {
-        s->jit = std::make_unique<JitImage>();
-        const uint32_t chunk = jit_chunk_rules();
+  return guarded(KV_E_PARSE, err, [&]() -> int {
+    auto s = std::make_unique<kv_policyset>();
+    compile_policies(policies_json, len, &s->ps, flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH));
+    if (flags & KV_COMPILE_SPECIALIZE) {
+      s->jit = std::make_unique<JitImage>();
+      const uint32_t chunk = jit_chunk_rules();
+      jit_generate(s->ps, chunk, s->jit.get());
+      if (const char* dump = getenv("KVGPU_JIT_DUMP")) {
+        if (FILE* f = fopen(dump, "w")) {
+          fwrite(s->jit->source.data(), 1, s->jit->source.size(), f);
+          fclose(f);
+        }
+      }
+      if (!getenv("KVGPU_JIT_SKIP_COMPILE")) {  // (dump-only analysis runs skip it)
+        const std::string pkey = jit_plan_key(*s->jit);
+        const bool cached_plan = jit_load_plan(pkey, s->jit.get());
+        if (!cached_plan) jit_refine_blocks(s->ps, chunk, s->jit.get());  // block sizes from probe compiles
+        double ms = s->jit->compile_ms;
         jit_generate(s->ps, chunk, s->jit.get());
-        if (const char* dump = getenv("KVGPU_JIT_DUMP")) {
+        // register budget: re-plan kernels that spill until the compiled plan is the final one
+        // (the codes must belong to the last generated image: a plan still changing when the
+        // rounds run out is an error, never shipped nor cached)
+        bool settled = false;
+        for (int round = 0; round < 64 && !settled; round++) {
+          jit_compile(s->jit.get());
+          ms += s->jit->compile_ms;
+          settled = !jit_plan_spills(s->jit.get());
+          if (!settled) jit_generate(s->ps, chunk, s->jit.get());
+        }
+        if (!settled)
+          throw std::runtime_error("kvjit: the register plan did not settle (kernels still spill after 64 re-plans)");
+        const double c0 = s->jit->compile_ms;
+        jit_compile_variants(s->jit.get());  // (output-mode variants of the final kernels)
+        ms += s->jit->compile_ms - c0;
+        s->jit->compile_ms = ms;
+        jit_save_plan(pkey, *s->jit);
+        if (const char* dump = getenv("KVGPU_JIT_DUMP")) {  // (the source of the final plan)
           if (FILE* f = fopen(dump, "w")) {
             fwrite(s->jit->source.data(), 1, s->jit->source.size(), f);
             fclose(f);
           }
         }
-        if (!getenv("KVGPU_JIT_SKIP_COMPILE")) {  // (dump-only analysis runs skip it)
-          const std::string pkey = jit_plan_key(*s->jit);
-          const bool cached_plan = jit_load_plan(pkey, s->jit.get());
-          if (!cached_plan) jit_refine_blocks(s->ps, chunk, s->jit.get());  // block sizes from probe compiles
-          double ms = s->jit->compile_ms;
-          jit_generate(s->ps, chunk, s->jit.get());
-          // register budget: re-plan kernels that spill until the compiled plan is the final one
-          // (the codes must belong to the last generated image: a plan still changing when the
-          // rounds run out is an error, never shipped nor cached)
-          bool settled = false;
-          for (int round = 0; round < 64 && !settled; round++) {
-            jit_compile(s->jit.get());
-            ms += s->jit->compile_ms;
-            settled = !jit_plan_spills(s->jit.get());
-            if (!settled) jit_generate(s->ps, chunk, s->jit.get());
-          }
-          if (!settled)
-            throw std::runtime_error("kvjit: the register plan did not settle (kernels still spill after 64 re-plans)");
-          const double c0 = s->jit->compile_ms;
-          jit_compile_variants(s->jit.get());  // (output-mode variants of the final kernels)
-          ms += s->jit->compile_ms - c0;
-          s->jit->compile_ms = ms;
-          jit_save_plan(pkey, *s->jit);
-          if (const char* dump = getenv("KVGPU_JIT_DUMP")) {  // (the source of the final plan)
-            if (FILE* f = fopen(dump, "w")) {
-              fwrite(s->jit->source.data(), 1, s->jit->source.size(), f);
-              fclose(f);
-            }
-          }
-        }
-        if (const char* dump = getenv("KVGPU_JIT_DUMP_CO")) {  // gfx950 code objects (llvm-objdump / readelf)
-          for (size_t i = 0; i < s->jit->codes.size(); i++) {
-            if (FILE* f = fopen((std::string(dump) + "." + s->jit->kernel_name[i] + ".co").c_str(), "wb")) {
-              fwrite(s->jit->codes[i].data(), 1, s->jit->codes[i].size(), f);
-              fclose(f);
-            }
-          }
-          for (const JitImage::Variant& v : s->jit->variants)  // (output-mode variants: <name>.m<full>)
-            for (size_t i = 0; i < v.codes.size(); i++) {
-              if (v.codes[i].empty()) continue;
-              const std::string fn = std::string(dump) + "." + s->jit->kernel_name[i] + ".m" + std::to_string(v.full) + ".co";
-              if (FILE* f = fopen(fn.c_str(), "wb")) {
-                fwrite(v.codes[i].data(), 1, v.codes[i].size(), f);
-                fclose(f);
-              }
-            }
-        }
       }
-    } catch (...) {
-      delete s;
-      throw;
+      if (const char* dump = getenv("KVGPU_JIT_DUMP_CO")) {  // gfx950 code objects (llvm-objdump / readelf)
+        for (size_t i = 0; i < s->jit->codes.size(); i++) {
+          if (FILE* f = fopen((std::string(dump) + "." + s->jit->kernel_name[i] + ".co").c_str(), "wb")) {
+            fwrite(s->jit->codes[i].data(), 1, s->jit->codes[i].size(), f);
+            fclose(f);
+          }
+        }
+        for (const JitImage::Variant& v : s->jit->variants)  // (output-mode variants: <name>.m<full>)
+          for (size_t i = 0; i < v.codes.size(); i++) {
+            if (v.codes[i].empty()) continue;
+            const std::string fn = std::string(dump) + "." + s->jit->kernel_name[i] + ".m" + std::to_string(v.full) + ".co";
+            if (FILE* f = fopen(fn.c_str(), "wb")) {
+              fwrite(v.codes[i].data(), 1, v.codes[i].size(), f);
+              fclose(f);
+            }
+          }
+      }
     }
-    *out = s;
+    *out = s.release();
     return 0;
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_PARSE, e.what());
-  }
+  });
 }
 
 int kv_policyset_info(const kv_policyset* ps, uint32_t* n_policies, uint32_t* n_rules) {
@@ -2562,23 +1607,16 @@ int kv_rule_info_get(const kv_policyset* ps, uint32_t rule, kv_rule_info* out) {
 int kv_ingest(const kv_policyset* ps, const char* resources_json, size_t len, const char* ns_labels_json, kv_batch** out,
               kv_error** err) {
   if (!ps || !resources_json || !out) return fail(err, KV_E_INVALID, "null argument");
-  try {
-    auto* b = new kv_batch();
+  return guarded(KV_E_PARSE, err, [&]() -> int {
+    auto b = std::make_unique<kv_batch>();
     b->owner = ps;
-    try {
-      ingest_resources(ps->ps, resources_json, len, ns_labels_json, &b->b);
-    } catch (...) {
-      delete b;
-      throw;
-    }
+    ingest_resources(ps->ps, resources_json, len, ns_labels_json, &b->b);
     if (getenv("KVGPU_VERBOSE"))
       fprintf(stderr, "[kvgpu] ingest: %zu resources, %zu cells, %zu vals, %zu string bytes\n", b->b.res.size(),
               (size_t)b->b.cells_used, b->b.vals.size(), b->b.strs.size());
-    *out = b;
+    *out = b.release();
     return 0;
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_PARSE, e.what());
-  }
+  });
 }
 
 int kv_batch_info(const kv_batch* b, uint64_t* n_res, uint64_t* store_bytes) {
@@ -2596,125 +1634,23 @@ int kv_batch_transfer_bytes(const kv_batch* b, uint64_t* bytes) {
 
 int kv_validate(const kv_policyset* ps, const kv_batch* b, const char* ctx_json, int device, uint32_t mode,
                 kv_result** out, kv_error** err) {
-  if (!ps || !b || !out) return fail(err, KV_E_INVALID, "null argument");
-  if (b->owner != ps) return fail(err, KV_E_INVALID, "batch was ingested for a different policy set");
-  try {
-    auto* r = new kv_result();
-    try {
-      run(const_cast<kv_policyset*>(ps), const_cast<kv_batch*>(b), ctx_json, {device}, mode, r, 0, 1, nullptr);
-    } catch (...) {
-      delete r;
-      throw;
-    }
-    *out = r;
-    return 0;
-  } catch (const HipError& e) {
-    return fail(err, KV_E_DEVICE, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_PARSE, e.what());
-  }
+  return guarded(KV_E_PARSE, err, [&]() -> int { return validate_on(ps, b, ctx_json, {device}, mode, out, err); });
 }
 
 int kv_validate_devices(const kv_policyset* ps, const kv_batch* b, const char* ctx_json, uint32_t device_mask,
                         uint32_t mode, kv_result** out, kv_error** err) {
-  if (!ps || !b || !out) return fail(err, KV_E_INVALID, "null argument");
-  if (b->owner != ps) return fail(err, KV_E_INVALID, "batch was ingested for a different policy set");
-  try {
-    auto* r = new kv_result();
-    try {
-      run(const_cast<kv_policyset*>(ps), const_cast<kv_batch*>(b), ctx_json, mask_devices(device_mask), mode, r, 0, 1,
-          nullptr);
-    } catch (...) {
-      delete r;
-      throw;
-    }
-    *out = r;
-    return 0;
-  } catch (const HipError& e) {
-    return fail(err, KV_E_DEVICE, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_PARSE, e.what());
-  }
+  return guarded(KV_E_PARSE, err,
+                 [&]() -> int { return validate_on(ps, b, ctx_json, mask_devices(device_mask), mode, out, err); });
 }
 
 int kv_bench(const kv_policyset* ps, const kv_batch* b, const char* ctx_json, int device, uint32_t mode, int warmup,
              int iters, double* ms_per_iter, kv_error** err) {
   if (!ps || !b || !ms_per_iter) return fail(err, KV_E_INVALID, "null argument");
-  try {
+  return guarded(KV_E_PARSE, err, [&]() -> int {
     run(const_cast<kv_policyset*>(ps), const_cast<kv_batch*>(b), ctx_json, {device}, mode, nullptr, warmup, iters,
         ms_per_iter);
     return 0;
-  } catch (const HipError& e) {
-    return fail(err, KV_E_DEVICE, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_PARSE, e.what());
-  }
-}
-
-int kv_result_status(const kv_result* r, const uint8_t** status, uint64_t* n_rules, uint64_t* n_res) {
-  if (!r) return KV_E_INVALID;
-  if (status) {
-    try {
-      *status = const_cast<kv_result*>(r)->status_caller();
-    } catch (const std::exception&) {
-      return KV_E_NOMEM;
-    }
-  }
-  if (n_rules) *n_rules = r->n_rules;
-  if (n_res) *n_res = r->n_res;
-  return 0;
-}
-
-int kv_host_reserve(uint64_t bytes) {
-  try {
-    return PinnedStore::enabled() && PinnedPool::get().reserve(bytes) ? 0 : KV_E_DEVICE;
-  } catch (const std::exception&) {
-    return KV_E_DEVICE;
-  }
-}
-
-int kv_device_pool_limit(uint64_t bytes) {
-  DevPool& p = DevPool::get();
-  std::lock_guard<std::mutex> g(p.mu);
-  p.hold = (size_t)bytes;
-  return 0;
-}
-
-int kv_device_trim(int device) {
-  int n = 0, cur = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n || hipGetDevice(&cur) != hipSuccess) {
-    (void)hipGetLastError();
-    return KV_E_DEVICE;
-  }
-  if (hipSetDevice(device) != hipSuccess) {
-    (void)hipGetLastError();
-    return KV_E_DEVICE;
-  }
-  DevPool::get().trim(device);
-  (void)hipSetDevice(cur);
-  return 0;
-}
-
-int kv_result_phase(const kv_result* r, uint32_t i, const char** name, double* ms) {
-  if (!r) return KV_E_INVALID;
-  if (i >= r->phases.size()) return KV_E_RANGE;
-  if (name) *name = r->phases[i].first.c_str();
-  if (ms) *ms = r->phases[i].second;
-  return 0;
-}
-
-int kv_result_counts(const kv_result* r, const int64_t** counts) {
-  if (!r || !counts) return KV_E_INVALID;
-  *counts = r->counts.data();
-  return 0;
-}
-
-int kv_result_scope_counts(const kv_result* r, const int64_t** counts, uint32_t* n_scopes) {
-  if (!r || !counts) return KV_E_INVALID;
-  if (!(r->mode & KV_MODE_SCOPES)) return KV_E_INVALID;
-  *counts = r->scope_counts.data();
-  if (n_scopes) *n_scopes = (uint32_t)r->b->b.namespaces.size();
-  return 0;
+  });
 }
 
 int kv_batch_namespaces(const kv_batch* b, uint32_t* n) {
@@ -2728,304 +1664,9 @@ const char* kv_batch_namespace(const kv_batch* b, uint32_t i) {
   return b->b.namespaces[i].c_str();
 }
 
-int kv_result_path(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
-  if (!r || !r->has_err()) return KV_E_INVALID;
-  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
-  res = r->sidx(res);
-  size_t o = (size_t)rule * r->n_res + res;
-  if (const_cast<kv_result*>(r)->st_store()[o] != ST_FAIL) return KV_E_INVALID;
-  if (r->ps->ps.rules[rule].deny) return KV_E_INVALID;  // (a deny FAIL has no failing path, as a gated SKIP)
-  ErrRec e;
-  const Batch* bt = nullptr;
-  if (!r->err(rule, res, &e, &bt)) return KV_E_INVALID;
-  std::string p = render_path(r->ps->ps, *bt, e);
-  if (buf && cap) {
-    size_t n = std::min(cap - 1, p.size());
-    memcpy(buf, p.data(), n);
-    buf[n] = 0;
-  }
-  return (int)p.size();
-}
-
-int kv_result_error(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* kind, uint32_t* flags) {
-  if (!r || !r->has_err()) return KV_E_INVALID;
-  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
-  res = r->sidx(res);
-  const uint8_t st = const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res];
-  if (st != ST_FAIL && st != ST_ERROR && st != ST_SKIP) return KV_E_INVALID;
-  ErrRec e;
-  const Batch* bt = nullptr;
-  if (!r->err(rule, res, &e, &bt)) return KV_E_INVALID;
-  if (kind) *kind = e.kind_flags & 0xFFFF;
-  if (flags) *flags = e.kind_flags >> 16;
-  return 0;
-}
-
-namespace {
-// a message into the caller's buffer (truncated to cap - 1 bytes); returns its full length
-int put_message(const std::string& m, char* buf, size_t cap) {
-  if (buf && cap) {
-    size_t n = std::min(cap - 1, m.size());
-    memcpy(buf, m.data(), n);
-    buf[n] = 0;
-  }
-  return (int)m.size();
-}
-}  // namespace
-
-int kv_result_error_message(const kv_result* r, uint32_t rule, uint64_t res, const char* resource_json, size_t len,
-                            char* buf, size_t cap) {
-  if (!r || !r->has_err() || !resource_json) return KV_E_INVALID;
-  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
-  const uint64_t s = r->store_of(res);  // the batch's tables are in store order
-  res = r->sidx(res);  // the caller's document of its resource `res`, the record of its status slot
-  size_t o = (size_t)rule * r->n_res + res;
-  const uint8_t st = const_cast<kv_result*>(r)->st_store()[o];
-  if (st != ST_FAIL && st != ST_ERROR && st != ST_SKIP) return KV_E_INVALID;
-  std::string m;
-  try {
-    JDoc doc;
-    parse_json(resource_json, len, NUM_UNSTRUCTURED, &doc);
-    ErrRec e;
-    const Batch* bt = nullptr;
-    if (!r->err(rule, res, &e, &bt)) return KV_E_INVALID;
-    std::string pv;
-    const std::string* dyn_pv = nullptr;
-    if (e.pnode < r->ps->ps.pnodes.size() && r->ps->ps.pnodes[e.pnode].dleaf >= 0) {
-      const ResultPart* p = r->part_of(s);
-      kv_batch* kb = p->shard ? p->shard.get() : const_cast<kv_batch*>(r->b);
-      const DynHost& h = kb->dyn_host(r->ps->ps);
-      const uint64_t nl = kb->b.res.size(), local = s - p->lo;
-      const uint32_t o = h.dleaf[(size_t)r->ps->ps.pnodes[e.pnode].dleaf * nl + local];
-      pv = pattern_go_v(outcome_value(kb->b.vout_tab[o]));
-      dyn_pv = &pv;
-    }
-    m = error_message(r->ps->ps, *bt, e, doc, dyn_pv);
-  } catch (const std::exception&) {
-    return KV_E_PARSE;
-  }
-  if (m.empty()) return KV_E_INVALID;  // a compile-time constant status: no pattern error record
-  return put_message(m, buf, cap);
-}
-
-int kv_result_subst_error(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
-  if (!r) return KV_E_INVALID;
-  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
-  if (!r->has_status()) return KV_E_INVALID;  // counts-only result: no statuses were fetched
-  const uint64_t s = r->store_of(res);          // (the batch's tables are in store order)
-  res = r->sidx(res);
-  try {
-    const RuleRec& rr = r->ps->ps.rules[rule];
-    if (!rr.dyn || const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res] != ST_ERROR) return 0;
-    const ResultPart* p = r->part_of(s);
-    if (!p) return 0;
-    kv_batch* kb = p->shard ? p->shard.get() : const_cast<kv_batch*>(r->b);
-    const DynHost& h = kb->dyn_host(r->ps->ps);
-    const uint64_t nl = kb->b.res.size(), local = s - p->lo;
-    const size_t q = (size_t)(rr.dyn - 1) * nl + local;
-    if (h.dyn_st[q] != ST_ERROR) return 0;
-    // ruleError(rule, Validation, "variable substitution failed", err) (validation.go:186-188)
-    return put_message("variable substitution failed: " + kb->b.vout_tab[h.dyn_msg[q]].substr(1), buf, cap);
-  } catch (const std::exception&) {
-    return KV_E_INVALID;
-  }
-}
-
-int kv_result_precond_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
-  if (!r) return KV_E_INVALID;
-  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
-  if (!r->has_status()) return KV_E_INVALID;  // counts-only result: no statuses were fetched
-  const uint64_t s = r->store_of(res);          // (the batch's tables are in store order)
-  res = r->sidx(res);
-  try {
-    const RuleRec& rr = r->ps->ps.rules[rule];
-    if (!rr.pre || const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res] != ST_SKIP) return 0;
-    const ResultPart* p = r->part_of(s);
-    if (!p) return 0;
-    kv_batch* kb = p->shard ? p->shard.get() : const_cast<kv_batch*>(r->b);
-    const CondHost& h = kb->pre_host(r->ps->ps);
-    // the pair recomputed from the batch's tables: a SKIP of the pattern's condition anchors has
-    // another cause
-    if (pre_status_host(h, rr.pre - 1, kb->b.res.size(), s - p->lo) != ST_SKIP) return 0;
-    // ruleResponse(rule, Validation, "preconditions not met", RuleStatusSkip) (validation.go:183-184)
-    return put_message("preconditions not met", buf, cap);
-  } catch (const std::exception&) {
-    return KV_E_INVALID;
-  }
-}
-
-int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
-  if (!r) return KV_E_INVALID;
-  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
-  if (!r->has_status()) return KV_E_INVALID;  // counts-only result: no statuses were fetched
-  const uint64_t s = r->store_of(res);          // (the batch's tables are in store order)
-  res = r->sidx(res);
-  try {
-    const RuleRec& rr = r->ps->ps.rules[rule];
-    if (!rr.deny || r->ps->ps.rhost[rule].foreach_set) return 0;
-    if (const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res] != ST_ERROR) return 0;
-    const ResultPart* p = r->part_of(s);
-    if (!p) return 0;
-    const kv_batch* kb = p->shard ? p->shard.get() : r->b;
-    // the error recomputed from the batch's outcome rows: the first unresolved string of the block
-    const std::string e = deny_error_host(r->ps->ps, kb->b, rr.deny - 1, s - p->lo);
-    if (e.empty()) return 0;
-    // ruleError(rule, Validation, "failed to substitute variables in deny conditions", err)
-    // (validation.go:301-304)
-    return put_message("failed to substitute variables in deny conditions: " + e, buf, cap);
-  } catch (const std::bad_alloc&) {  // (the lazily built store-order status matrix)
-    return KV_E_NOMEM;
-  } catch (const std::exception&) {
-    return KV_E_INVALID;
-  }
-}
-
-int kv_policyset_deny_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings) {
-  if (!ps) return KV_E_INVALID;
-  if (sets) *sets = (uint32_t)ps->ps.dsets.size();
-  if (conditions) *conditions = (uint32_t)ps->ps.deny.conds.size();
-  if (strings) *strings = (uint32_t)ps->ps.deny.keys.size();
-  return 0;
-}
-
-int kv_batch_deny_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint64_t n) {
-  if (!ps || !b || !status) return KV_E_INVALID;
-  if (set >= ps->ps.dsets.size() || n != b->b.res.size()) return KV_E_RANGE;
-  try {
-    CondHost h;
-    build_deny(ps->ps, b->b, &h);
-    const std::vector<uint32_t>& order = b->b.order;  // store index -> caller index (empty: identity)
-    for (uint64_t s = 0; s < n; s++) status[order.empty() ? s : order[s]] = deny_status_host(h, set, n, s);
-    return 0;
-  } catch (const std::bad_alloc&) {
-    return KV_E_NOMEM;
-  } catch (const std::exception&) {
-    return KV_E_INVALID;
-  }
-}
-
-int kv_rule_deny_set(const kv_policyset* ps, uint32_t rule, uint32_t* set) {
-  if (!ps || !set) return KV_E_INVALID;
-  if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
-  *set = ps->ps.rhost[rule].foreach_set ? 0u : ps->ps.rules[rule].deny;
-  return 0;
-}
-
-// ------------------------------------------------------------------ foreach
-int kv_policyset_foreach_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* lists, uint32_t* conditions,
-                              uint32_t* strings) {
-  if (!ps) return KV_E_INVALID;
-  if (sets) *sets = (uint32_t)ps->ps.fsets.size();
-  if (lists) *lists = (uint32_t)ps->ps.flists.size();
-  if (conditions) *conditions = (uint32_t)ps->ps.elem.conds.size();
-  if (strings) *strings = (uint32_t)ps->ps.fkeys.size();
-  return 0;
-}
-
-int kv_rule_foreach_set(const kv_policyset* ps, uint32_t rule, uint32_t* set) {
-  if (!ps || !set) return KV_E_INVALID;
-  if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
-  *set = ps->ps.rhost[rule].foreach_set;
-  return 0;
-}
-
-int kv_batch_foreach_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint32_t* elem,
-                          uint64_t n) {
-  if (!ps || !b || !status) return KV_E_INVALID;
-  if (set >= ps->ps.fsets.size() || n != b->b.res.size()) return KV_E_RANGE;
-  try {
-    FeHost h;
-    build_foreach(ps->ps, b->b, &h);
-    const std::vector<uint32_t>& order = b->b.order;  // store index -> caller index (empty: identity)
-    for (uint64_t s = 0; s < n; s++) {
-      uint32_t e = 0xFFFFFFFFu;
-      const uint64_t i = order.empty() ? s : order[s];
-      status[i] = foreach_fold_host(h, set, n, s, &e);
-      if (elem) elem[i] = e;
-    }
-    return 0;
-  } catch (const std::bad_alloc&) {
-    return KV_E_NOMEM;
-  } catch (const std::exception&) {
-    return KV_E_INVALID;
-  }
-}
-
-namespace {
-// the host fold of a foreach rule's pair of a result: the batch (or shard) that holds store
-// resource s and the resource's index in it; false when the rule is not a device foreach rule
-bool fe_pair(const kv_result* r, uint32_t rule, uint64_t s, kv_batch** kb, uint64_t* local) {
-  if (!r->ps->ps.rhost[rule].foreach_set) return false;
-  const ResultPart* p = r->part_of(s);
-  if (!p) return false;
-  *kb = p->shard ? p->shard.get() : const_cast<kv_batch*>(r->b);
-  *local = s - p->lo;
-  return true;
-}
-}  // namespace
-
-int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* index) {
-  if (!r || !index) return KV_E_INVALID;
-  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
-  if (!r->has_status()) return KV_E_INVALID;
-  const uint64_t s = r->store_of(res);
-  res = r->sidx(res);
-  try {
-    *index = 0xFFFFFFFFu;
-    const uint8_t st = const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res];
-    if (st != ST_FAIL && st != ST_ERROR) return 0;  // (PASS, SKIP: no deciding element; CPU: not reported)
-    kv_batch* kb = nullptr;
-    uint64_t local = 0;
-    if (!fe_pair(r, rule, s, &kb, &local)) return 0;
-    const PolicySet& ps = r->ps->ps;
-    uint32_t e = 0xFFFFFFFFu;
-    if (foreach_fold_host(kb->fe_host(ps), ps.rhost[rule].foreach_set - 1, kb->b.res.size(), local, &e) == st) *index = e;
-    return 0;
-  } catch (const std::bad_alloc&) {
-    return KV_E_NOMEM;
-  } catch (const std::exception&) {
-    return KV_E_INVALID;
-  }
-}
-
-int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
-  if (!r) return KV_E_INVALID;
-  if (rule >= r->n_rules || res >= r->n_res) return KV_E_RANGE;
-  if (!r->has_status()) return KV_E_INVALID;
-  const uint64_t s = r->store_of(res);
-  res = r->sidx(res);
-  try {
-    const uint8_t st = const_cast<kv_result*>(r)->st_store()[(size_t)rule * r->n_res + res];
-    if (st != ST_ERROR && st != ST_SKIP) return 0;
-    kv_batch* kb = nullptr;
-    uint64_t local = 0;
-    if (!fe_pair(r, rule, s, &kb, &local)) return 0;
-    const PolicySet& ps = r->ps->ps;
-    const uint32_t set = ps.rhost[rule].foreach_set - 1;
-    const FeHost& h = kb->fe_host(ps);
-    uint32_t e = 0xFFFFFFFFu;
-    // the pair recomputed from the batch's tables: a SKIP of the rule's own preconditions has
-    // another cause (kv_result_precond_message)
-    if (foreach_fold_host(h, set, kb->b.res.size(), local, &e) != st) return 0;
-    if (st == ST_SKIP) {
-      const RuleRec& rr = ps.rules[rule];
-      if (rr.pre && pre_status_host(kb->pre_host(ps), rr.pre - 1, kb->b.res.size(), local) == ST_SKIP) return 0;
-      return put_message("rule skipped", buf, cap);  // (validation.go:279-281)
-    }
-    const std::string err = foreach_error_host(ps, kb->b, h, set, local, e);
-    if (err.empty()) return 0;
-    return put_message("validation failed in foreach rule for failed to substitute variables in deny conditions: " + err,
-                       buf, cap);
-  } catch (const std::bad_alloc&) {
-    return KV_E_NOMEM;
-  } catch (const std::exception&) {
-    return KV_E_INVALID;
-  }
-}
-
 int kv_condition_eval(const char* condition_json, size_t len, int* result) {
   if (!condition_json || !result) return KV_E_INVALID;
-  try {
+  return guarded(KV_E_PARSE, nullptr, [&]() -> int {
     JDoc d;
     parse_json(condition_json, len, NUM_FLOAT, &d);
     if (d.at(d.root).t != J_MAP) return KV_E_PARSE;
@@ -3041,198 +1682,36 @@ int kv_condition_eval(const char* condition_json, size_t len, int* result) {
     if (range) return KV_E_RANGE;
     *result = v ? 1 : 0;
     return 0;
-  } catch (const std::exception&) {
-    return KV_E_PARSE;
-  }
-}
-
-int kv_policyset_cond_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings) {
-  if (!ps) return KV_E_INVALID;
-  if (sets) *sets = (uint32_t)ps->ps.csets.size();
-  if (conditions) *conditions = (uint32_t)ps->ps.gate.conds.size();
-  if (strings) *strings = (uint32_t)ps->ps.gate.keys.size();
-  return 0;
-}
-
-double kv_result_kernel_ms(const kv_result* r) { return r ? r->kernel_ms : -1.0; }
-
-int kv_result_failures(const kv_result* cr, uint64_t* n, const uint32_t** rule, const uint64_t** res,
-                       const uint32_t** path_id) {
-  if (!cr || !cr->has_err() || !n) return KV_E_INVALID;
-  kv_result* r = const_cast<kv_result*>(cr);
-  try {
-    std::call_once(r->fail_once, [r]() {
-      // one pass over the statuses: records come rule-major, in resource order per part
-      std::unordered_map<uint64_t, uint32_t> compact;      // (path pnode, packed indices) -> path id
-      std::unordered_map<std::string, uint32_t> rendered;  // wide records: by rendered path
-      const PolicySet& ps = r->ps->ps;
-      const uint8_t* stm = r->st_store();
-      for (uint32_t rl = 0; rl < r->n_rules; rl++) {
-        const uint8_t* row = stm + (size_t)rl * r->n_res;
-        for (const ResultPart& p : r->parts) {
-          uint64_t i = p.base[rl];
-          for (uint64_t q = p.lo; q < p.lo + p.n; q++) {
-            const uint8_t st = row[q];
-            if (st != ST_FAIL && st != ST_ERROR && st != ST_SKIP) continue;
-            uint32_t id = KV_PATH_NONE;
-            if (st == ST_FAIL && !ps.rules[rl].deny) {  // (a deny FAIL has an empty record: no failing path)
-              const ErrRec8 c = p.r8(rl, i);
-              if ((c.w0 & ERR8_WIDE) && !p.recw.empty()) {
-                const std::string path = render_path(ps, r->batch_of(p), p.recw[i]);
-                auto it = rendered.find(path);
-                if (it == rendered.end()) {
-                  it = rendered.emplace(path, (uint32_t)r->f_paths.size()).first;
-                  r->f_paths.push_back(path);
-                }
-                id = it->second;
-              } else {
-                const ErrRec e = kv_result::decode(c);
-                const uint64_t key = (uint64_t)path_pnode(ps, e) << 32 | (c.w1 & ERR8_IDX_MASK);
-                auto it = compact.find(key);
-                if (it == compact.end()) {
-                  const std::string path = render_path(ps, r->batch_of(p), e);
-                  auto jt = rendered.find(path);
-                  if (jt == rendered.end()) {
-                    jt = rendered.emplace(path, (uint32_t)r->f_paths.size()).first;
-                    r->f_paths.push_back(path);
-                  }
-                  it = compact.emplace(key, jt->second).first;
-                }
-                id = it->second;
-              }
-            }
-            r->f_rule.push_back(rl);
-            r->f_res.push_back(r->cidx(q));
-            r->f_path.push_back(id);
-            i++;
-          }
-        }
-      }
-      if (!r->b->b.order.empty() && !r->caller_order) {
-        // caller order: by rule, then caller resource index. Each rule's pairs are a subset of
-        // [0, n_res) with distinct caller indices: a rule with pairs on 1/16 of the resources or more
-        // is scattered into a per-thread slot array and swept in order, a sparser one sorted
-        // (rules split over host threads)
-        std::vector<size_t> rb(r->n_rules + 1, 0);
-        for (size_t i = 0; i < r->f_rule.size(); i++) rb[r->f_rule[i] + 1]++;
-        for (uint32_t rl = 0; rl < r->n_rules; rl++) rb[rl + 1] += rb[rl];
-        std::vector<uint64_t> fs(r->f_res.size());
-        std::vector<uint32_t> fp(r->f_path.size());
-        const unsigned T = std::max(1u, std::min<unsigned>(16u, std::thread::hardware_concurrency()));
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < T; t++)
-          th.emplace_back([&, t]() {
-            // caller index -> path id + 1 (0: no pair; 64-bit: KV_PATH_NONE + 1 of an ERROR / SKIP
-            // pair must not wrap to "no pair")
-            std::vector<uint64_t> slot;
-            for (uint32_t rl = t; rl < r->n_rules; rl += T) {
-              if (rb[rl] == rb[rl + 1]) continue;
-              if ((rb[rl + 1] - rb[rl]) * 16u < r->n_res) {
-                std::vector<std::pair<uint64_t, uint32_t>> v;
-                v.reserve(rb[rl + 1] - rb[rl]);
-                for (size_t i = rb[rl]; i < rb[rl + 1]; i++) v.push_back({r->f_res[i], r->f_path[i]});
-                std::sort(v.begin(), v.end());
-                for (size_t i = 0; i < v.size(); i++) {
-                  fs[rb[rl] + i] = v[i].first;
-                  fp[rb[rl] + i] = v[i].second;
-                }
-                continue;
-              }
-              if (slot.empty()) slot.assign(r->n_res, 0ull);
-              for (size_t i = rb[rl]; i < rb[rl + 1]; i++) slot[r->f_res[i]] = (uint64_t)r->f_path[i] + 1ull;
-              size_t o = rb[rl];
-              for (uint64_t j = 0; j < r->n_res && o < rb[rl + 1]; j++)
-                if (slot[j]) {
-                  fs[o] = j;
-                  fp[o++] = (uint32_t)(slot[j] - 1ull);
-                  slot[j] = 0ull;
-                }
-            }
-          });
-        for (auto& x : th) x.join();
-        r->f_res.swap(fs);
-        r->f_path.swap(fp);
-        // path ids numbered by first appearance in the returned order
-        std::vector<uint32_t> renum(r->f_paths.size(), KV_PATH_NONE);
-        std::vector<std::string> paths;
-        for (uint32_t& id : r->f_path) {
-          if (id == KV_PATH_NONE) continue;
-          if (renum[id] == KV_PATH_NONE) {
-            renum[id] = (uint32_t)paths.size();
-            paths.push_back(std::move(r->f_paths[id]));
-          }
-          id = renum[id];
-        }
-        r->f_paths.swap(paths);
-      }
-    });
-  } catch (const std::exception&) {
-    return KV_E_NOMEM;
-  }
-  *n = r->f_rule.size();
-  if (rule) *rule = r->f_rule.data();
-  if (res) *res = r->f_res.data();
-  if (path_id) *path_id = r->f_path.data();
-  return 0;
-}
-
-const char* kv_path_string(const kv_result* r, uint32_t path_id) {
-  if (!r || path_id >= r->f_paths.size()) return nullptr;
-  return r->f_paths[path_id].c_str();
+  });
 }
 
 int kv_session_create(const kv_policyset* ps, const kv_batch* b, const char* ctx_json, int device, uint32_t mode,
                       kv_session** out, kv_error** err) {
-  if (!ps || !b || !out) return fail(err, KV_E_INVALID, "null argument");
-  if (b->owner != ps) return fail(err, KV_E_INVALID, "batch was ingested for a different policy set");
-  try {
-    *out = new kv_session(const_cast<kv_policyset*>(ps), const_cast<kv_batch*>(b), ctx_json, {device}, mode);
-    return 0;
-  } catch (const HipError& e) {
-    return fail(err, KV_E_DEVICE, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_PARSE, e.what());
-  }
+  return guarded(KV_E_PARSE, err, [&]() -> int { return session_on(ps, b, ctx_json, {device}, mode, out, err); });
 }
 
 int kv_session_create_devices(const kv_policyset* ps, const kv_batch* b, const char* ctx_json, uint32_t device_mask,
                               uint32_t mode, kv_session** out, kv_error** err) {
-  if (!ps || !b || !out) return fail(err, KV_E_INVALID, "null argument");
-  if (b->owner != ps) return fail(err, KV_E_INVALID, "batch was ingested for a different policy set");
-  try {
-    const std::vector<int> devs = mask_devices(device_mask);
-    if (devs.empty()) return fail(err, KV_E_INVALID, "empty device mask");
-    *out = new kv_session(const_cast<kv_policyset*>(ps), const_cast<kv_batch*>(b), ctx_json, devs, mode);
-    return 0;
-  } catch (const HipError& e) {
-    return fail(err, KV_E_DEVICE, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_PARSE, e.what());
-  }
+  return guarded(KV_E_PARSE, err,
+                 [&]() -> int { return session_on(ps, b, ctx_json, mask_devices(device_mask), mode, out, err); });
 }
 
 int kv_session_create_parts(const kv_policyset* ps, const char* ctx_json, uint32_t mode, uint32_t n_parts,
                             kv_session** out, kv_error** err) {
   if (!ps || !out || n_parts == 0) return fail(err, KV_E_INVALID, "bad argument");
-  try {
+  return guarded(KV_E_PARSE, err, [&]() -> int {
     *out = new kv_session(const_cast<kv_policyset*>(ps), ctx_json, mode, n_parts);
     return 0;
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_PARSE, e.what());
-  }
+  });
 }
 
 int kv_session_attach_part(kv_session* s, uint32_t part, const kv_batch* b, int device, kv_error** err) {
   if (!s || !b) return fail(err, KV_E_INVALID, "null argument");
   if (b->owner != s->set.ps) return fail(err, KV_E_INVALID, "batch was ingested for a different policy set");
-  try {
+  return guarded(KV_E_INVALID, err, [&]() -> int {
     s->set.attach(part, const_cast<kv_batch*>(b), device);
     return 0;
-  } catch (const HipError& e) {
-    return fail(err, KV_E_DEVICE, e.what());
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_INVALID, e.what());
-  }
+  });
 }
 
 int kv_session_scopes(const kv_session* s, uint32_t* n_scopes) {
@@ -3260,15 +1739,13 @@ int kv_session_rccl_ranks(const kv_session* s, int* ranks) {
 
 int kv_session_status_bytes(kv_session* s, uint64_t* bytes) {
   if (!s || !bytes) return KV_E_INVALID;
-  try {
+  return guarded(KV_E_DEVICE, nullptr, [&]() -> int {
     uint64_t t = 0;
     for (auto& p : s->set.parts)
       if (p) t += p->written_status_bytes();
     *bytes = t;
     return 0;
-  } catch (const std::exception&) {
-    return KV_E_DEVICE;
-  }
+  });
 }
 
 int kv_session_part_ms(const kv_session* s, double* ms) {
@@ -3285,52 +1762,39 @@ int kv_session_parts(const kv_session* s, uint32_t* n_parts) {
 
 int kv_session_fetch(kv_session* s, kv_result** out, kv_error** err) {
   if (!s || !out) return fail(err, KV_E_INVALID, "null argument");
-  try {
-    auto* r = new kv_result();
-    try {
-      s->set.fetch(r, 0.0);
-    } catch (...) {
-      delete r;
-      throw;
-    }
-    *out = r;
+  return guarded(KV_E_DEVICE, err, [&]() -> int {
+    auto r = std::make_unique<kv_result>();
+    s->set.fetch(r.get(), 0.0);
+    *out = r.release();
     return 0;
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_DEVICE, e.what());
-  }
+  });
 }
 
 int kv_session_run(kv_session* s, int iters, double* event_ms, kv_error** err) {
   if (!s || iters < 0) return fail(err, KV_E_INVALID, "bad argument");
-  try {
+  return guarded(KV_E_DEVICE, err, [&]() -> int {
     double t = s->set.run(iters);
     if (event_ms) *event_ms = t;
     return 0;
-  } catch (const std::exception& e) {
-    return fail(err, KV_E_DEVICE, e.what());
-  }
+  });
 }
 
 int kv_session_counts(kv_session* s, int64_t* counts) {
   if (!s || !counts) return KV_E_INVALID;
-  try {
+  return guarded(KV_E_DEVICE, nullptr, [&]() -> int {
     s->set.reduce();
     std::copy(s->set.counts_.begin(), s->set.counts_.end(), counts);
     return 0;
-  } catch (const std::exception&) {
-    return KV_E_DEVICE;
-  }
+  });
 }
 
 int kv_session_scope_counts(kv_session* s, int64_t* counts) {
   if (!s || !counts || !(s->set.mode & KV_MODE_SCOPES)) return KV_E_INVALID;
-  try {
+  return guarded(KV_E_DEVICE, nullptr, [&]() -> int {
     s->set.reduce();
     std::copy(s->set.scope_counts_.begin(), s->set.scope_counts_.end(), counts);
     return 0;
-  } catch (const std::exception&) {
-    return KV_E_DEVICE;
-  }
+  });
 }
 
 void kv_free_session(kv_session* s) { delete s; }

@@ -57,4 +57,7 @@ KV_HD inline Node cell_widen(uint32_t kt, uint32_t hi, uint64_t row, const Val* 
   return Node{kt, 0u, 0u, 0u};
 }
 
+// Transfer form of a coded rule's records (kvdev.h launch_rec_codes): distinct records per rule
+constexpr uint32_t KV_REC_CODES = 256;
+
 }  // namespace kv

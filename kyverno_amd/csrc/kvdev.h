@@ -71,8 +71,7 @@ hipError_t launch_rec_compact(const uint8_t* status, const ErrRec8* err8, const 
 // Record codes of a compacted record array (rule-major, rule r at [base[r], base[r + 1])): phase 0
 // writes each record's slot in its rule's table of KV_REC_CODES distinct records (tkey, keys w0 << 32
 // | w1 without the lane, preset ~0) as a 1-byte code, and flags raw[rule] (preset 0) when the table
-// fills up; phase 1 copies the raw rules' records to out[nbase[rule] ...)
-constexpr uint32_t KV_REC_CODES = 256;
+// fills up; phase 1 copies the raw rules' records to out[nbase[rule] ...) (KV_REC_CODES: kvcell.h)
 hipError_t launch_rec_codes(const ErrRec8* rec, const unsigned long long* base, uint32_t n_rules,
                             unsigned long long* tkey, uint8_t* code, uint32_t* raw, const unsigned long long* nbase,
                             ErrRec8* out, int phase, hipStream_t stream);

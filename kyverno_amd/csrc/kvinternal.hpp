@@ -266,7 +266,7 @@ struct PolicySet {
 // objects (flags: kv_compile's KV_COMPILE_DENY | KV_COMPILE_FOREACH). Throws std::runtime_error on malformed input.
 void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flags = 0);
 
-// Host memory of the large store arrays of an ingested batch. libkvgpu (kvapi.cpp)
+// Host memory of the large store arrays of an ingested batch. libkvgpu (kvmem.cpp)
 // installs a pooled page-locked allocator, so the store's H2D upload is one direct
 // DMA instead of a copy through a staging ring; without it (host-only builds) plain
 // malloc. `take` returns nullptr to fall back; `give` returns false for a block it
