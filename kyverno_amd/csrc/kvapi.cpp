@@ -1497,61 +1497,7 @@ int kv_compile(const char* policies_json, size_t len, uint32_t flags, kv_policys
     compile_policies(policies_json, len, &s->ps, flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH));
     if (flags & KV_COMPILE_SPECIALIZE) {
       s->jit = std::make_unique<JitImage>();
-      const uint32_t chunk = jit_chunk_rules();
-      jit_generate(s->ps, chunk, s->jit.get());
-      if (const char* dump = getenv("KVGPU_JIT_DUMP")) {
-        if (FILE* f = fopen(dump, "w")) {
-          fwrite(s->jit->source.data(), 1, s->jit->source.size(), f);
-          fclose(f);
-        }
-      }
-      if (!getenv("KVGPU_JIT_SKIP_COMPILE")) {  // (dump-only analysis runs skip it)
-        const std::string pkey = jit_plan_key(*s->jit);
-        const bool cached_plan = jit_load_plan(pkey, s->jit.get());
-        if (!cached_plan) jit_refine_blocks(s->ps, chunk, s->jit.get());  // block sizes from probe compiles
-        double ms = s->jit->compile_ms;
-        jit_generate(s->ps, chunk, s->jit.get());
-        // register budget: re-plan kernels that spill until the compiled plan is the final one
-        // (the codes must belong to the last generated image: a plan still changing when the
-        // rounds run out is an error, never shipped nor cached)
-        bool settled = false;
-        for (int round = 0; round < 64 && !settled; round++) {
-          jit_compile(s->jit.get());
-          ms += s->jit->compile_ms;
-          settled = !jit_plan_spills(s->jit.get());
-          if (!settled) jit_generate(s->ps, chunk, s->jit.get());
-        }
-        if (!settled)
-          throw std::runtime_error("kvjit: the register plan did not settle (kernels still spill after 64 re-plans)");
-        const double c0 = s->jit->compile_ms;
-        jit_compile_variants(s->jit.get());  // (output-mode variants of the final kernels)
-        ms += s->jit->compile_ms - c0;
-        s->jit->compile_ms = ms;
-        jit_save_plan(pkey, *s->jit);
-        if (const char* dump = getenv("KVGPU_JIT_DUMP")) {  // (the source of the final plan)
-          if (FILE* f = fopen(dump, "w")) {
-            fwrite(s->jit->source.data(), 1, s->jit->source.size(), f);
-            fclose(f);
-          }
-        }
-      }
-      if (const char* dump = getenv("KVGPU_JIT_DUMP_CO")) {  // gfx950 code objects (llvm-objdump / readelf)
-        for (size_t i = 0; i < s->jit->codes.size(); i++) {
-          if (FILE* f = fopen((std::string(dump) + "." + s->jit->kernel_name[i] + ".co").c_str(), "wb")) {
-            fwrite(s->jit->codes[i].data(), 1, s->jit->codes[i].size(), f);
-            fclose(f);
-          }
-        }
-        for (const JitImage::Variant& v : s->jit->variants)  // (output-mode variants: <name>.m<full>)
-          for (size_t i = 0; i < v.codes.size(); i++) {
-            if (v.codes[i].empty()) continue;
-            const std::string fn = std::string(dump) + "." + s->jit->kernel_name[i] + ".m" + std::to_string(v.full) + ".co";
-            if (FILE* f = fopen(fn.c_str(), "wb")) {
-              fwrite(v.codes[i].data(), 1, v.codes[i].size(), f);
-              fclose(f);
-            }
-          }
-      }
+      jit_build(s->ps, s->jit.get());  // (kvjitbuild.cpp: generate, plan, compile, variants)
     }
     *out = s.release();
     return 0;

@@ -1,10 +1,10 @@
 // Path columns (kvdevtypes.h ColDesc / ColFam): built once per batch and device from the node
-// rows, read by the specialized kernels in place of their row walks (kvjit.cpp hoist). Device
+// rows, read by the specialized kernels in place of their row walks (kvjitgen.cpp hoist). Device
 // functions over the kvdevfn.h helpers: the kv_pcol_* kernels (kvkernel.hip) and the host
 // emulator (tools/kvemu/mtab.cpp) run these bodies. Include after kvdevfn.h.
 //
 // A column cell is what the specialized kernels' row walk leaves in its hoisted node
-// (kvjit.cpp hoist): the node at the path, or all zero when a step finds no node (a missing
+// (kvjitgen.cpp hoist): the node at the path, or all zero when a step finds no node (a missing
 // key, a non-map parent, a slot past the map's slots); the present cells carry
 // KV_COL_PRESENT in kt (their key is dropped: the walk never reads a hoisted node's key) and
 // in c the node's own index when it is a map (the cursor of a wildcard-key lookup) or the

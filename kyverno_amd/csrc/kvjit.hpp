@@ -32,12 +32,10 @@ struct JitKernelPlan {
 
 struct JitImage {
   std::vector<JitKernelPlan> plan;     // kernel grouping (empty: default groups; kept across re-plans)
-  std::vector<uint32_t> kernel_scratch;  // private segment bytes per lane of each planned kernel
   std::string source;       // generated HIP source, all of it (diagnostics, tools/kvemu)
   std::string common;       // prelude + helper functions shared by the kernels
   std::vector<std::string> kernel_name, kernel_src;  // one hiprtc program per kernel: common + kernel_src[i]
   std::vector<std::vector<char>> codes;              // gfx950 code object per kernel program
-  uint32_t cache_hits = 0;  // programs loaded from the code-object cache
   std::vector<JitChunk> chunks;
   // leaf predicates memoized per distinct scalar value: slot k = memo_preds[k];
   // kernel "kvj_ptab" fills DevPS::ptab (memo_words words per value)
@@ -45,12 +43,12 @@ struct JitImage {
   uint32_t memo_words = 0;
   uint32_t ptab_row = 1;    // predicates per kvj_ptab grid row (one row: every predicate of a value)
   // match bits per tuple (kv_mtup_kernel, DevPS::mtup): words of 32 rules in kernel order,
-  // from the factored-match descriptors (DevPS::fac_*, kvjit.cpp build_fac)
+  // from the factored-match descriptors (DevPS::fac_*, kvjitgen.cpp build_fac)
   uint32_t mtup_words = 0;
   std::vector<uint32_t> fac_word, fac_bit, fac_flist, fac_rule;
   uint32_t fac_slots = 0;
   // per rule: 1 = its records are appended to its wave's 64-slot segment (lane in the record),
-  // 0 = at the resource's slot (members of large rule groups, kvjit.cpp gslot_members; members of
+  // 0 = at the resource's slot (members of large rule groups, kvjitgen.cpp kGslotMembers; members of
   // groups with site records, expanded there at fetch)
   std::vector<uint8_t> rec_compact;
   // site-record groups (kvdevtypes.h GSiteDesc): 4 words per group, (rule, node shift) per member,
@@ -65,7 +63,7 @@ struct JitImage {
   // formats: kvdevtypes.h ColFmt; KVGPU_JIT_NARROW=0 at generation: every column wide)
   std::vector<uint32_t> fam_nw, fam_nb, fam_nn;
   // what the kernels read of each column ("<family array path>|<relative path>" -> use bits,
-  // kvjit.cpp Gen::ColUse): the formats follow from the uses of every rule of the policy set, so
+  // kvjitgen.cpp Gen::ColUse): the formats follow from the uses of every rule of the policy set, so
   // an image that generates only some rules (a block probe) is seeded with the whole image's
   std::map<std::string, uint32_t> col_use;
   bool probe = false;      // a block-probe image (jit_refine_blocks): rule kernels only
@@ -81,45 +79,48 @@ struct JitImage {
   std::vector<Variant> variants;
 };
 
-// Generate the specialized source for every rule of `ps` (chunks of at most
-// `chunk_rules` rules per kernel).
+// ---- kvjitgen.cpp
 // most rules per kernel (one fused block): KVGPU_JIT_CHUNK, default 128
 uint32_t jit_chunk_rules();
 // diagnostics (KVGPU_JIT_STAMPS): stamps per wave of the rule kernels' segment boundaries
 constexpr uint32_t kJitStamps = 16;
+// Generate the specialized source for every rule of `ps` (kernels of at most `chunk_rules` rules).
 void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out);
-// Compile every kernel program with hiprtc for gfx950, on parallel host threads
-// (KVGPU_JIT_THREADS, default: hardware threads), through the code-object cache
-// (KVGPU_JIT_CACHE directory, default $XDG_CACHE_HOME/kvgpu or ~/.cache/kvgpu;
-// "0" disables; entries keyed by a hash of compiler options + program text).
-// Throws std::runtime_error with the log on failure.
-void jit_compile(JitImage* img);
+
+// ---- kvjitbuild.cpp
+// The whole build of a policy set's kernels into a fresh `img`: generate, the plan (from the plan
+// cache, or block sizes from probe compiles), compile / re-plan rounds until every kernel meets the
+// register rules, the output-mode variants, the plan cache entry; img->compile_ms: every compile on
+// the way. KVGPU_JIT_DUMP / _DUMP_CO: the source / the code objects to files; _SKIP_COMPILE: no compile.
+void jit_build(const PolicySet& ps, JitImage* img);
 uint64_t code_bytes(const JitImage& img);
-// Register budget of the plan: no kernel ships with a private (scratch) segment, and a wave
-// bound is kept only when the compiler met it. A multi-block kernel that spills (or exceeds the
-// registers) under a bound of w > 6 waves per SIMD is recompiled at w - 1; otherwise its
-// largest block is split in two; a kernel of one-rule blocks is compiled at w - 1, then
-// without a bound (a one-rule kernel that still spills: std::runtime_error).
-// Returns true when the plan changed (regenerate + compile again; the kernels that did not
-// change come from the code-object cache).
-bool jit_plan_spills(JitImage* img);
-// The output-mode variants of the final plan (JitImage::variants): FULL (status + records, DevOut::
-// full 3) and SCOPES-only (per-scope counts, 8); through the code-object cache.
-void jit_compile_variants(JitImage* img);
-// Block sizes of the plan from probe compiles: every multi-rule block of a multi-block kernel
-// is compiled alone under its kernel's bound, and the blocks that spill or exceed the bound's
-// registers are split in two, until every probe meets its bound (then regenerate the image).
-void jit_refine_blocks(const PolicySet& ps, uint32_t chunk_rules, JitImage* img);
+// Does a compiled kernel meet the register rules? One verdict for the spill plan, the variants
+// and the block probes, from the kernel descriptor's private segment and VGPR count, the bound of
+// `waves` per SIMD it was compiled under (0: none) and whether it calls kv_dleaf_impl (the
+// out-of-line dynamic-leaf evaluator of pattern variables, which keeps a call frame in scratch).
+struct RegVerdict {
+  uint32_t priv, vgprs;
+  bool calls;
+  bool fits;        // within the bound's registers: vgprs <= 512 / waves
+  bool scratch_ok;  // no private segment, or the call frame in a kernel without a bound (the round-1
+                    // fault was spill code under a bound)
+  bool ships() const { return fits && scratch_ok; }  // a planned kernel is kept, a variant ships
+  // A block probe splits its block. Deliberately not !ships(): a probe always has a bound, and the
+  // call frame is excused there too (the spill plan drops such a kernel's bound, blocks untouched).
+  bool probe_splits() const { return (priv != 0 && !calls) || !fits; }
+};
+RegVerdict reg_verdict_of(uint32_t priv, uint32_t vgprs, int waves, bool calls);
+// Register budget of the plan, from the verdict of each planned kernel: a kernel that ships is kept;
+// one whose only fault is a call frame under a bound drops the bound. Otherwise a multi-block kernel
+// under a bound of w > 6 waves per SIMD is recompiled at w - 1; else its largest block is split in
+// two; a kernel of one-rule blocks is compiled at w - 1, then without a bound, then as two kernels
+// (a one-rule kernel that still spills: std::runtime_error). Returns true when the plan changed
+// (regenerate + compile again; the kernels that did not change come from the code-object cache).
+bool jit_plan_spills(JitImage* img, const std::vector<RegVerdict>& verdicts);
 // Plan cache (in the code-object cache directory): the final kernel plan of a policy set,
-// keyed by a hash of its first generated image (jit_plan_key), so a later compile of the
-// same set goes straight to its final kernels (plan-<key>.txt, which also lists their
-// code-object files).
-std::string jit_plan_key(const JitImage& img);
+// keyed by a hash of its first generated image, so a later compile of the same set goes
+// straight to its final kernels (plan-<key>.txt, which also lists their code-object files).
 bool jit_load_plan(const std::string& key, JitImage* img);
 void jit_save_plan(const std::string& key, const JitImage& img);
-bool co_kernel_info(const std::vector<char>& co, const std::string& name, uint32_t* private_seg, uint64_t* code,
-                    uint32_t* vgprs = nullptr);
-// SGPRs the compiler spilled into VGPR lanes (AMDGPU metadata .sgpr_spill_count)
-uint32_t co_sgpr_spills(const std::vector<char>& co);
 
 }  // namespace kvh

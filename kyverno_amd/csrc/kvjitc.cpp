@@ -2,7 +2,7 @@
 //
 //   kvjitc <program.hip> <out.co> <name>
 //
-// libkvgpu spawns several of these (jit_compile, kvjit.cpp): hiprtc serialises
+// libkvgpu spawns several of these (jit_compile, kvjitbuild.cpp): hiprtc serialises
 // compilations inside one process, so the kernel programs of a large policy set
 // compile in parallel only across processes. The child never touches a GPU.
 #include <hip/hiprtc.h>
@@ -31,7 +31,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "kvjitc: hiprtcCreateProgram failed\n");
     return 1;
   }
-  // the options of kvjit.cpp kOpts
+  // the options of kvjitbuild.cpp kOpts
   const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-label", "-Wno-unused-variable"};
   if (hiprtcCompileProgram(prog, (int)(sizeof opts / sizeof opts[0]), opts) != HIPRTC_SUCCESS) {
     size_t ls = 0;

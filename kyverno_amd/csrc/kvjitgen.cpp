@@ -1,4 +1,5 @@
-// Specialized kernels for a compiled policy set (see kvjit.hpp).
+// Specialized kernels for a compiled policy set (see kvjit.hpp): the source generator. String emission
+// over a PolicySet: no HIP, no hiprtc, no process, no file (kvjitbuild.cpp compiles the programs).
 //
 // Every GPU-routed rule's bytecode program (kvcompile.cpp) is re-emitted as a
 // device function whose statements are the interpreter's op semantics
@@ -9,20 +10,7 @@
 // hardware exec mask runs the divergence). Rule functions are inlined into
 // chunk kernels, so lookups shared by several rules (root -> spec ->
 // containers ...) are loaded once per chunk (the node store is __restrict__).
-#include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
-
-#include <dlfcn.h>
-#include <sched.h>
-#include <spawn.h>
-#include <sys/stat.h>
-#include <sys/wait.h>
-
-#include <cerrno>
-#include <unistd.h>
-
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -31,13 +19,10 @@
 #include <set>
 #include <sstream>
 #include <stdexcept>
-#include <thread>
 #include <unordered_map>
 
 #include "kvjit.hpp"
 #include "kvdevtypes.h"
-
-extern char** environ;
 
 namespace kvh {
 
@@ -75,10 +60,37 @@ std::string f64(double v) {
 // 21-member image-glob groups go to slots), C3 8.22 / 9.7; from 22 C2 0.701 / 0.40, C3 8.24 /
 // 9.4; never C2 0.699 / 0.40, C3 9.13 / 7.5.
 constexpr uint32_t kGslotMembers = 22u;
-uint32_t gslot_members() { return kGslotMembers; }
+
+// The generator's tuning environment, read once per jit_generate. Every one of these is part of
+// the program text and so of the cache keys (code objects and plan):
+//   KVGPU_JIT_NARROW=0   every path column wide (A/B runs; col_plan)
+//   KVGPU_JIT_STAMPS     the rule kernels stamp their segment boundaries (group_kernel, kJitStamps)
+//   KVGPU_JIT_WAVES      first launch bound in waves per SIMD (default: at most 8, 0: none)
+//   KVGPU_JIT_BLOCK_W    weight budget of the first block sizes (initial_blocks; default 160 / 240)
+//   KVGPU_JIT_DIAG=A,B   diagnostics-only kernels (#define KV_DIAG_A ... ahead of the prelude; wrong results)
+struct GenOpts {
+  bool narrow, stamps, has_waves;
+  int waves;
+  uint32_t block_w;  // 0: the defaults
+  std::string diag;  // the #define lines
+  GenOpts() {
+    const char* e = getenv("KVGPU_JIT_NARROW");
+    narrow = !(e && e[0] == '0');
+    stamps = getenv("KVGPU_JIT_STAMPS") != nullptr;
+    e = getenv("KVGPU_JIT_WAVES");
+    has_waves = e != nullptr;
+    waves = e ? atoi(e) : 0;
+    e = getenv("KVGPU_JIT_BLOCK_W");
+    block_w = e && atoi(e) > 0 ? (uint32_t)atoi(e) : 0u;
+    std::istringstream names((e = getenv("KVGPU_JIT_DIAG")) ? e : "");
+    for (std::string t; std::getline(names, t, ',');)
+      if (!t.empty()) diag += "#define KV_DIAG_" + t + " 1\n";
+  }
+};
 
 struct Gen {
   const PolicySet& ps;
+  const GenOpts opt;
   std::ostringstream o;
   std::set<uint32_t> preds_done, atoms_done;
   // value-predicate memo: a leaf predicate on a scalar is a pure function of the
@@ -123,9 +135,8 @@ struct Gen {
   // (an array's element count); CU_LEAF: a leaf predicate reads it (its array case needs a and b
   // when the cell is wide, and reads the array's node when it is narrow: kv_leaf_word_n). The uses of every
   // rule of the policy set decide, whatever the kernel plan; KVGPU_JIT_NARROW=0 makes every
-  // column wide (A/B runs; read here, so part of the program text and of the cache keys).
+  // column wide (GenOpts).
   enum ColUse : uint32_t { CU_WIDE = 1u, CU_B = 2u, CU_LEAF = 4u };
-  const bool narrow_on = !(getenv("KVGPU_JIT_NARROW") && getenv("KVGPU_JIT_NARROW")[0] == '0');
   std::map<std::string, uint32_t> use_seed;  // uses known before generation (JitImage::col_use)
   void col_mark(int fam, uint32_t j, uint32_t use) {
     if (fam >= 0 && j != kNoCol) fams.at((size_t)fam).use.at(j) |= use;
@@ -210,7 +221,7 @@ struct Gen {
         c.j = j;
         c.nsteps = (uint32_t)F.steps[j].size();
         for (uint32_t s = 0; s < c.nsteps; s++) c.steps[s] = F.steps[j][s];
-        if (narrow_on && !(use[j] & CU_WIDE)) {
+        if (opt.narrow && !(use[j] & CU_WIDE)) {
           c.fmt = KV_COLF_NARROW;
           c.pos = nn++;
         } else {
@@ -247,13 +258,6 @@ struct Gen {
     }
     for (uint32_t f = 1; f < fams.size(); f++) out->cols.at(out->fam_arr[f]).arr_fam = f;
     *defs = d.str();
-  }
-
-  // leaf predicate `pi` on node expression `n` (arrays: every element): one bit of the
-  // value-predicate table
-  std::string leaf_test(uint32_t pi, const std::string& n) {
-    const uint32_t slot = slot_for(pi);
-    return "((kv_leaf_word(P, N, " + n + ", " + u32(slot / 32) + ") >> " + u32(slot % 32) + ") & 1u) != 0u";
   }
 
   // ---------------------------------------------------------------- globs
@@ -1132,7 +1136,7 @@ struct Gen {
       for (uint32_t lv = 0; lv < 4; lv++) r << ", " << (lv <= g.max_level ? li(lv) : std::string("0u"));
       r << ", s_w + " << u32(KV_ROW0 + g.grow * KV_RSTRIDE) << ", " << u32(g.grow) << ", " << (g.gtab.empty() ? std::string("nullptr") : g.gtab) << ", "
         << u32(g.gn) << ", " << u32(g.gri[0]) << ", " << u32(g.gsri) << ", " << u32(g.gspn) << ", "
-        << (!g.gsite && g.gn >= gslot_members() ? "true" : "false");
+        << (!g.gsite && g.gn >= kGslotMembers ? "true" : "false");
       if (g.gsite) r << ", s_gc_ + " << u32(KV_RWAVES * g.gl) << ", " << u32(g.gpre);
       r << ");";
       return r.str();
@@ -1564,7 +1568,7 @@ struct Gen {
   // the tuple kernel sets to 1).
   uint32_t mt_kbase = 0;
   std::vector<uint32_t> mt_bits;
-  std::vector<uint8_t> rec_slot;  // rules whose records go to their resource slot (gslot_members)
+  std::vector<uint8_t> rec_slot;  // rules whose records go to their resource slot (kGslotMembers)
   bool name_dependent(uint32_t ri) const {
     const RuleRec& rr = ps.rules[ri];
     for (uint32_t f = rr.m_first; f < rr.m_first + rr.m_count; f++)
@@ -1678,7 +1682,7 @@ struct Gen {
           gs_members += g.gn;
         }
         // (site-record members get their records expanded to their resource slots at fetch)
-        if (g.gsite || g.gn >= gslot_members())
+        if (g.gsite || g.gn >= kGslotMembers)
           for (uint32_t m : G.members) rec_slot.at(m) = 1;
         g.grow = hbase + q;
         for (const auto& m : G.preds)
@@ -2112,7 +2116,7 @@ struct Gen {
     if (k_gsn > 64u) throw std::runtime_error("kvjit: more than 64 site-record groups in one kernel");
     KernelText kt(*this, name);
     o << block_decls;
-    if (getenv("KVGPU_JIT_STAMPS")) o << "__device__ unsigned long long* kvj_stamps;\n";
+    if (opt.stamps) o << "__device__ unsigned long long* kvj_stamps;\n";
     o << "__device__ const uint32_t " << name << "_rules[" << nr << "] = {";
     for (uint32_t q = 0; q < nr; q++) o << (q ? ", " : "") << u32(rules[q]);
     o << "};\n";
@@ -2157,9 +2161,8 @@ struct Gen {
     // diagnostics (KVGPU_JIT_STAMPS): a wave's shader clock at the start, after each block and
     // after the flush, into the program's global kvj_stamps ([workgroup][wave][kJitStamps], set by
     // kvapi.cpp)
-    const bool stamps = getenv("KVGPU_JIT_STAMPS") != nullptr;
     auto stamp = [&](size_t k) {
-      if (stamps && k < kJitStamps)
+      if (opt.stamps && k < kJitStamps)
         o << "  if (kvj_stamps && (threadIdx.x & 63u) == 0u) kvj_stamps[((size_t)blockIdx.x * KV_RWAVES + (threadIdx.x >> 6)) * "
           << kJitStamps << "u + " << k << "u] = __builtin_amdgcn_s_memtime();\n";
     };
@@ -2290,8 +2293,7 @@ struct Gen {
   // fit its registers (round 4, gpurun_out/ab9 / ab8, ms per pass: C5 3.45 -> 3.25, C4 1.00 ->
   // 0.99; C2, three blocks, keeps the default: with 1.5x 0.694 -> 0.712).
   std::vector<uint32_t> initial_blocks(const std::vector<uint32_t>& sorted, uint32_t a, uint32_t e) {
-    const char* bw = getenv("KVGPU_JIT_BLOCK_W");
-    if (bw && atoi(bw) > 0) return initial_blocks_w(sorted, a, e, (uint32_t)atoi(bw));
+    if (opt.block_w) return initial_blocks_w(sorted, a, e, opt.block_w);
     std::vector<uint32_t> out = initial_blocks_w(sorted, a, e, 160u);
     if (out.size() >= 6) out = initial_blocks_w(sorted, a, e, 240u);
     return out;
@@ -2401,21 +2403,8 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
   auto t0 = std::chrono::steady_clock::now();
   Gen g(ps);
   g.use_seed = out->col_use;
-  // KVGPU_JIT_DIAG=A,B: diagnostics-only kernel variants (#define KV_DIAG_A ... ahead of the
-  // prelude; their results are wrong)
-  std::string diag;
-  if (const char* dg = getenv("KVGPU_JIT_DIAG")) {
-    const std::string d = dg;
-    for (size_t at = 0; at <= d.size();) {
-      const size_t nx = d.find(',', at);
-      const std::string t = d.substr(at, nx == std::string::npos ? std::string::npos : nx - at);
-      if (!t.empty()) diag += "#define KV_DIAG_" + t + " 1\n";
-      if (nx == std::string::npos) break;
-      at = nx + 1;
-    }
-  }
   const std::string prelude =
-      diag + kPrelude + std::string("\nusing namespace kv;\n\n") +
+      g.opt.diag + kPrelude + std::string("\nusing namespace kv;\n\n") +
       "__device__ __noinline__ bool kv_dleaf_impl(const DevBatch& B, const Node* __restrict__ N, uint32_t dp, Node vn);\n\n";
   for (uint32_t ri = 0; ri < ps.rules.size(); ri++)
     if (!no_program(ps.rules[ri])) g.leaf_classes(ri);
@@ -2443,7 +2432,6 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
       // fewer, larger blocks (fewer walks of the resource tree) wins there: C2 (100 rules, one
       // kernel) 6 waves 4 blocks 0.697 ms, 7 waves 16 blocks 0.902 ms, 8 waves 35 blocks
       // 1.224 ms per pass (round 4, gpurun_out/r4b/ab); C4's ~70-rule kernels run at 8.
-      const char* wz = getenv("KVGPU_JIT_WAVES");
       uint32_t parts = (n + chunk_rules - 1) / chunk_rules;
       // one more range while the longest ranges would get fewer workgroups per CU than the
       // shortest (C3: 1 973 rules in 16 ranges of 123/124 -> 17 of 116/117)
@@ -2456,7 +2444,7 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
         // workgroups of 4 waves: waves per SIMD = workgroups per CU the LDS admits
         const int lds_waves = Gen::lds_waves(e - a);
         const int rule_waves = (int)std::max<uint32_t>(1u, (160u * 1024u) / std::max<uint32_t>(1u, (e - a) * 256u));
-        out->plan.push_back({a, e - a, wz ? atoi(wz) : std::min({8, lds_waves, rule_waves}), bl});
+        out->plan.push_back({a, e - a, g.opt.has_waves ? g.opt.waves : std::min({8, lds_waves, rule_waves}), bl});
       }
     }
     for (const JitKernelPlan& kp : out->plan) {
@@ -2556,531 +2544,6 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
     out->source += k.second;
   }
   out->gen_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-namespace {
-
-uint64_t fnv1a64(const std::string& a, uint64_t h = 1469598103934665603ull) {
-  for (unsigned char c : a) h = (h ^ c) * 1099511628211ull;
-  return h;
-}
-
-std::string cache_dir() {
-  const char* e = getenv("KVGPU_JIT_CACHE");
-  if (e && std::string(e) == "0") return "";
-  if (e && *e) return e;
-  if (const char* x = getenv("XDG_CACHE_HOME"); x && *x) return std::string(x) + "/kvgpu";
-  if (const char* h = getenv("HOME"); h && *h) return std::string(h) + "/.cache/kvgpu";
-  return "";
-}
-
-bool read_file(const std::string& path, std::vector<char>* out) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return false;
-  fseek(f, 0, SEEK_END);
-  long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  out->resize(n > 0 ? (size_t)n : 0);
-  const bool ok = n > 0 && fread(out->data(), 1, (size_t)n, f) == (size_t)n;
-  fclose(f);
-  return ok;
-}
-
-void write_file_atomic(const std::string& dir, const std::string& path, const std::vector<char>& data) {
-  std::string cmd = dir;  // create the directory (one level under an existing parent is enough here)
-  for (size_t i = 1; i <= cmd.size(); i++)
-    if (i == cmd.size() || cmd[i] == '/') mkdir(cmd.substr(0, i).c_str(), 0755);
-  const std::string tmp = path + ".tmp." + std::to_string((unsigned long long)getpid()) + "." +
-                          std::to_string(std::hash<std::thread::id>()(std::this_thread::get_id()));
-  FILE* f = fopen(tmp.c_str(), "wb");
-  if (!f) return;
-  const bool ok = fwrite(data.data(), 1, data.size(), f) == data.size();
-  fclose(f);
-  if (!ok || rename(tmp.c_str(), path.c_str()) != 0) unlink(tmp.c_str());
-}
-
-const char* const kOpts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-label", "-Wno-unused-variable"};
-
-std::vector<char> compile_one(const std::string& src, const std::string& name) {
-  hiprtcProgram prog;
-  if (hiprtcCreateProgram(&prog, src.c_str(), (name + ".hip").c_str(), 0, nullptr, nullptr) != HIPRTC_SUCCESS)
-    throw std::runtime_error("hiprtcCreateProgram failed");
-  hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof kOpts / sizeof kOpts[0]), kOpts);
-  if (rc != HIPRTC_SUCCESS) {
-    size_t ls = 0;
-    hiprtcGetProgramLogSize(prog, &ls);
-    std::string log(ls, '\0');
-    if (ls) hiprtcGetProgramLog(prog, &log[0]);
-    hiprtcDestroyProgram(&prog);
-    throw std::runtime_error("hiprtc compile of " + name + " failed: " + log.substr(0, 4000));
-  }
-  size_t cs = 0;
-  hiprtcGetCodeSize(prog, &cs);
-  std::vector<char> code(cs);
-  hiprtcGetCode(prog, code.data());
-  hiprtcDestroyProgram(&prog);
-  return code;
-}
-
-// kvjitc next to libkvgpu.so (KVGPU_JITC overrides): compiles one program per process
-std::string jitc_path() {
-  if (const char* e = getenv("KVGPU_JITC")) return e;
-  Dl_info info{};
-  if (!dladdr((void*)&jitc_path, &info) || !info.dli_fname) return "";
-  std::string p = info.dli_fname;
-  const size_t slash = p.rfind('/');
-  p = (slash == std::string::npos ? std::string(".") : p.substr(0, slash)) + "/kvjitc";
-  return access(p.c_str(), X_OK) == 0 ? p : "";
-}
-
-// cores this process may use: affinity, capped by a cgroup v2 CPU quota
-unsigned host_threads() {
-  unsigned n = std::thread::hardware_concurrency();
-  cpu_set_t cs;
-  if (sched_getaffinity(0, sizeof cs, &cs) == 0) n = (unsigned)CPU_COUNT(&cs);
-  if (FILE* f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-    char q[32] = {0};
-    unsigned long long per = 0;
-    if (fscanf(f, "%31s %llu", q, &per) == 2 && strcmp(q, "max") != 0 && per)
-      n = std::min<unsigned>(n, (unsigned)std::max(1ull, strtoull(q, nullptr, 10) / per));
-    fclose(f);
-  }
-  return std::max(1u, n);
-}
-
-// compile programs `todo` of img in child processes (kvjitc), `T` at a time
-void compile_in_children(JitImage* img, const std::vector<size_t>& todo, const std::string& jitc, unsigned T) {
-  const char* td = getenv("TMPDIR");
-  std::string tmpl = std::string(td && *td ? td : "/tmp") + "/kvjit.XXXXXX";
-  std::vector<char> tbuf(tmpl.begin(), tmpl.end());
-  tbuf.push_back('\0');
-  if (!mkdtemp(tbuf.data())) throw std::runtime_error("kvjit: mkdtemp failed");
-  const std::string dir(tbuf.data());
-  std::atomic<size_t> next{0}, done{0};
-  std::vector<std::string> errs(T);
-  // KVGPU_PROGRESS=1: a line on stderr at most every 15 s (long compiles stay visibly alive)
-  const bool progress = getenv("KVGPU_PROGRESS") && getenv("KVGPU_PROGRESS")[0] == '1';
-  const auto t0 = std::chrono::steady_clock::now();
-  std::atomic<int64_t> last_ms{0};
-  std::vector<std::thread> th;
-  for (unsigned t = 0; t < T; t++)
-    th.emplace_back([&, t]() {
-      for (size_t j; (j = next++) < todo.size();) {
-        const size_t i = todo[j];
-        const std::string src = dir + "/" + std::to_string(i) + ".hip", out = dir + "/" + std::to_string(i) + ".co";
-        {
-          FILE* f = fopen(src.c_str(), "wb");
-          const std::string prog = img->common + img->kernel_src[i];
-          if (!f || fwrite(prog.data(), 1, prog.size(), f) != prog.size()) {
-            errs[t] = "kvjit: cannot write " + src;
-            if (f) fclose(f);
-            return;
-          }
-          fclose(f);
-        }
-        std::vector<std::string> av = {jitc, src, out, img->kernel_name[i]};
-        std::vector<char*> argv;
-        for (auto& a : av) argv.push_back(&a[0]);
-        argv.push_back(nullptr);
-        pid_t pid = 0;
-        if (posix_spawn(&pid, jitc.c_str(), nullptr, nullptr, argv.data(), environ) != 0) {
-          errs[t] = "kvjit: cannot start " + jitc;
-          return;
-        }
-        int status = 0;
-        while (waitpid(pid, &status, 0) < 0 && errno == EINTR) {
-        }
-        std::vector<char> code;
-        if (!WIFEXITED(status) || WEXITSTATUS(status) != 0 || !read_file(out, &code)) {
-          errs[t] = "kvjit: compiling " + img->kernel_name[i] + " failed (kvjitc status " + std::to_string(status) + ")";
-          return;
-        }
-        img->codes[i] = std::move(code);
-        unlink(src.c_str());
-        unlink(out.c_str());
-        const size_t d = ++done;
-        if (progress) {
-          const int64_t now =
-              (int64_t)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-          int64_t prev = last_ms.load();
-          if (now - prev >= 15000 && last_ms.compare_exchange_strong(prev, now))
-            fprintf(stderr, "[kvgpu] hiprtc: %zu/%zu kernel programs compiled (%.0f s)\n", d, todo.size(), now / 1e3);
-        }
-      }
-    });
-  for (auto& x : th) x.join();
-  rmdir(dir.c_str());
-  for (auto& e : errs)
-    if (!e.empty()) throw std::runtime_error(e);
-}
-
-}  // namespace
-
-// Private (scratch) segment size and code size of kernel `name` in a gfx950 code
-// object: the kernel descriptor `<name>.kd` (offset 4: private_segment_fixed_size)
-// and the size of the function symbol. A non-zero private segment in these
-// kernels means register spills (they keep no arrays on the stack).
-bool co_kernel_info(const std::vector<char>& co, const std::string& name, uint32_t* private_seg, uint64_t* code,
-                    uint32_t* vgprs) {
-  auto rd = [&](size_t off, size_t n, void* out) {
-    if (off + n > co.size()) return false;
-    memcpy(out, co.data() + off, n);
-    return true;
-  };
-  if (co.size() < 64 || memcmp(co.data(), "\x7f" "ELF", 4) != 0 || co[4] != 2) return false;
-  uint64_t shoff = 0;
-  uint16_t shentsize = 0, shnum = 0;
-  rd(0x28, 8, &shoff);
-  rd(0x3A, 2, &shentsize);
-  rd(0x3C, 2, &shnum);
-  struct Sh { uint32_t name, type; uint64_t flags, addr, off, size; uint32_t link, info; uint64_t align, entsize; };
-  std::vector<Sh> sh(shnum);
-  for (uint16_t i = 0; i < shnum; i++)
-    if (!rd(shoff + (uint64_t)i * shentsize, sizeof(Sh), &sh[i])) return false;
-  bool kd = false, fn = false;
-  for (const Sh& t : sh) {
-    if (t.type != 2 /* SHT_SYMTAB */ || t.link >= shnum) continue;
-    const Sh& strtab = sh[t.link];
-    for (uint64_t o = t.off; o + 24 <= t.off + t.size; o += 24) {
-      uint32_t nm = 0;
-      uint16_t shndx = 0;
-      uint64_t value = 0, size = 0;
-      rd(o, 4, &nm);
-      rd(o + 6, 2, &shndx);
-      rd(o + 8, 8, &value);
-      rd(o + 16, 8, &size);
-      if (strtab.off + nm >= co.size()) continue;
-      const char* sn = co.data() + strtab.off + nm;
-      const size_t maxlen = co.size() - (strtab.off + nm);
-      const std::string sym(sn, strnlen(sn, maxlen));
-      if (sym == name + ".kd" && shndx < shnum) {
-        const Sh& sec = sh[shndx];
-        kd = rd(sec.off + (value - sec.addr) + 4, 4, private_seg);
-        // compute_pgm_rsrc1 (descriptor offset 48): granulated VGPR count, 8-register granules
-        // of the unified (arch + acc) file on gfx950
-        uint32_t rsrc1 = 0;
-        if (kd && vgprs && rd(sec.off + (value - sec.addr) + 48, 4, &rsrc1)) *vgprs = ((rsrc1 & 0x3Fu) + 1u) * 8u;
-      } else if (sym == name) {
-        *code = size;
-        fn = true;
-      }
-    }
-  }
-  return kd && fn;
-}
-
-// SGPR spill count of a code object's kernel from its AMDGPU metadata note (msgpack:
-// ".sgpr_spill_count" then a positive fixint / uint8 / uint16 / uint32; one kernel per object).
-// SGPRs spill into VGPR lanes (v_writelane / v_readlane), not into the private segment.
-uint32_t co_sgpr_spills(const std::vector<char>& co) {
-  static const char key[] = "\xb1.sgpr_spill_count";
-  const auto it = std::search(co.begin(), co.end(), key, key + sizeof key - 1);
-  if (it == co.end()) return 0;
-  const size_t at = (size_t)(it - co.begin()) + sizeof key - 1;
-  if (at >= co.size()) return 0;
-  const uint8_t t = (uint8_t)co[at];
-  auto be = [&](size_t n) {
-    uint32_t v = 0;
-    for (size_t i = 0; i < n && at + 1 + i < co.size(); i++) v = v << 8 | (uint8_t)co[at + 1 + i];
-    return v;
-  };
-  if (t < 0x80) return t;
-  if (t == 0xcc) return be(1);
-  if (t == 0xcd) return be(2);
-  if (t == 0xce) return be(4);
-  return 0;
-}
-
-bool jit_plan_spills(JitImage* img) {
-  // No rule kernel ships with a private (scratch) segment, bounded or not (DESIGN.md §4
-  // *Register plan*: every faulting round-1 build had one), and a bound is only kept when the
-  // compiler met it. A kernel that spills under its bound of w waves per SIMD, or that takes
-  // more than 512 / w registers, is recompiled at w - 1 (w = 1: without a bound); an unbounded
-  // kernel that still spills is split in two; a single rule range that does is an error.
-  std::vector<JitKernelPlan> next;
-  bool changed = false;
-  img->kernel_scratch.assign(img->plan.size(), 0);
-  for (size_t k = 0; k < img->plan.size(); k++) {
-    const JitKernelPlan& kp = img->plan[k];
-    const std::string& name = img->chunks[k].name;
-    uint32_t priv = 0, vgprs = 0;
-    uint64_t code = 0;
-    size_t ci = 0;
-    while (ci < img->kernel_name.size() && img->kernel_name[ci] != name) ci++;
-    if (ci == img->kernel_name.size() || !co_kernel_info(img->codes[ci], name, &priv, &code, &vgprs))
-      throw std::runtime_error("kvjit: no kernel descriptor for " + name);
-    img->kernel_scratch[k] = priv;
-    const bool met = kp.waves == 0 || vgprs <= 512u / (uint32_t)kp.waves;
-    // the out-of-line dynamic-leaf evaluator (pattern variables) keeps a call frame in
-    // scratch: allowed in a kernel without a launch bound (the round-1 fault was spill code
-    // under a bound), so such a kernel drops its bound instead of splitting blocks
-    const bool calls = img->kernel_src[ci].find("kv_dleaf_impl") != std::string::npos;
-    if ((priv == 0 || (calls && kp.waves == 0)) && met) {
-      next.push_back(kp);
-      continue;
-    }
-    changed = true;
-    JitKernelPlan np = kp;
-    if (calls && met && priv != 0) {
-      np.waves = 0;
-      next.push_back(np);
-      continue;
-    }
-    size_t big = 0;
-    for (size_t b = 1; b < np.blocks.size(); b++)
-      if (np.blocks[b] > np.blocks[big]) big = b;
-    if (kp.waves > 6 && np.blocks.size() > 1) {
-      // the blocks met the bound alone (jit_refine_blocks) and the kernel still does not: the
-      // pressure crosses blocks, which splitting one block at a time fixes only slowly (C4:
-      // 20+ recompiles); a kernel of multi-block form gives up a wave first (down to 6)
-      np.waves = kp.waves - 1;
-    } else if (!np.blocks.empty() && np.blocks[big] > 1) {  // the largest block in two halves
-      const uint32_t c = np.blocks[big], h = c / 2;
-      np.blocks[big] = h;
-      np.blocks.insert(np.blocks.begin() + big + 1, c - h);
-    } else if (kp.waves > 1) {
-      np.waves = kp.waves - 1;
-    } else if (kp.waves == 1) {
-      np.waves = 0;
-    } else if (kp.count > 1) {
-      const uint32_t h = kp.count / 2;
-      next.push_back({kp.first, h, 0, std::vector<uint32_t>(h, 1u)});
-      next.push_back({kp.first + h, kp.count - h, 0, std::vector<uint32_t>(kp.count - h, 1u)});
-      continue;
-    } else {
-      throw std::runtime_error("kvjit: kernel " + name + " needs " + std::to_string(priv) +
-                               " B of scratch per lane even without a launch bound");
-    }
-    next.push_back(np);
-  }
-  if (changed) img->plan = next;
-  return changed;
-}
-
-void jit_compile_variants(JitImage* img) {
-  img->variants.clear();
-  for (uint32_t full : {3u, 8u}) {
-    JitImage v;
-    v.common = "#define KVJ_FULL " + std::to_string(full) + "u\n" + img->common;
-    std::vector<size_t> at;  // program of each variant program
-    for (size_t i = 0; i < img->kernel_name.size(); i++)
-      if (img->kernel_name[i].rfind("kvj_r", 0) == 0) {
-        v.kernel_name.push_back(img->kernel_name[i]);
-        v.kernel_src.push_back(img->kernel_src[i]);
-        at.push_back(i);
-      }
-    if (at.empty()) return;
-    jit_compile(&v);
-    img->compile_ms += v.compile_ms;
-    JitImage::Variant out;
-    out.full = full;
-    out.codes.resize(img->kernel_name.size());
-    for (size_t j = 0; j < at.size(); j++) {
-      // the plan's bound of this kernel; the variant ships only where it meets the same register
-      // rules as the generic kernel (no scratch, within the bound's registers)
-      int waves = 0;
-      for (size_t k = 0; k < img->chunks.size() && k < img->plan.size(); k++)
-        if (img->chunks[k].name == v.kernel_name[j]) waves = img->plan[k].waves;
-      uint32_t priv = 0, vgprs = 0;
-      uint64_t code = 0;
-      if (!co_kernel_info(v.codes[j], v.kernel_name[j], &priv, &code, &vgprs)) continue;
-      const bool calls = v.kernel_src[j].find("kv_dleaf_impl") != std::string::npos;
-      if ((priv != 0 && !(calls && waves == 0)) || (waves > 0 && vgprs > 512u / (uint32_t)waves)) continue;
-      out.codes[at[j]] = std::move(v.codes[j]);
-    }
-    img->variants.push_back(std::move(out));
-  }
-}
-
-void jit_refine_blocks(const PolicySet& ps, uint32_t chunk_rules, JitImage* img) {
-  // Each block of the plan compiled alone as a probe kernel under its kernel's bound (small
-  // programs, compiled in parallel); a block whose probe spills or exceeds the bound's
-  // registers is split in two, and its halves are probed in the next round.
-  for (int round = 0; round < 12; round++) {
-    JitImage probe;
-    probe.probe = true;
-    probe.col_use = img->col_use;
-    std::vector<std::pair<size_t, size_t>> at;  // (kernel, block) of each probe
-    for (size_t k = 0; k < img->plan.size(); k++) {
-      const JitKernelPlan& kp = img->plan[k];
-      if (kp.blocks.size() < 2 || kp.waves == 0) continue;
-      uint32_t first = kp.first;
-      for (size_t b = 0; b < kp.blocks.size(); b++) {
-        if (kp.blocks[b] > 1) {
-          probe.plan.push_back({first, kp.blocks[b], kp.waves, {kp.blocks[b]}});
-          at.push_back({k, b});
-        }
-        first += kp.blocks[b];
-      }
-    }
-    if (probe.plan.empty()) return;
-    jit_generate(ps, chunk_rules, &probe);
-    jit_compile(&probe);
-    img->compile_ms += probe.compile_ms;
-    std::vector<std::vector<char>> split(img->plan.size());
-    bool any = false;
-    for (size_t i = 0; i < probe.plan.size(); i++) {
-      const std::string& name = probe.chunks[i].name;
-      size_t ci = 0;
-      while (ci < probe.kernel_name.size() && probe.kernel_name[ci] != name) ci++;
-      uint32_t priv = 0, vgprs = 0;
-      uint64_t code = 0;
-      if (ci == probe.kernel_name.size() || !co_kernel_info(probe.codes[ci], name, &priv, &code, &vgprs))
-        throw std::runtime_error("kvjit: no kernel descriptor for probe " + name);
-      const bool calls = probe.kernel_src[ci].find("kv_dleaf_impl") != std::string::npos;
-      if ((priv != 0 && !calls) || vgprs > 512u / (uint32_t)probe.plan[i].waves) {
-        split[at[i].first].resize(img->plan[at[i].first].blocks.size(), 0);
-        split[at[i].first][at[i].second] = 1;
-        any = true;
-      }
-    }
-    if (!any) return;
-    for (size_t k = 0; k < img->plan.size(); k++) {
-      if (split[k].empty()) continue;
-      std::vector<uint32_t> nb;
-      for (size_t b = 0; b < img->plan[k].blocks.size(); b++) {
-        const uint32_t c = img->plan[k].blocks[b];
-        if (split[k][b]) {
-          nb.push_back(c / 2);
-          nb.push_back(c - c / 2);
-        } else {
-          nb.push_back(c);
-        }
-      }
-      img->plan[k].blocks = nb;
-    }
-  }
-}
-
-uint64_t code_bytes(const JitImage& img) {
-  uint64_t n = 0;
-  for (auto& c : img.codes) n += c.size();
-  return n;
-}
-
-namespace {
-
-// hash of the compiler options, hiprtc version and the common prelude of img's programs
-uint64_t common_hash(const JitImage& img) {
-  std::string opt_key;
-  for (const char* o : kOpts) opt_key += std::string(o) + "\n";
-  int hv = 0;
-  (void)hiprtcVersion(&hv, &hv);
-  opt_key += "hiprtc " + std::to_string(hv) + "\n";
-  return fnv1a64(img.common, fnv1a64(opt_key));
-}
-
-// code-object cache file of kernel program i: <name>-<hash of options + program text>.co
-std::string cache_file(const JitImage& img, size_t i, uint64_t hcommon) {
-  char key[40];
-  snprintf(key, sizeof key, "%016llx", (unsigned long long)fnv1a64(img.kernel_src[i], hcommon));
-  return img.kernel_name[i] + "-" + key + ".co";
-}
-
-}  // namespace
-
-std::string jit_plan_key(const JitImage& img) {
-  uint64_t h = common_hash(img);
-  for (size_t i = 0; i < img.kernel_src.size(); i++) h = fnv1a64(img.kernel_src[i], fnv1a64(img.kernel_name[i], h));
-  char key[40];
-  snprintf(key, sizeof key, "%016llx", (unsigned long long)h);
-  return key;
-}
-
-bool jit_load_plan(const std::string& key, JitImage* img) {
-  const std::string dir = cache_dir();
-  std::vector<char> text;
-  if (dir.empty() || !read_file(dir + "/plan-" + key + ".txt", &text)) return false;
-  std::vector<JitKernelPlan> plan;
-  std::string line;
-  for (size_t i = 0; i <= text.size(); i++) {
-    if (i < text.size() && text[i] != '\n') {
-      line.push_back(text[i]);
-      continue;
-    }
-    if (line.rfind("kernel ", 0) == 0) {  // kernel <first> <count> <waves> <block sizes...>
-      JitKernelPlan kp{0, 0, 0, {}};
-      const char* c = line.c_str() + 7;
-      char* e = nullptr;
-      kp.first = (uint32_t)strtoul(c, &e, 10);
-      kp.count = (uint32_t)strtoul(e, &e, 10);
-      kp.waves = (int)strtol(e, &e, 10);
-      uint32_t sum = 0;
-      while (*e) {
-        char* f = nullptr;
-        const unsigned long b = strtoul(e, &f, 10);
-        if (f == e) break;
-        kp.blocks.push_back((uint32_t)b);
-        sum += (uint32_t)b;
-        e = f;
-      }
-      if (sum != kp.count || kp.blocks.empty()) return false;
-      plan.push_back(kp);
-    }
-    line.clear();
-  }
-  if (plan.empty()) return false;
-  img->plan = plan;
-  return true;
-}
-
-void jit_save_plan(const std::string& key, const JitImage& img) {
-  const std::string dir = cache_dir();
-  if (dir.empty()) return;
-  std::string t;
-  for (const JitKernelPlan& kp : img.plan) {
-    t += "kernel " + std::to_string(kp.first) + " " + std::to_string(kp.count) + " " + std::to_string(kp.waves);
-    for (uint32_t b : kp.blocks) t += " " + std::to_string(b);
-    t += "\n";
-  }
-  // the code objects of the final kernels (tools/jit_warm.sh keeps these, drops the
-  // intermediate probes and re-plans)
-  const uint64_t hc = common_hash(img);
-  for (size_t i = 0; i < img.kernel_src.size(); i++) t += "co " + cache_file(img, i, hc) + "\n";
-  for (const JitImage::Variant& v : img.variants) {  // (the output-mode variants' code objects)
-    JitImage w;
-    w.common = "#define KVJ_FULL " + std::to_string(v.full) + "u\n" + img.common;
-    w.kernel_src = img.kernel_src;
-    w.kernel_name = img.kernel_name;
-    const uint64_t hv = common_hash(w);
-    for (size_t i = 0; i < img.kernel_src.size(); i++)
-      if (i < v.codes.size() && !v.codes[i].empty()) t += "co " + cache_file(w, i, hv) + "\n";
-  }
-  write_file_atomic(dir, dir + "/plan-" + key + ".txt", std::vector<char>(t.begin(), t.end()));
-}
-
-void jit_compile(JitImage* img) {
-  auto t0 = std::chrono::steady_clock::now();
-  const size_t K = img->kernel_src.size();
-  img->codes.assign(K, {});
-  img->cache_hits = 0;
-  const std::string dir = cache_dir();
-  const uint64_t hcommon = common_hash(*img);
-  // cache lookups; the misses compile in child processes (hiprtc serialises the
-  // compilations of one process), or in this process when kvjitc is unavailable
-  // (KVGPU_JIT_PROCS=0 forces that)
-  std::vector<std::string> paths(K);
-  std::vector<size_t> todo;
-  uint32_t hits = 0;
-  for (size_t i = 0; i < K; i++) {
-    paths[i] = dir.empty() ? "" : dir + "/" + cache_file(*img, i, hcommon);
-    if (!paths[i].empty() && read_file(paths[i], &img->codes[i])) hits++;
-    else todo.push_back(i);
-  }
-  unsigned T = std::min(16u, host_threads());
-  if (const char* e = getenv("KVGPU_JIT_THREADS")) T = (unsigned)std::max(1, atoi(e));
-  T = std::max(1u, std::min<unsigned>(T, (unsigned)todo.size()));
-  const std::string jitc = jitc_path();
-  const bool procs = !(getenv("KVGPU_JIT_PROCS") && getenv("KVGPU_JIT_PROCS")[0] == '0');
-  if (!todo.empty() && procs && !jitc.empty() && todo.size() > 1) {
-    compile_in_children(img, todo, jitc, T);
-  } else {
-    for (size_t i : todo) img->codes[i] = compile_one(img->common + img->kernel_src[i], img->kernel_name[i]);
-  }
-  if (!dir.empty())
-    for (size_t i : todo) write_file_atomic(dir, paths[i], img->codes[i]);
-  img->cache_hits = hits;
-  img->compile_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 }  // namespace kvh

@@ -1,6 +1,6 @@
 """Host (x86) runs of the generated specialized kernels under ASan/UBSan (tools/kvemu).
 
-Test infrastructure only: the generated gfx950 source of a policy set (kvjit.cpp,
+Test infrastructure only: the generated gfx950 source of a policy set (kvjitgen.cpp,
 dumped with KVGPU_JIT_DUMP, no hiprtc compile) is compiled for the host with
 tools/kvemu/shim.h and run lane by lane over the same ingested batch. This finds
 out-of-bounds reads and undefined behaviour in the generated code without a GPU,

@@ -15,7 +15,7 @@ from parity_util import compare, load_gold
 pytestmark = pytest.mark.gpu
 
 # every parity case runs on both device engines: the bytecode interpreter
-# (kvkernel.hip) and the per-policy-set specialized kernels (kvjit.cpp)
+# (kvkernel.hip) and the per-policy-set specialized kernels (kvjitgen.cpp)
 engines = pytest.mark.parametrize("spec", [False, True], ids=["vm", "specialized"])
 
 

@@ -1,4 +1,4 @@
-"""CPU-side checks of the specialized-kernel generator (kvjit.cpp) without a GPU.
+"""CPU-side checks of the specialized-kernel generator (kvjitgen.cpp) without a GPU.
 
 The generated gfx950 source of each policy set is compiled for the host under
 ASan/UBSan (tests/kvemu.py, tools/kvemu) and run lane by lane over the same

@@ -1,4 +1,4 @@
-"""Narrow path-column cells (kvdevtypes.h ColFmt, kvjit.cpp col_plan) without a GPU.
+"""Narrow path-column cells (kvdevtypes.h ColFmt, kvjitgen.cpp col_plan) without a GPU.
 
 The generated kernels of the narrow_cols_data policies run on the host under ASan/UBSan
 (tests/kvemu.py), once with the generator's choice of cell formats and once with every column

@@ -1,4 +1,4 @@
-// kvemu driver: runs the generated specialized kernels (kvjit.cpp output for one
+// kvemu driver: runs the generated specialized kernels (kvjitgen.cpp output for one
 // policy set, compiled for the host with shim.h) over an ingested batch, lane by
 // lane, and writes the status matrix and error records. Test / debugging
 // infrastructure only (sanitizer runs of the generated code, CPU-side checks of

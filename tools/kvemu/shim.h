@@ -1,6 +1,6 @@
 // kvemu: host (x86) execution of the generated gfx950 kernel source, for
 // debugging and sanitizer runs only (test infrastructure, never the product
-// path: libkvgpu has no CPU evaluation). The generated source (kvjit.cpp,
+// path: libkvgpu has no CPU evaluation). The generated source (kvjitgen.cpp,
 // dumped with KVGPU_JIT_DUMP) is compiled by g++/clang++ with this header
 // force-included; every lane of every workgroup then runs the kernel body on
 // its own, one after the other (tools/kvemu/driver.cpp). Cross-lane parts
