@@ -89,24 +89,84 @@ struct GenOpts {
 };
 
 struct Gen {
+  struct Fam {
+    std::string arr;                          // family array expr (family 0: "")
+    std::map<std::string, uint32_t> idx;      // relative expr -> column
+    std::vector<std::vector<uint32_t>> steps; // per column: its path steps
+    std::vector<uint32_t> use;                // per column: what the kernels read of it (ColUse)
+  };
+  // Structural form of a rule's program (group_form): rules of one form whose pattern nodes
+  // differ by one constant can run as a rule group
+  struct Form {
+    std::string text;                      // empty: the rule cannot join a group
+    std::vector<uint32_t> preds, pns;      // its leaf predicates and pattern nodes, in program order
+    std::vector<uint32_t> leafpcs;         // its LEAF pcs relative to the program start
+  };
+
   const PolicySet& ps;
   const GenOpts opt;
-  std::ostringstream o;
-  std::set<uint32_t> preds_done, atoms_done;
+
+  // ================================================================ state of the image
+  // Everything below lives for one jit_generate: ids are handed out in order of first use over
+  // the whole image, and every one of them is part of the program text.
+  //
   // value-predicate memo: a leaf predicate on a scalar is a pure function of the
   // (deduplicated) Val it reads, so each one is evaluated once per distinct value
   // of the batch (kvj_ptab) and the rule kernels test one bit of the table
-  std::vector<uint32_t> mpreds;  // memo slot -> pred
+  std::vector<uint32_t> mpreds;        // memo slot -> pred
   std::map<uint32_t, uint32_t> pslot;  // pred -> memo slot
-  // Leaves on a hoisted scalar read their table word(s) through a load hoisted with the
-  // cursor (issued with the other lookups of the region instead of one dependent load
-  // per rule). Hoisted lookups are branch-free (a failed guard reads cell 0 and discards
-  // it) and are placed at the top of their chunk / fused-loop body, so the loads of one
-  // tree level issue together instead of one dependent wait per lookup.
+  std::map<uint32_t, uint32_t> pmask;  // pred -> position classes of its leaves (leaf_classes)
+  // path columns (below): the families, and the uses known before generation (JitImage::col_use)
+  std::vector<Fam> fams;
+  std::map<std::string, uint32_t> fam_of;  // family array expr -> family
+  std::map<std::string, uint32_t> use_seed;
+  // Site records of rule groups (kvdevtypes.h GSiteDesc): per group of 2+ members its descriptor
+  // (n, gpre, moff, 0) in gs_desc and its members' (rule, pattern-node shift) in gs_mem, numbered
+  // in generation order over the image (round 5, with the unwritten NOMATCH segments: C3 writes
+  // 9.4 -> 2.9 GB per pass).
+  std::vector<uint32_t> gs_desc, gs_mem;
+  uint32_t gs_members = 0;
+  // Match bits (kv_mtup_kernel): mt_bits[p] = the rule at bit position p (KV_SENT: padding), in
+  // kernel and LDS-row order; a kernel's rows start at a word boundary (Kern::mt_kbase)
+  std::vector<uint32_t> mt_bits;
+  std::vector<uint8_t> rec_slot;  // rules whose records go to their resource slot (kGslotMembers)
+  uint32_t gtab_n = 0;            // member tables emitted so far
+  std::map<uint32_t, Form> forms;  // group_form of the rules asked for so far (form_of)
+  // kvj_ptab register-path globs (qglob_fn)
+  std::map<uint32_t, uint32_t> bslot;                 // byte -> slot of bm[]
+  std::map<uint32_t, std::set<uint32_t>> glob_bytes;  // atom -> bytes its middle segments search
+  // helper functions (name, text) in generation order, which is dependency order: a helper's
+  // callees are emitted before its own text. Each is emitted once (the done-sets).
+  std::vector<std::pair<std::string, std::string>> helpers;
+  std::set<uint32_t> globs_done, atoms_done, preds_done, blks_done;
+  std::set<std::pair<char, uint32_t>> qglobs_done, qatoms_done, qpreds_done;
+  bool dleaf_done = false;
+  // kernel texts (name, source): each one is compiled as its own hiprtc program after the
+  // helpers it reaches (jit_generate)
+  std::vector<std::pair<std::string, std::string>> kernels;
+
+  // ================================================================ state of one kernel
+  // The rule kernel being generated: group_kernel owns it and hands it to its blocks (a block's
+  // own state is struct Block, below)
+  struct Kern {
+    uint32_t mt_kbase = 0;      // first match word of the kernel: LDS row q has bit 32 * mt_kbase + q
+    uint32_t gs0 = 0, gsn = 0;  // site-record groups: the kernel's first (of the image) and its count
+    std::string decls;          // declarations its blocks need ahead of the kernel (member tables)
+  };
+
   explicit Gen(const PolicySet& p) : ps(p), rec_slot(p.rules.size(), 0) {
     fams.emplace_back();
     col_of(0, "R");  // column 0 of family 0: the root
   }
+
+  // a helper function's text, recorded under its name when it is complete
+  struct Helper : std::ostringstream {
+    Gen& g;
+    const std::string name;
+    Helper(Gen& gg, std::string n) : g(gg), name(std::move(n)) {}
+    ~Helper() { g.helpers.push_back({name, str()}); }
+  };
+  static std::string num(const char* prefix, uint32_t i) { return prefix + std::to_string(i); }
 
   // ---------------------------------------------------------------- path columns
   // Hoisted lookups (below) read the node at their static path from a column of the batch
@@ -117,18 +177,6 @@ struct Gen {
   // kernels read column j of family f through macros (KVC_LD_<f>_<j> and its kin, col_plan)
   // defined at the head of every kernel program once the whole image is generated and the
   // cell format of every column is known.
-  // Site records of rule groups (kvdevtypes.h GSiteDesc): per group of 2+ members its descriptor
-  // (n, gpre, moff, 0) in gs_desc and its members' (rule, pattern-node shift) in gs_mem, numbered
-  // in generation order over the image; k_gs0 / k_gsn: the first group and the groups of the kernel
-  // being generated (round 5, with the unwritten NOMATCH segments: C3 writes 9.4 -> 2.9 GB per pass).
-  std::vector<uint32_t> gs_desc, gs_mem;
-  uint32_t gs_members = 0, k_gs0 = 0, k_gsn = 0;
-  struct Fam {
-    std::string arr;                          // family array expr (family 0: "")
-    std::map<std::string, uint32_t> idx;      // relative expr -> column
-    std::vector<std::vector<uint32_t>> steps; // per column: its path steps
-    std::vector<uint32_t> use;                // per column: what the kernels read of it (ColUse)
-  };
   // Cell format of a column (kvdevtypes.h ColFmt): narrow unless a consumer, marked where it is
   // emitted, reads more of a cell than its presence, its type and a scalar's Val id. CU_WIDE: a
   // field of the node (.a / .b / .c) or a map's own node index is read; CU_B: the node's b is
@@ -137,15 +185,12 @@ struct Gen {
   // rule of the policy set decide, whatever the kernel plan; KVGPU_JIT_NARROW=0 makes every
   // column wide (GenOpts).
   enum ColUse : uint32_t { CU_WIDE = 1u, CU_B = 2u, CU_LEAF = 4u };
-  std::map<std::string, uint32_t> use_seed;  // uses known before generation (JitImage::col_use)
   void col_mark(int fam, uint32_t j, uint32_t use) {
     if (fam >= 0 && j != kNoCol) fams.at((size_t)fam).use.at(j) |= use;
   }
   static std::string col_macro(const char* what, uint32_t f, uint32_t j) {
     return std::string("KVC_") + what + "_" + std::to_string(f) + "_" + std::to_string(j);
   }
-  std::vector<Fam> fams;
-  std::map<std::string, uint32_t> fam_of;  // family array expr -> family
   static constexpr uint32_t kNoCol = 0xFFFFFFFFu;
   // steps of a symbolic path: "/s<slot>" (slot-addressed map) or "/k<key>" (keep-all map
   // scan) after the root token ("R", or "E<tag>" of a loop element, or nothing)
@@ -260,6 +305,18 @@ struct Gen {
     *defs = d.str();
   }
 
+  // every atom of string predicate pi (none of another kind), in alternative and conjunct order
+  template <class Fn>
+  void each_atom(uint32_t pi, Fn fn) const {
+    const Pred& pr = ps.preds[pi];
+    if (pr.kind != PK_STRING) return;
+    for (uint32_t a = pr.first; a < pr.first + pr.count; a++)
+      for (uint32_t c = ps.alts[a].first; c < ps.alts[a].first + ps.alts[a].count; c++) {
+        fn(ps.conjs[c].a0);
+        if (ps.conjs[c].kind != CJ_ATOM) fn(ps.conjs[c].a1);
+      }
+  }
+
   // ---------------------------------------------------------------- globs
   // word compare of segment `sg` against value bytes [k, k + len) (base 4-byte aligned)
   std::string seg_expr(const GSeg& sg, const std::string& k, bool aligned0) {
@@ -287,14 +344,11 @@ struct Gen {
     return e.str();
   }
 
-  std::set<uint32_t> globs_done;
-  void glob_once(uint32_t ai) {
-    if (globs_done.insert(ai).second) glob_fn(ai);
-  }
-
   void glob_fn(uint32_t ai) {
+    if (!globs_done.insert(ai).second) return;
     const Atom& A = ps.atoms[ai];
-    o << "__device__ __forceinline__ bool g_glob_" << ai
+    Helper o(*this, num("g_glob_", ai));
+    o << "__device__ __forceinline__ bool " << o.name
       << "(const uint8_t* __restrict__ s, uint32_t sl, bool ascii, const uint8_t* __restrict__ pstr) {\n";
     const uint32_t fl = A.gflags;
     if (fl & G_ALL) { o << "  return true;\n}\n"; return; }
@@ -330,15 +384,7 @@ struct Gen {
       // positions of its first literal byte, found 4 bytes at a time (SWAR
       // zero-byte test, exact: it never misses a match, false candidates are
       // rejected by the full word compare)
-      int32_t j = -1;
-      uint32_t cbyte = 0;
-      for (uint32_t q = 0; q < sg.len && j < 0; q++) {
-        const GWord& gw = ps.gwords[sg.wfirst + q / 4];
-        if ((gw.mask >> (8 * (q % 4))) & 0xFFu) {
-          j = (int32_t)q;
-          cbyte = (gw.w >> (8 * (q % 4))) & 0xFFu;
-        }
-      }
+      const auto [j, cbyte] = seg_key(sg);
       if (j < 0) {  // all-'?' segment: plain scan
         o << "  { bool found = false;\n"
           << "    for (uint32_t k = pos; k + " << u32(sg.len) << " <= end; k++)\n"
@@ -373,9 +419,6 @@ struct Gen {
   // leftmost verified candidate at or after `pos` wins (the same leftmost-occurrence
   // search as glob_fn, without the per-lane word loop that made the kernel
   // scalar-issue bound: 2.1e8 SALU against 6.0e7 VALU instructions per pass on C2).
-  std::map<uint32_t, uint32_t> bslot;  // byte -> slot of bm[]
-  std::map<uint32_t, std::set<uint32_t>> glob_bytes;  // atom -> bytes its middle segments search
-  std::set<std::pair<char, uint32_t>> qglobs_done, qatoms_done, qpreds_done;
   static constexpr uint32_t kMaxBSlots = 48;
   // register-path variants: values of <= 64 bytes (16 words, 64-bit masks, prefix q_) and
   // of <= 128 bytes (32 words, two-word masks KvM2, prefix r_); the mask helpers
@@ -405,10 +448,10 @@ struct Gen {
   void qglob_fn(uint32_t ai, const QV& v) {
     if (!qglobs_done.insert({v.pfx, ai}).second) return;
     const Atom& A = ps.atoms[ai];
-    std::ostringstream& q = o;
+    Helper q(*this, v.pfx + num("_glob_", ai));
     // branch-free: every step folds into `ok` (indices clamped so a failed step reads in
     // bounds); only a segment whose leftmost candidate fails verification loops over the rest
-    q << "__device__ __forceinline__ bool " << v.pfx << "_glob_" << ai
+    q << "__device__ __forceinline__ bool " << q.name
       << "(const uint32_t* w, const uint32_t* lw, const " << v.mt << "* bm, uint32_t sl, bool ascii, "
          "const uint8_t* __restrict__ pstr) {\n";
     const uint32_t fl = A.gflags;
@@ -485,8 +528,9 @@ struct Gen {
     const Atom& A = ps.atoms[ai];
     atom_fn(ai);
     if (A.kind == AT_GLOB_E || A.kind == AT_GLOB_N) qglob_fn(ai, v);
-    const std::string g = std::string(1, v.pfx) + "_glob_" + std::to_string(ai);
-    o << "__device__ __forceinline__ bool " << v.pfx << "_atom_" << ai << qsig(v) << " {\n";
+    const std::string g = v.pfx + num("_glob_", ai);
+    Helper o(*this, v.pfx + num("_atom_", ai));
+    o << "__device__ __forceinline__ bool " << o.name << qsig(v) << " {\n";
     switch (A.kind) {
       case AT_GLOB_E:
         o << "  const bool r = " << g << "(w, lw, bm, n.c & NC_LEN_MASK, (n.c & NC_ASCII_E) != 0u, pstr);\n"
@@ -508,15 +552,9 @@ struct Gen {
   void qpred_fn(uint32_t pi, const QV& v) {
     if (!qpreds_done.insert({v.pfx, pi}).second) return;
     const Pred& pr = ps.preds[pi];
-    if (pr.kind == PK_STRING)
-      for (uint32_t a = pr.first; a < pr.first + pr.count; a++) {
-        const Alt& al = ps.alts[a];
-        for (uint32_t c = al.first; c < al.first + al.count; c++) {
-          qatom_fn(ps.conjs[c].a0, v);
-          if (ps.conjs[c].kind != CJ_ATOM) qatom_fn(ps.conjs[c].a1, v);
-        }
-      }
-    o << "__device__ __forceinline__ bool " << v.pfx << "_pred_" << pi << qsig(v) << " {\n";
+    each_atom(pi, [&](uint32_t a) { qatom_fn(a, v); });
+    Helper o(*this, v.pfx + num("_pred_", pi));
+    o << "__device__ __forceinline__ bool " << o.name << qsig(v) << " {\n";
     if (pr.kind != PK_STRING) {
       o << "  return g_pred_" << pi << "(V, S, (const uint8_t*)lw, pstr, type, n);\n}\n";
       return;
@@ -541,26 +579,20 @@ struct Gen {
   }
 
   // bytes whose masks the q_pred / r_pred of `pi` reads
-  void pred_bytes(uint32_t pi, std::set<uint32_t>* out) {
-    const Pred& pr = ps.preds[pi];
-    if (pr.kind != PK_STRING) return;
-    for (uint32_t a = pr.first; a < pr.first + pr.count; a++) {
-      const Alt& al = ps.alts[a];
-      for (uint32_t c = al.first; c < al.first + al.count; c++) {
-        for (uint32_t at : {ps.conjs[c].a0, ps.conjs[c].kind != CJ_ATOM ? ps.conjs[c].a1 : ps.conjs[c].a0}) {
-          auto it = glob_bytes.find(at);
-          if (it != glob_bytes.end()) out->insert(it->second.begin(), it->second.end());
-        }
-      }
-    }
+  void pred_bytes(uint32_t pi, std::set<uint32_t>* out) const {
+    each_atom(pi, [&](uint32_t at) {
+      auto it = glob_bytes.find(at);
+      if (it != glob_bytes.end()) out->insert(it->second.begin(), it->second.end());
+    });
   }
 
   // ---------------------------------------------------------------- atoms / predicates
   void atom_fn(uint32_t ai) {
     if (!atoms_done.insert(ai).second) return;
     const Atom& A = ps.atoms[ai];
-    if (A.kind == AT_GLOB_E || A.kind == AT_GLOB_N) glob_once(ai);
-    o << "__device__ __forceinline__ bool g_atom_" << ai
+    if (A.kind == AT_GLOB_E || A.kind == AT_GLOB_N) glob_fn(ai);
+    Helper o(*this, num("g_atom_", ai));
+    o << "__device__ __forceinline__ bool " << o.name
       << "(const Val* __restrict__ V, const uint8_t* __restrict__ S, const uint8_t* __restrict__ E, "
          "const uint8_t* __restrict__ pstr, uint32_t type, const Node& n) {\n";
     switch (A.kind) {
@@ -599,17 +631,10 @@ struct Gen {
   void pred_fn(uint32_t pi) {
     if (!preds_done.insert(pi).second) return;
     const Pred& pr = ps.preds[pi];
-    if (pr.kind == PK_STRING) {
-      for (uint32_t a = pr.first; a < pr.first + pr.count; a++) {
-        const Alt& al = ps.alts[a];
-        for (uint32_t c = al.first; c < al.first + al.count; c++) {
-          atom_fn(ps.conjs[c].a0);
-          if (ps.conjs[c].kind != CJ_ATOM) atom_fn(ps.conjs[c].a1);
-        }
-      }
-    }
+    each_atom(pi, [&](uint32_t a) { atom_fn(a); });
     // E: the validateString (e-form) bytes of the value, S + n.b in the rule kernels (a staged copy in kvj_ptab)
-    o << "__device__ __forceinline__ bool g_pred_" << pi
+    Helper o(*this, num("g_pred_", pi));
+    o << "__device__ __forceinline__ bool " << o.name
       << "(const Val* __restrict__ V, const uint8_t* __restrict__ S, const uint8_t* __restrict__ E, "
          "const uint8_t* __restrict__ pstr, uint32_t type, const Node& n) {\n";
     switch (pr.kind) {
@@ -673,7 +698,6 @@ struct Gen {
   // and the element position when the value is an array). Ingest marks each
   // value with the class bits of the positions holding it (Val::cls), so the
   // table bit of (pred, value) is computed exactly when some node could read it.
-  std::map<uint32_t, uint32_t> pmask;
   void leaf_classes(uint32_t ri) {
     // per cursor depth: projection-trie node (child lookups) and position id (value classes,
     // kv_pos_elem); -2 = unknown (every class)
@@ -721,19 +745,6 @@ struct Gen {
   // kvj_ptab: one lane per distinct scalar Val of the batch; evaluates every memo
   // slot's predicate on the scalar node ingest builds for that value
   // (kvingest.cpp scalar(): a = val id, b = e_off, c = e_len | NC_* flags)
-  // kernel texts (name, source): each one is compiled as its own hiprtc program
-  // after the helpers every kernel may use (Gen::o, the common part)
-  std::vector<std::pair<std::string, std::string>> kernels;
-  struct KernelText {  // redirects Gen::o into a kernel's own text for its lifetime
-    Gen& g;
-    std::string name;
-    std::ostringstream saved;
-    KernelText(Gen& gg, std::string n) : g(gg), name(std::move(n)) { std::swap(g.o, saved); }
-    ~KernelText() {
-      std::swap(g.o, saved);
-      g.kernels.push_back({name, saved.str()});
-    }
-  };
 
   // the slots `ks` by predicate (a predicate holds several slots when rule groups share it):
   // predicate -> (table word -> bits), in first-slot order
@@ -758,7 +769,7 @@ struct Gen {
     // register-path predicates (helpers: emitted before the kernel text)
     for (uint32_t k = 0; k < mpreds.size(); k++) qpred_fn(mpreds[k], kQ64);
     for (uint32_t k = 0; k < mpreds.size(); k++) qpred_fn(mpreds[k], kQ128);
-    KernelText kt(*this, "kvj_ptab");
+    std::ostringstream o;
     const uint32_t nw = (uint32_t)((mpreds.size() + 31) / 32);
     auto pm = [&](uint32_t k) { auto it = pmask.find(mpreds[k]); return it == pmask.end() ? 0xFFFFFFFFu : it->second; };
     // predicates grouped by position class: a value runs the groups its class bits select
@@ -852,15 +863,17 @@ struct Gen {
     o << "  }\n  }\n";
     for (uint32_t i = 0; i < nw; i++) o << "  PT[(size_t)" << i << "u * NP + v] = w[" << i << "];\n";
     o << "}\n\n";
+    kernels.push_back({"kvj_ptab", o.str()});
   }
 
   // dynamic leaves (pattern variables, kvvars.cpp): the generic predicate evaluator on the
   // batch table, out of line (one copy per program; inlined per leaf it multiplies the
-  // kernel's code and its compile time)
-  bool dleaf_done = false;
+  // kernel's code and its compile time). One record: the wrapper every VLEAF calls, and the
+  // evaluator it reaches (declared in the prelude), so a program that takes one takes both.
   void dleaf_fn() {
     if (dleaf_done) return;
     dleaf_done = true;
+    Helper o(*this, "g_dleaf_0");
     o << "__device__ __forceinline__ bool g_dleaf_0(const DevBatch& B, const Node* __restrict__ N, uint32_t dp, "
          "const Node& vn) { return kv_dleaf_impl(B, N, dp, vn); }\n"
       << "__device__ __noinline__ bool kv_dleaf_impl(const DevBatch& B, const Node* __restrict__ N, uint32_t dp, Node vn) {\n"
@@ -875,12 +888,12 @@ struct Gen {
   // blk_ok(f) == !(MF_EMPTY) && doesResourceMatchConditionBlock(f) has no errors
   // (pkg/engine/utils.go:265-336); MF_EMPTY / MF_UI_FAIL are folded per launch
   // (user info), so they are read from P.fflags; every other criterion is static.
-  std::set<uint32_t> blks_done;
   void blk_fn(uint32_t f) {
     if (!blks_done.insert(f).second) return;
     const MFilter& F = ps.filters[f];
-    for (uint32_t a : ps.filter_name_atoms.at(f)) glob_once(a);  // before this function's text
-    o << "__device__ __forceinline__ bool g_blk_" << f
+    for (uint32_t a : ps.filter_name_atoms.at(f)) glob_fn(a);  // before this function's text
+    Helper o(*this, num("g_blk_", f));
+    o << "__device__ __forceinline__ bool " << o.name
       << "(const DevPS& P, const DevBatch& B, const Res* __restrict__ R, uint32_t rkind, uint32_t rflags) {\n"
       << "  if (sld(P.fflags + " << f << "u) & (MF_EMPTY | MF_UI_FAIL)) return false;\n";
     if (F.flags & MF_KINDS) {
@@ -940,7 +953,8 @@ struct Gen {
       }
       return e.str();
     };
-    o << "__device__ __forceinline__ bool g_match_" << ri
+    Helper o(*this, num("g_match_", ri));
+    o << "__device__ __forceinline__ bool " << o.name
       << "(const DevPS& P, const DevBatch& B, const Res* __restrict__ R, uint32_t rkind, uint32_t rflags) {\n"
       << "  if (!" << combine(rr.m_mode, rr.m_first, rr.m_count) << ") return false;\n"
       << "  return !" << combine(rr.x_mode, rr.x_first, rr.x_count) << ";\n}\n";
@@ -969,6 +983,12 @@ struct Gen {
   // node << 8), loop indices of the raise (ei0..), anchor bitsets when used.
   static constexpr uint32_t FIN = 0x7F000000u, ACT = 0x80000000u;
 
+  // Leaves on a hoisted scalar read their table word(s) through a load hoisted with the
+  // cursor (issued with the other lookups of the region instead of one dependent load
+  // per rule). Hoisted lookups are branch-free (a failed guard reads cell 0 and discards
+  // it) and are placed at the top of their chunk / fused-loop body, so the loads of one
+  // tree level issue together instead of one dependent wait per lookup.
+  //
   // hoisted cursor: node index var + Node var, and the path column the node is read from
   // (fam -1: none). The index var of a column's node is a node index for a map only.
   struct HVar {
@@ -1003,17 +1023,15 @@ struct Gen {
     // cursor as a node index makes them all wide)
     std::vector<std::vector<std::pair<int, uint32_t>>> csrc;
     std::set<uint32_t> resume;                          // resume targets of later segments
-    // targets past the segment being emitted, reached without / with a pending error
-    std::set<uint32_t> seg_jumps, seg_err_jumps;
     // resume targets set by earlier stages and not consumed yet (the segment holding them lies
     // further on), reached without / with a pending error
     std::set<uint32_t> carry_ok, carry_err;
     // per stage loop k: the rule is "lean" there (its state is one bit of the block's stage-k
     // masks and a failing element decides its status at once), the status its post chain adds
-    // to the error (flags) and whether that chain ends at the last anyPattern alternative
-    std::vector<char> lean;
-    std::vector<uint32_t> post_flags, skip_to, skip_flags;
-    std::vector<char> post_alt, skip_alt;
+    // to the error (flags), whether that chain ends at the last anyPattern alternative, and the
+    // one target past the loop that the stage-k segment jumps to (0xFFFFFFFF: none)
+    std::vector<char> lean, post_alt;
+    std::vector<uint32_t> post_flags, skip_to;
     uint32_t q = 0;                                     // position in the block (mask bit, LDS row)
     bool uses_anchor = false, uses_keyglob = false;
     // rule group: the representative's program run once for all members (bit j of `al` = member
@@ -1077,22 +1095,57 @@ struct Gen {
     uint32_t rb = 0, re = 0;  // ops emitted: [rb, re)
     uint32_t jre = 0;         // local jump targets: [rb, jre)
     std::string se;           // segment end label
+    // out (kind 0): the targets past the segment that it jumps to, without / with a pending error
+    std::set<uint32_t>*jumps = nullptr, *err_jumps = nullptr;
     std::string li0;          // level-0 loop index expression
     HoistTable* T = nullptr;  // hoist table for exprs rooted at this region's loop element
     std::string troot;        // expr root of T
   };
 
-  HoistTable* gT = nullptr;  // global (root-derived) hoist table of the current chunk
-  // per-rule histogram of a rule kernel from its statuses staged in LDS (one byte per rule and
-  // lane, counted once when the kernel ends: kv_end_flush); otherwise (store_result2) with ballots
-  // + LDS atomics per rule and wave
-  bool hist_lds = false;
+  // Rule groups: rules of one structural form (group_form) whose pattern nodes differ by one
+  // constant run the representative's program once, with one bit per member; their leaf predicates
+  // take consecutive bits of one table word, so a leaf tests every member with one shift and mask.
+  struct GInfo {
+    std::vector<uint32_t> members, pns0, leafpcs;
+    std::vector<uint32_t> dpn;                 // pattern-node shift of each member
+    std::vector<std::vector<uint32_t>> preds;  // leaf predicates of each member
+  };
 
-  void emit_region(RGen& g, const Region& R, std::ostringstream& wout) {
-    struct OpOut {
-      std::string code;
-    };
-    std::vector<OpOut> outs;
+  // One fused block of a kernel while it is generated (fused_block owns it): its rules in block
+  // position order (a group's members take consecutive positions, at its first member's place),
+  // their status rows [hbase, hbase + rules) of the kernel's LDS (KV_RSTRIDE bytes each), the
+  // generation state of every rule that runs a program (a group: its representative's), and the
+  // hoist table of the lookups from the resource root.
+  struct Block {
+    Kern& kern;
+    const uint32_t hbase;
+    std::vector<uint32_t> rules;
+    std::vector<GInfo> ginfo;
+    std::map<uint32_t, size_t> gof;  // rule -> group
+    std::vector<RGen> gs;
+    HoistTable global;
+    size_t K = 0;  // stage loops of its deepest rule
+    Block(Kern& k, uint32_t hb) : kern(k), hbase(hb) {
+      global.prefix = "g";
+      global.fam = 0;
+      global.cell0 = "gw_";
+    }
+    uint32_t mask_words() const { return ((uint32_t)rules.size() + 31) / 32; }
+    // the generation state of the rule (or group representative) at block position q, if it has one
+    const RGen* at(uint32_t q) const {
+      for (const RGen& x : gs)
+        if (x.q == q) return &x;
+      return nullptr;
+    }
+    // the group whose representative `ri` is (nullptr: no group); member: `ri` is a later member
+    const GInfo* group_of(uint32_t ri, bool* member) const {
+      auto it = gof.find(ri);
+      *member = it != gof.end() && ginfo[it->second].members[0] != ri;
+      return it == gof.end() ? nullptr : &ginfo[it->second];
+    }
+  };
+
+  void emit_region(Block& B, RGen& g, const Region& R, std::ostream& w) {
     const std::string& s = g.s;
     auto C = [&](uint32_t d) { return "c" + std::to_string(d) + s; };
     auto L = [&](uint32_t pc) { return "R" + std::to_string(g.ri) + "_L" + std::to_string(pc); };
@@ -1101,7 +1154,7 @@ struct Gen {
       if (t >= R.rb && t < R.jre) return "goto " + L(t) + ";";
       if (R.kind == 0 && t >= R.jre) {
         g.resume.insert(t);
-        (err ? g.seg_err_jumps : g.seg_jumps).insert(t);
+        (err ? R.err_jumps : R.jumps)->insert(t);
         return "{ rs" + s + " = " + u32(t) + "; goto " + R.se + "; }";
       }
       throw std::runtime_error("kvjit: jump out of a fused region (rule " + std::to_string(g.ri) + ")");
@@ -1172,9 +1225,15 @@ struct Gen {
     };
     auto table_for = [&](uint32_t d) -> HoistTable* {
       const std::string& ex = g.expr[d];
-      if (ex[0] == 'R') return gT;
+      if (ex[0] == 'R') return &B.global;
       if (R.T && ex.compare(0, R.troot.size(), R.troot) == 0) return R.T;
       return nullptr;
+    };
+    // "the node at depth d is absent or its type <cmp>": a hoisted node carries its absence as
+    // type 0; otherwise the cursor is tested before the node it points at is read
+    auto absent_or = [&](uint32_t d, const char* cmp) {
+      const std::string test = "node_type(" + NODE(d) + ".kt) " + cmp;
+      return known(d) ? test : C(d) + " == ABSENT || " + test;
     };
     auto set_unknown = [&](uint32_t from) {
       for (uint32_t x = from; x < g.expr.size(); x++) g.expr[x].clear();
@@ -1199,6 +1258,14 @@ struct Gen {
     };
     const std::string ek = "ek" + s;
     const std::string kindof = "(" + ek + " & 15u)";
+    // a fresh anyPattern alternative: no error, no anchor seen
+    const std::string alt_reset =
+        "  " + ek + " = 0u;" + (g.uses_anchor ? " areg" + s + " = 0ull; apres" + s + " = 0ull;" : "") + "\n";
+    // the next element of the per-rule loop at level `lv`, while there is one: back to its body
+    auto next_elem = [&](const std::string& lv, const std::string& cur, uint32_t body) {
+      return "  if (li" + lv + s + " + 1u < ll" + lv + s + ") { li" + lv + s + "++; " + cur + " = ni(lf" + lv + s + " + li" + lv +
+             s + "); " + jump(body) + " }\n";
+    };
 
     for (uint32_t pc = R.rb; pc < R.re; pc++) {
       const Inst& in = ps.prog[pc];
@@ -1206,48 +1273,26 @@ struct Gen {
       const std::string cd = C(d), cn = C(d + 1);
       const uint32_t lv = aux & 3;
       const std::string L_lv = std::to_string(lv);
-      std::ostringstream w;
-      OpOut oo;  // this op's code and, for the fast-path guards, its exit condition / assignments
       w << L(pc) << ":;\n";
       switch (op) {
         case OP_MAPCHK:
-        case OP_ARRCHK: {
-          const char* t = op == OP_MAPCHK ? "NT_MAP" : "NT_ARR";
-          if (known(d)) {
-            w << "  if (node_type(" << NODE(d) << ".kt) != " << t << ") ";
-          } else {
-            IDX(d);
-            w << "  if (" << cd << " == ABSENT || node_type(N[" << cd << "].kt) != " << t << ") ";
-          }
-          w << raise(op == OP_MAPCHK ? E_TYPE_MAP : E_TYPE_ARR, in.a, in.c) << "\n";
+          w << "  if (" << absent_or(d, "!= NT_MAP") << ") " << raise(E_TYPE_MAP, in.a, in.c) << "\n";
           break;
-        }
+        case OP_ARRCHK:
+          w << "  if (" << absent_or(d, "!= NT_ARR") << ") " << raise(E_TYPE_ARR, in.a, in.c) << "\n";
+          break;
         case OP_AREG: {
           const std::string bit = "(1ull << " + std::to_string(aux & 63) + ")";
-          const bool h = known(d) && table_for(d);
-          const std::string st = "  areg" + s + " |= " + bit + "; if (" + lookup(d, in.a, aux, false) + " != ABSENT) apres" +
-                                 s + " |= " + bit + ";\n";
-          w << st;
-          if (h) {
-          }
+          w << "  areg" << s << " |= " << bit << "; if (" << lookup(d, in.a, aux, false) << " != ABSENT) apres" << s
+            << " |= " << bit << ";\n";
           break;
         }
-        case OP_KEY: {
-          const bool h = known(d) && table_for(d);
-          std::string x = lookup(d, in.a, aux, true);
-          w << "  " << cn << " = " << x << "; if (" << cn << " == ABSENT) " << jump(in.b) << "\n";
-          if (h) {
-          }
+        case OP_KEY:
+          w << "  " << cn << " = " << lookup(d, in.a, aux, true) << "; if (" << cn << " == ABSENT) " << jump(in.b) << "\n";
           break;
-        }
-        case OP_KEYV: {
-          const bool h = known(d) && table_for(d);
-          std::string x = lookup(d, in.a, aux, true);
-          w << "  " << cn << " = " << x << ";\n";
-          if (h) {
-          }
+        case OP_KEYV:
+          w << "  " << cn << " = " << lookup(d, in.a, aux, true) << ";\n";
           break;
-        }
         case OP_KEYGLOB:
           if (G) throw std::runtime_error("kvjit: KEYGLOB in a rule group");
           set_unknown(d + 1);
@@ -1256,9 +1301,7 @@ struct Gen {
             << u32(in.c) << ", &nd_, &kn" << s << ")) " << jump(in.b) << " " << cn << " = nd_; }\n";
           break;
         case OP_SCOPE_END:
-          if (G) {  // groups carry no pending error (decided where raised)
-            break;
-          }
+          if (G) break;  // groups carry no pending error (decided where raised)
           if (in.c == 0) w << "  if (" << kindof << ") " << ek << " |= " << u32(aux << 4) << ";\n";
           else w << "  if (" << kindof << ") { " << ek << " |= " << u32(aux << 4) << "; " << jump(in.c, true) << " }\n";
           break;
@@ -1267,22 +1310,11 @@ struct Gen {
           w << "  if (" << kindof << ") { if (" << ek << " & " << u32(EF_COND << 4) << ") " << ek << " = 0u; else "
             << jump(in.c, true) << " }\n";
           break;
-        case OP_NEG: {
-          const bool h = known(d) && table_for(d);
-          const std::string x = lookup(d, in.a, aux, false);
-          w << "  if (" << x << " != ABSENT) " << raise(E_NEG, in.b, in.c) << "\n";
-          if (h) {
-          }
+        case OP_NEG:
+          w << "  if (" << lookup(d, in.a, aux, false) << " != ABSENT) " << raise(E_NEG, in.b, in.c) << "\n";
           break;
-        }
         case OP_STAR:
-          if (known(d + 1)) {
-            w << "  if (node_type(" << NODE(d + 1) << ".kt) == NT_NULL) ";
-          } else {
-            IDX(d + 1);
-            w << "  if (" << cn << " == ABSENT || node_type(N[" << cn << "].kt) == NT_NULL) ";
-          }
-          w << raise(E_STAR, in.b, in.c) << "\n";
+          w << "  if (" << absent_or(d + 1, "== NT_NULL") << ") " << raise(E_STAR, in.b, in.c) << "\n";
           break;
         case OP_LEAF: {
           // one bit of the leaf's table word (a group: one bit per member, consecutive): hoisted
@@ -1311,12 +1343,8 @@ struct Gen {
             w << "  { const uint32_t f_ = " << al << " & ~((" << wx << " >> " << u32(slot % 32) << ") & " << hex32(mask)
               << ");\n    if (f_) { " << gfin("f_", E_VALUE, in.b, in.c) << " " << al << " &= ~f_; if (!" << al << ") "
               << gdone() << " } }\n";
-            if (T) {
-            }
           } else {
             w << "  if (!(((" << wx << " >> " << u32(slot % 32) << ") & 1u) != 0u)) " << raise(E_VALUE, in.b, in.c) << "\n";
-            if (T) {
-            }
           }
           break;
         }
@@ -1335,23 +1363,13 @@ struct Gen {
           w << "  " << raise(in.b, in.a, in.c) << "\n";
           break;
         case OP_EXISTCHK:
-          if (known(d)) {
-            w << "  if (node_type(" << NODE(d) << ".kt) != NT_ARR) ";
-          } else {
-            IDX(d);
-            w << "  if (" << cd << " == ABSENT || node_type(N[" << cd << "].kt) != NT_ARR) ";
-          }
-          w << raise(E_EXIST_RESTYPE, in.a, in.c) << "\n";
+          w << "  if (" << absent_or(d, "!= NT_ARR") << ") " << raise(E_EXIST_RESTYPE, in.a, in.c) << "\n";
           break;
         case OP_LENCHK:
           w << "  if (" << NODE(d, CU_WIDE | CU_B) << ".b < " << u32(in.a) << ") " << raise(E_LEN, in.b, in.c) << "\n";
-          if (known(d)) {
-          }
           break;
         case OP_INDEX:
           w << "  " << cn << " = ni(" << NODE(d, CU_WIDE) << ".a + " << u32(in.a) << ");\n";
-          if (known(d)) {
-          }
           set_unknown(d + 1);
           break;
         case OP_LOOP_BEGIN:
@@ -1374,34 +1392,25 @@ struct Gen {
           if (!G)  // groups carry no pending error
             w << "  if (" << kindof << ") { if (" << ek << " & " << u32(EF_COND << 4) << ") " << ek << " = 0u; else "
               << jump(in.c, true) << " }\n";
-          w << "  if (li" << L_lv << s << " + 1u < ll" << L_lv << s << ") { li" << L_lv << s << "++; " << cn << " = ni(lf"
-            << L_lv << s << " + li" << L_lv << s << "); " << jump(in.a + 1) << " }\n";
+          w << next_elem(L_lv, cn, in.a + 1);
           set_unknown(d + 1);
           break;
         case OP_EXIST_END:
           if (G) throw std::runtime_error("kvjit: EXIST in a rule group");
           w << "  if (!" << kindof << ") " << jump(pc + 1) << "\n  " << ek << " = 0u;\n"
-            << "  if (li" << L_lv << s << " + 1u < ll" << L_lv << s << ") { li" << L_lv << s << "++; " << cn << " = ni(lf"
-            << L_lv << s << " + li" << L_lv << s << "); " << jump(in.a + 1) << " }\n"
-            << "  " << raise(E_EXIST_FAIL, in.b, in.c) << "\n";
+            << next_elem(L_lv, cn, in.a + 1) << "  " << raise(E_EXIST_FAIL, in.b, in.c) << "\n";
           set_unknown(d + 1);
           break;
         case OP_ALT_BEGIN:
           if (G) throw std::runtime_error("kvjit: anyPattern in a rule group");
-          w << "  " << ek << " = 0u;";
-          if (g.uses_anchor) w << " areg" << s << " = 0ull; apres" << s << " = 0ull;";
-          w << "\n";
+          w << alt_reset;
           break;
         case OP_ALT_END:
           if (G) throw std::runtime_error("kvjit: anyPattern in a rule group");
           w << "  if (" << kindof << " == 0u) " << finish("ST_PASS") << "\n  if (" << kindof << " == E_CPU) "
             << finish("ST_CPU") << "\n";
           if (in.b) w << "  " << finish("ST_FAIL") << "\n";
-          else {
-            w << "  " << ek << " = 0u;";
-            if (g.uses_anchor) w << " areg" << s << " = 0ull; apres" << s << " = 0ull;";
-            w << "\n";
-          }
+          else w << alt_reset;
           break;
         case OP_DONE:  // the MatchPattern epilogue as one select chain (no per-lane branches)
           if (R.kind != 0) throw std::runtime_error("kvjit: rule end inside a fused loop");
@@ -1417,10 +1426,7 @@ struct Gen {
         default:  // OP_NOP, OP_METACHK (handled per resource by RF_BAD_META)
           break;
       }
-      oo.code = w.str();
-      outs.push_back(std::move(oo));
     }
-    for (const auto& x : outs) wout << x.code;
   }
 
   RGen analyze(uint32_t ri) {
@@ -1513,15 +1519,19 @@ struct Gen {
   // targets relative to the program start; the pattern nodes and leaf predicates are left out
   // (listed in pns / preds, the LEAF pcs relative to the start in leafpcs). Empty when the
   // program holds an op a group cannot run: condition anchors (errors cleared later), existence
-  // anchors, anyPattern, wildcard keys, pattern variables.
-  std::string group_form(uint32_t ri, std::vector<uint32_t>* preds, std::vector<uint32_t>* pns,
-                         std::vector<uint32_t>* leafpcs) const {
+  // anchors, anyPattern, wildcard keys, pattern variables. Computed once per rule and image.
+  const Form& form_of(uint32_t ri) {
+    const auto [it, fresh] = forms.try_emplace(ri);
+    if (fresh) group_form(ri, &it->second);
+    return it->second;
+  }
+  void group_form(uint32_t ri, Form* F) const {
     const RuleRec& rr = ps.rules[ri];
     // (pattern-variable rules stay out of groups: their substitution status is decided per
     // member before the walk, and a group's record layout may be per resource slot)
     // (nor rules with preconditions: their gate is applied per rule before the walk)
     // (nor deny rules: they have no program)
-    if (rr.route != 0 || rr.dyn || rr.pre || rr.deny) return "";
+    if (rr.route != 0 || rr.dyn || rr.pre || rr.deny) return;
     const uint32_t b = rr.prog, e = prog_end(ps, b);
     std::ostringstream f;
     auto rel = [&](uint32_t t) { return (int64_t)t - (int64_t)b; };
@@ -1531,44 +1541,39 @@ struct Gen {
       f << (in.op & 0xFFFFFFu) << ':';  // op | depth << 8 | aux << 16
       switch (op) {
         case OP_MAPCHK:
-        case OP_ARRCHK: pns->push_back(in.a); f << rel(in.c); break;
+        case OP_ARRCHK: F->pns.push_back(in.a); f << rel(in.c); break;
         case OP_AREG:
         case OP_KEYV:
         case OP_INDEX: f << in.a; break;
         case OP_KEY: f << in.a << ',' << rel(in.b); break;
         case OP_SCOPE_END:
-          if (aux & EF_COND) return "";
+          if (aux & EF_COND) return;
           f << (in.c ? rel(in.c) : -1);
           break;
-        case OP_NEG: f << in.a << ','; pns->push_back(in.b); f << rel(in.c); break;
-        case OP_STAR: pns->push_back(in.b); f << rel(in.c); break;
+        case OP_NEG: f << in.a << ','; F->pns.push_back(in.b); f << rel(in.c); break;
+        case OP_STAR: F->pns.push_back(in.b); f << rel(in.c); break;
         case OP_LEAF:
-          preds->push_back(in.a);
-          leafpcs->push_back(pc - b);
-          pns->push_back(in.b);
+          F->preds.push_back(in.a);
+          F->leafpcs.push_back(pc - b);
+          F->pns.push_back(in.b);
           f << rel(in.c);
           break;
-        case OP_RAISE: f << in.b << ','; pns->push_back(in.a); f << rel(in.c); break;
-        case OP_LENCHK: f << in.a << ','; pns->push_back(in.b); f << rel(in.c); break;
+        case OP_RAISE: f << in.b << ','; F->pns.push_back(in.a); f << rel(in.c); break;
+        case OP_LENCHK: f << in.a << ','; F->pns.push_back(in.b); f << rel(in.c); break;
         case OP_LOOP_BEGIN: f << rel(in.a); break;
         case OP_LOOP_END: f << rel(in.a) << ',' << rel(in.c); break;
         case OP_DONE:
         case OP_NOP:
         case OP_METACHK: break;
-        default: return "";
+        default: return;
       }
       f << ';';
     }
-    return f.str();
+    F->text = f.str();
   }
 
-  // Match bits (kv_mtup_kernel): the rule at LDS row q of the kernel being generated has bit
-  // position 32 * mt_kbase + q; mt_bits[p] = the rule at bit position p (KV_SENT: padding).
-  // A rule whose match reads the resource name is evaluated per resource behind its bit (which
-  // the tuple kernel sets to 1).
-  uint32_t mt_kbase = 0;
-  std::vector<uint32_t> mt_bits;
-  std::vector<uint8_t> rec_slot;  // rules whose records go to their resource slot (kGslotMembers)
+  // A rule whose match reads the resource name is evaluated per resource behind its match bit
+  // (which the tuple kernel sets to 1).
   bool name_dependent(uint32_t ri) const {
     const RuleRec& rr = ps.rules[ri];
     for (uint32_t f = rr.m_first; f < rr.m_first + rr.m_count; f++)
@@ -1577,480 +1582,493 @@ struct Gen {
       if (ps.filters[f].flags & (MF_NAME | MF_NAMES)) return true;
     return false;
   }
-  std::string mt_cond(uint32_t ri, uint32_t row) const {
-    const uint32_t p = mt_kbase * 32u + row;
+  // the match of rule ri at LDS row `row` of kernel `kn`: its bit of the kernel's match words
+  std::string mt_cond(const Kern& kn, uint32_t ri, uint32_t row) const {
+    const uint32_t p = kn.mt_kbase * 32u + row;
     std::string c = "((mw" + std::to_string(p / 32u) + " >> " + std::to_string(p % 32u) + "u) & 1u)";
     if (name_dependent(ri)) c += " && g_match_" + std::to_string(ri) + "(P, B, R, rkind, rflags)";
     return c;
   }
 
-  uint32_t gtab_n = 0;          // member tables emitted so far (per generated program text)
-  std::string block_decls;      // declarations the current kernel's blocks need (member tables)
+  // ================================================================ one fused block
+  // The code of one fused block inside a kernel body (its own C++ scope), in passes over a Block
+  // (fused_block, at the end, runs them): form_groups, prepare_rules, per stage emit_segment and
+  // emit_fused_loops, emit_rule_state; all over the status and record emitters.
+  //
+  // Lean rules: at the end of stage segment k a rule that enters stage loop k keeps only one bit
+  // (am<k>_<w>, bit q of its block position), one that jumps past the loop one bit of sk<k>_<w>
+  // (its single target), and one that finished stores its status at once; inside the fused loop
+  // its error state is local to the element and an element that fails decides the status there
+  // (post_chain), so no per-rule register lives across the loop. After the loops the resume pc is
+  // rebuilt from the bits.
 
-  // Code block of one fused chunk inside a kernel body (its own C++ scope); the
-  // chunk's status rows are s_stw rows [hbase, hbase + rules) (KV_RSTRIDE bytes each).
-  //
-  // Lean rules (hist_lds kernels): at the end of stage segment k a rule that enters stage
-  // loop k keeps only one bit (am<k>_<w>, bit q of its block position), one that jumps past
-  // the loop one bit of sk<k>_<w> (its single target), and one that finished stores its
-  // status at once; inside the fused loop its error state is local to the element and an
-  // element that fails decides the status there (post_chain), so no per-rule register lives
-  // across the loop. After the loops the resume pc is rebuilt from the bits.
-  //
-  // Rule groups (hist_lds kernels): rules of one structural form (group_form) whose pattern
-  // nodes differ by one constant run the representative's program once, with one bit per
-  // member; their leaf predicates take consecutive bits of one table word, so a leaf tests
-  // every member with one shift and mask. The members take consecutive block positions.
-  // `order` receives the block's rules in block position order.
-  std::string fused_block(const JitChunk& ch_in, uint32_t hbase, std::vector<uint32_t>* order) {
-    struct GInfo {
-      std::vector<uint32_t> members, pns0, leafpcs;
-      std::vector<uint32_t> dpn;                 // pattern-node shift of each member
-      std::vector<std::vector<uint32_t>> preds;  // leaf predicates of each member
-    };
-    std::vector<GInfo> ginfo;
-    std::map<uint32_t, size_t> gof;  // rule -> group
-    if (hist_lds) {
-      std::map<std::string, size_t> open;
-      for (uint32_t ri : ch_in.rules) {
-        std::vector<uint32_t> pr, pn, lp;
-        const std::string f = group_form(ri, &pr, &pn, &lp);
-        if (f.empty()) continue;
-        auto it = open.find(f);
-        if (it != open.end()) {
-          GInfo& G = ginfo[it->second];
-          const uint32_t dp = pn.empty() ? 0u : pn[0] - G.pns0[0];
-          bool ok = G.members.size() < 32;
-          for (size_t i = 0; i < pn.size() && ok; i++) ok = pn[i] - G.pns0[i] == dp;
-          if (ok) {
-            G.members.push_back(ri);
-            G.dpn.push_back(dp);
-            G.preds.push_back(pr);
-            gof[ri] = it->second;
-            continue;
-          }
+  void form_groups(const std::vector<uint32_t>& rules_in, Block* B) {
+    std::map<std::string, size_t> open;  // form -> the group that still takes members
+    for (uint32_t ri : rules_in) {
+      const Form& F = form_of(ri);
+      if (F.text.empty()) continue;
+      auto it = open.find(F.text);
+      if (it != open.end()) {
+        GInfo& G = B->ginfo[it->second];
+        const uint32_t dp = F.pns.empty() ? 0u : F.pns[0] - G.pns0[0];
+        bool ok = G.members.size() < 32;
+        for (size_t i = 0; i < F.pns.size() && ok; i++) ok = F.pns[i] - G.pns0[i] == dp;
+        if (ok) {
+          G.members.push_back(ri);
+          G.dpn.push_back(dp);
+          G.preds.push_back(F.preds);
+          B->gof[ri] = it->second;
+          continue;
         }
-        GInfo G;
-        G.members = {ri};
-        G.pns0 = pn;
-        G.leafpcs = lp;
-        G.dpn = {0u};
-        G.preds = {pr};
-        open[f] = ginfo.size();
-        gof[ri] = ginfo.size();
-        ginfo.push_back(std::move(G));
       }
+      GInfo G;
+      G.members = {ri};
+      G.pns0 = F.pns;
+      G.leafpcs = F.leafpcs;
+      G.dpn = {0u};
+      G.preds = {F.preds};
+      open[F.text] = B->ginfo.size();
+      B->gof[ri] = B->ginfo.size();
+      B->ginfo.push_back(std::move(G));
     }
-    JitChunk ch;  // block order: a group's members together, at its first member's place
-    for (uint32_t ri : ch_in.rules) {
-      auto it = gof.find(ri);
-      if (it == gof.end()) ch.rules.push_back(ri);
-      else if (ginfo[it->second].members[0] == ri)
-        ch.rules.insert(ch.rules.end(), ginfo[it->second].members.begin(), ginfo[it->second].members.end());
+    // block order: a group's members together, at its first member's place
+    for (uint32_t ri : rules_in) {
+      bool member;
+      const GInfo* G = B->group_of(ri, &member);
+      if (!G) B->rules.push_back(ri);
+      else if (!member) B->rules.insert(B->rules.end(), G->members.begin(), G->members.end());
     }
-    *order = ch.rules;
-    const uint32_t nr = (uint32_t)ch.rules.size();
-    std::vector<RGen> gs;
-    HoistTable global;
-    global.prefix = "g";
-    global.fam = 0;
-    global.cell0 = "gw_";
-    gT = &global;
-    size_t K = 0;
-    for (uint32_t q = 0; q < nr; q++) {
-      const uint32_t ri = ch.rules[q];
+  }
+
+  // The group state of representative `g` (at block position g->q): its site descriptor, its
+  // members' record layout, their leaf predicates and slots, its member table. Every id here
+  // (kern.gsn, gs_members, the memo slots, gtab_n) is handed out in call order.
+  void prepare_group(const GInfo& G, Block* B, RGen* gp) {
+    RGen& g = *gp;
+    Kern& kern = B->kern;
+    g.grp = true;
+    g.s = "_G" + std::to_string(B->hbase + g.q);
+    g.gn = (uint32_t)G.members.size();
+    g.gri = G.members;
+    g.gdpn = G.dpn;
+    if (g.gn >= 2u) {
+      g.gsite = true;
+      g.gl = kern.gsn++;
+      g.gpre = gs_members;
+      gs_desc.insert(gs_desc.end(), {g.gn, gs_members, (uint32_t)(gs_mem.size() / 2u), 0u});
+      for (uint32_t j = 0; j < g.gn; j++) gs_mem.insert(gs_mem.end(), {G.members[j], G.dpn[j]});
+      gs_members += g.gn;
+    }
+    // (site-record members get their records expanded to their resource slots at fetch)
+    if (g.gsite || g.gn >= kGslotMembers)
+      for (uint32_t m : G.members) rec_slot.at(m) = 1;
+    g.grow = B->hbase + g.q;
+    for (const auto& m : G.preds)
+      for (uint32_t pi : m) pred_fn(pi);
+    for (size_t i = 0; i < G.leafpcs.size(); i++) {
+      std::vector<uint32_t> lp;
+      for (const auto& m : G.preds) lp.push_back(m[i]);
+      g.gslot[g.b + G.leafpcs[i]] = group_slots(lp);
+    }
+    // members as arithmetic progressions (rule ids, node shifts), else a table
+    bool arith = true;
+    g.gsri = g.gn > 1 ? g.gri[1] - g.gri[0] : 0u;
+    g.gspn = g.gn > 1 ? g.gdpn[1] : 0u;
+    for (uint32_t j = 0; j < g.gn && arith; j++) arith = g.gri[j] == g.gri[0] + j * g.gsri && g.gdpn[j] == j * g.gspn;
+    if (!arith) {
+      g.gtab = "kvg_t" + std::to_string(gtab_n++);
+      std::ostringstream t;
+      t << "__device__ const uint32_t " << g.gtab << "[" << 2 * g.gn << "] = {";
+      for (uint32_t j = 0; j < g.gn; j++) t << u32(g.gri[j]) << ", ";
+      for (uint32_t j = 0; j < g.gn; j++) t << u32(g.gdpn[j]) << (j + 1 < g.gn ? ", " : "");
+      t << "};\n";
+      kern.decls += t.str();
+    }
+  }
+
+  void prepare_rules(Block* B) {
+    for (uint32_t q = 0; q < B->rules.size(); q++) {
+      const uint32_t ri = B->rules[q];
       if (no_program(ps.rules[ri])) continue;
-      auto git = gof.find(ri);
-      if (git != gof.end() && ginfo[git->second].members[0] != ri) continue;  // a group member
+      bool member;
+      const GInfo* G = B->group_of(ri, &member);
+      if (member) continue;  // runs as one bit of its group's representative
       RGen g = analyze(ri);
       g.q = q;
       for (uint32_t pc = g.b; pc <= g.e; pc++)
         if ((ps.prog[pc].op & 0xFF) == OP_LEAF) pred_fn(ps.prog[pc].a);
-      if (git != gof.end()) {
-        const GInfo& G = ginfo[git->second];
-        g.grp = true;
-        g.s = "_G" + std::to_string(hbase + q);
-        g.gn = (uint32_t)G.members.size();
-        g.gri = G.members;
-        g.gdpn = G.dpn;
-        if (g.gn >= 2u) {
-          g.gsite = true;
-          g.gl = k_gsn++;
-          g.gpre = gs_members;
-          gs_desc.insert(gs_desc.end(), {g.gn, gs_members, (uint32_t)(gs_mem.size() / 2u), 0u});
-          for (uint32_t j = 0; j < g.gn; j++) gs_mem.insert(gs_mem.end(), {G.members[j], G.dpn[j]});
-          gs_members += g.gn;
-        }
-        // (site-record members get their records expanded to their resource slots at fetch)
-        if (g.gsite || g.gn >= kGslotMembers)
-          for (uint32_t m : G.members) rec_slot.at(m) = 1;
-        g.grow = hbase + q;
-        for (const auto& m : G.preds)
-          for (uint32_t pi : m) pred_fn(pi);
-        for (size_t i = 0; i < G.leafpcs.size(); i++) {
-          std::vector<uint32_t> lp;
-          for (const auto& m : G.preds) lp.push_back(m[i]);
-          g.gslot[g.b + G.leafpcs[i]] = group_slots(lp);
-        }
-        // members as arithmetic progressions (rule ids, node shifts), else a table
-        bool arith = true;
-        g.gsri = g.gn > 1 ? g.gri[1] - g.gri[0] : 0u;
-        g.gspn = g.gn > 1 ? g.gdpn[1] : 0u;
-        for (uint32_t j = 0; j < g.gn && arith; j++) arith = g.gri[j] == g.gri[0] + j * g.gsri && g.gdpn[j] == j * g.gspn;
-        if (!arith) {
-          g.gtab = "kvg_t" + std::to_string(gtab_n++);
-          std::ostringstream t;
-          t << "__device__ const uint32_t " << g.gtab << "[" << 2 * g.gn << "] = {";
-          for (uint32_t j = 0; j < g.gn; j++) t << u32(g.gri[j]) << ", ";
-          for (uint32_t j = 0; j < g.gn; j++) t << u32(g.gdpn[j]) << (j + 1 < g.gn ? ", " : "");
-          t << "};\n";
-          block_decls += t.str();
-        }
-      }
-      K = std::max(K, g.loops.size());
+      if (G) prepare_group(*G, B, &g);
+      B->K = std::max(B->K, g.loops.size());
       g.lean.assign(g.loops.size(), 0);
       g.post_flags.assign(g.loops.size(), 0);
       g.post_alt.assign(g.loops.size(), 0);
       g.skip_to.assign(g.loops.size(), 0xFFFFFFFFu);
-      g.skip_flags.assign(g.loops.size(), 0);
-      g.skip_alt.assign(g.loops.size(), 0);
-      gs.push_back(std::move(g));
+      B->gs.push_back(std::move(g));
     }
-    const uint32_t nw = (nr + 31) / 32;
-    auto mword = [&](const char* m, size_t k, uint32_t q) {
-      return std::string(m) + std::to_string(k) + "_" + std::to_string(q / 32);
-    };
-    auto mbit = [&](uint32_t q) { return u32(1u << (q % 32)); };
-    // status row of block position q: its LDS address and row index
-    auto row = [&](uint32_t q) { return "s_w + " + u32(KV_ROW0 + (hbase + q) * KV_RSTRIDE) + ", " + u32(hbase + q); };
-    // EState of rule g from its registers (error kind / flags / pattern node in `ekx`)
-    auto estate = [&](const RGen* g, const std::string& ekx) {
-      std::ostringstream k;
-      if (!g) return std::string("EState e_{0u, 0u, 0u, ABSENT, ABSENT, 0u, 0u, 0u, 0u};");
-      k << "EState e_{" << ekx << " & 15u, (" << ekx << " >> 4) & 15u, " << ekx << " >> 8, "
-        << (g->uses_keyglob ? "ekn" + g->s : std::string("ABSENT")) << ", ABSENT";
-      for (uint32_t lv = 0; lv < 4; lv++) k << ", " << (lv <= g->max_level ? "ei" + std::to_string(lv) + g->s : "0u");
-      k << "};";
-      return k.str();
-    };
-    // status + error record of rule `ri` (block position q): LDS status byte (copied to the
-    // status matrix at the end of the kernel) + the error record, or the ballot histogram
-    auto store_st = [&](uint32_t q, const RGen* g, const std::string& st, const std::string& ekx) {
-      const uint32_t ri = ch.rules[q];
-      std::ostringstream k;
-      k << "  { " << estate(g, ekx) << "\n";
-      if (hist_lds)
-        k << "    kv_final(O, " << ri << "u, n_res, r, valid, " << st << ", e_, " << row(q) << "); }\n";
-      else
-        k << "    store_result2(O, " << ri << "u, n_res, r, valid, " << st << ", e_, &s_hist[" << (hbase + q)
-          << "][0]); }\n";
-      return k.str();
-    };
-    auto store = [&](uint32_t q) {
-      const RGen* g = nullptr;
-      for (const RGen& x : gs)
-        if (x.q == q) g = &x;
-      const std::string s = g ? g->s : "_" + std::to_string(ch.rules[q]);
-      const std::string st = "rs" + s + " & 0xFFu";
-      if (!g) return store_st(q, g, st, "0u");
-      // the members alive at a group's end passed: their PASS was staged by the match code
-      // (a group ends only at DONE, ST_PASS, or with every member decided, ST_STORED_)
-      if (g->grp) return std::string();
-      return "  if ((rs" + s + " & 0xFFu) != ST_STORED_" + (hist_lds ? std::string(" && (rs" + s + " & 0xFFu) != ST_NOMATCH") : "") +
-             ") {\n" + store_st(q, g, st, "ek" + s) + "  }\n";
-    };
-    // match / route of rule q (rs = its first pc, or FIN | status); of a group: every member's,
-    // the matched ones alive (al), the others stored
-    auto match_code = [&](uint32_t q) {
-      const RGen* gp = nullptr;
-      for (const RGen& x : gs)
-        if (x.q == q && x.grp) gp = &x;
-      if (gp) {
-        // a group's members are consecutive rows, so their match bits are consecutive bits of the
-        // block's match words: one extract instead of a branch per member. Statuses are staged
-        // here, branch-free: PASS for every member that runs (a failure overwrites its byte where
-        // it is raised, so the group's end stores nothing), CPU for the members an anchor-error
-        // phrase or a panicking labels / annotations shape routes (rows start as NOMATCH; 0xFF
-        // past the batch)
-        const RGen& g = *gp;
-        std::ostringstream k;
-        const uint32_t p0 = mt_kbase * 32u + g.grow, w0 = p0 / 32u, s0 = p0 % 32u;
-        const uint32_t mask = g.gn >= 32 ? 0xFFFFFFFFu : (1u << g.gn) - 1u;
-        k << "  { uint32_t mt_ = ((mw" << w0 << " >> " << s0 << "u)";
-        if (s0 + g.gn > 32u) k << " | (mw" << (w0 + 1) << " << " << (32u - s0) << "u)";
-        k << ") & " << hex32(mask) << ";\n";
-        for (uint32_t j = 0; j < g.gn; j++)
-          if (name_dependent(g.gri[j]))
-            k << "    if (((mt_ >> " << j << "u) & 1u) && !g_match_" << g.gri[j] << "(P, B, R, rkind, rflags)) mt_ &= "
-              << hex32(~(1u << j)) << ";\n";
-        k << "    uint32_t cpu_ = (rflags & RF_MAGIC) ? mt_ : 0u;\n";
-        for (uint32_t j = 0; j < g.gn; j++) {
-          const RuleRec& rr = ps.rules[g.gri[j]];
-          if (rr.flags & RR_META_EXPAND)
-            k << "    cpu_ |= (rflags & " << u32(meta_bad_flags(rr.flags)) << ") ? (mt_ & " << u32(1u << j) << ") : 0u;\n";
-        }
-        for (uint32_t j = 0; j < g.gn; j++)
-          k << "    s_w[" << u32(KV_ROW0 + (g.grow + j) * KV_RSTRIDE) << " + threadIdx.x] = valid ? (uint8_t)(((mt_ >> " << j
-            << "u) & 1u) ? (((cpu_ >> " << j << "u) & 1u) ? ST_CPU : ST_PASS) : ST_NOMATCH) : (uint8_t)0xFFu;\n";
-        k << "    al" << g.s << " = mt_ & ~cpu_; }\n";
-        k << "  rs" << g.s << " = al" << g.s << " ? " << u32(g.b) << " : FIN_ | ST_STORED_;\n";
-        return k.str();
-      }
-      const uint32_t ri = ch.rules[q];
-      const RuleRec& rr = ps.rules[ri];
-      const std::string s = "_" + std::to_string(ri);
-      std::ostringstream k;
-      k << "  if (" << mt_cond(ri, hbase + q) << ") {\n";
-      switch (rr.route) {
-        case 1: k << "    rs" << s << " = FIN_ | ST_CPU;\n"; break;
-        case 2: k << "    rs" << s << " = FIN_ | ST_NOMATCH;\n"; break;
-        case 3: k << "    rs" << s << " = FIN_ | " << u32(rr.const_status) << ";\n"; break;
-        default:
-          k << "    if (rflags & RF_MAGIC) rs" << s << " = FIN_ | ST_CPU;\n";
-          if (rr.flags & RR_META_EXPAND)
-            k << "    else if (rflags & " << u32(meta_bad_flags(rr.flags)) << ") rs" << s << " = FIN_ | ST_CPU;\n";
-          if (rr.pre)  // preconditions precede pattern substitution (validation.go:175-193)
-            k << "    else if (B.pre_st[(size_t)" << (rr.pre - 1) << "u * n_res + r]) rs" << s << " = FIN_ | B.pre_st[(size_t)"
-              << (rr.pre - 1) << "u * n_res + r];\n";
-          if (rr.dyn)
-            k << "    else if (B.dyn_st[(size_t)" << (rr.dyn - 1) << "u * n_res + r]) rs" << s << " = FIN_ | B.dyn_st[(size_t)"
-              << (rr.dyn - 1) << "u * n_res + r];\n";
-          if (rr.deny)  // validate.deny (validation.go:195-197): the fold's plane is the status
-            k << "    else rs" << s << " = FIN_ | B.deny_st[(size_t)" << (rr.deny - 1) << "u * n_res + r];\n";
-          else
-            k << "    else rs" << s << " = " << u32(rr.prog) << ";\n";
-          break;
-      }
-      k << "  }\n";
-      return k.str();
-    };
-    std::ostringstream body;  // everything after the per-rule declarations
-    for (size_t k = 0; k <= K; k++) {
-      std::ostringstream seg;  // the stage-k segments of every rule
-      for (RGen& g : gs) {
-        if (k > g.loops.size()) continue;
-        const uint32_t sb = k == 0 ? g.b : g.loops[k - 1].second + 1;
-        const uint32_t se = k < g.loops.size() ? g.loops[k].first + 1 : g.e + 1;  // include the LOOP_BEGIN
-        Region R;
-        R.kind = 0;
-        R.rb = sb;
-        R.re = se;
-        R.jre = se;
-        R.se = "R" + std::to_string(g.ri) + "_S" + std::to_string(k);
-        std::ostringstream w;
-        g.seg_jumps.clear();
-        g.seg_err_jumps.clear();
-        emit_region(g, R, w);
-        if (k == 0) seg << match_code(g.q);  // just before its first segment: rs is born here
-        if (k > 0 && g.lean[k - 1]) {  // resume pc of a lean rule from its stage-(k-1) bits
-          const uint32_t le = g.loops[k - 1].second;
-          seg << "  rs" << g.s << " = (" << mword("am", k - 1, g.q) << " & " << mbit(g.q) << ") ? " << u32(le + 1) << " : ";
-          if (g.skip_to[k - 1] != 0xFFFFFFFFu)
-            seg << "(" << mword("sk", k - 1, g.q) << " & " << mbit(g.q) << ") ? " << u32(g.skip_to[k - 1]) << " : ";
-          seg << "FIN_ | ST_STORED_;\n";
-          // the error state of a lane that left the loop clean (no register of the rule lives
-          // across the loop)
-          seg << "  ek" << g.s << " = 0u;";
-          for (uint32_t lv = 0; lv <= g.max_level && lv < 4; lv++) seg << " ei" << lv << g.s << " = 0u;";
-          if (g.uses_keyglob) seg << " ekn" << g.s << " = ABSENT;";
-          seg << "\n";
-        }
-        seg << "  // rule " << g.ri << " stage " << k << "\n  switch (rs" << g.s << ") {\n";
-        if (k == 0) seg << "    case " << u32(g.b) << ": goto R" << g.ri << "_L" << g.b << ";\n";
-        for (uint32_t t : g.resume)
-          if (t >= sb && t < se) seg << "    case " << u32(t) << ": goto R" << g.ri << "_L" << t << ";\n";
-        seg << "    default: goto " << R.se << ";\n  }\n" << w.str() << R.se << ":;\n";
-        if (k == g.loops.size()) {
-          seg << store(g.q);  // the rule has finished for every lane
-          continue;
-        }
-        // stage loop k follows: lean when the kernel stages statuses in LDS, the post chain of
-        // the loop is pure, and the segment leaves at most one way past the loop, whose chain
-        // is pure for any pending error (a lane that jumps there with an error is decided at
-        // once; one without resumes there after the loop)
-        const uint32_t le = g.loops[k].second;
-        const PostChain pcn = post_chain(g, ps.prog[le].c);
-        // every way past loop k: this segment's jumps and the targets of earlier stages that lie
-        // beyond this segment (they pass through it)
-        std::set<uint32_t> okset = g.seg_jumps, errset = g.seg_err_jumps;
-        for (uint32_t t : g.carry_ok)
-          if (t >= se) okset.insert(t);
-        for (uint32_t t : g.carry_err)
-          if (t >= se) errset.insert(t);
-        bool lean = hist_lds && pcn.pure && okset.size() <= 1;
-        std::vector<std::pair<uint32_t, PostChain>> errc;  // chains of the error targets
-        for (uint32_t t : errset) {
-          errc.push_back({t, post_chain(g, t, true)});
-          lean &= errc.back().second.pure;
-        }
-        bool alt0 = !errc.empty() && errc[0].second.alt;
-        for (auto& e : errc) lean &= e.second.alt == alt0;
-        g.carry_ok = okset;
-        if (lean) {
-          g.carry_err.clear();  // errors past the loop are decided at the segment end
-        } else {
-          g.carry_ok.insert(le + 1);
-          g.carry_err = errset;
-          g.carry_err.insert(ps.prog[le].c);
-        }
-        g.lean[k] = lean;
-        g.post_flags[k] = pcn.flags;
-        g.post_alt[k] = pcn.alt;
-        if (!lean) continue;
-        const std::string ek = "ek" + g.s;
-        seg << "  if (rs" << g.s << " & ACT_) " << mword("am", k, g.q) << " |= " << mbit(g.q) << ";\n";
-        if (!okset.empty() || !errc.empty()) {
-          // past the loop: with an error the status is decided now, else resume there later
-          seg << "  else if (rs" << g.s << " < FIN_) {\n";
-          if (!errc.empty()) {
-            std::string fl = "0u";
-            for (auto it = errc.rbegin(); it != errc.rend(); ++it)
-              fl = "(rs" + g.s + " == " + u32(it->first) + " ? " + u32(it->second.flags << 4) + " : " + fl + ")";
-            const std::string ekx = "(" + ek + " | " + fl + ")";
-            seg << "    if (" << ek << " & 15u) {\n" << store_st(g.q, &g, done_status(g, ekx, alt0), ekx) << "    }\n";
-          }
-          if (!okset.empty()) {
-            g.skip_to[k] = *okset.begin();
-            seg << "    " << (errc.empty() ? "" : "else ") << mword("sk", k, g.q) << " |= " << mbit(g.q) << ";\n";
-          }
-          seg << "  }\n";
-        }
-        seg << "  else {\n" << store(g.q) << "  }\n";
-      }
-      if (k < K) {  // stage-k masks of the lean rules
-        std::ostringstream mk;
-        mk << "  uint32_t";
-        for (uint32_t w = 0; w < nw; w++) mk << (w ? "," : "") << " am" << k << "_" << w << " = 0u, sk" << k << "_" << w << " = 0u";
-        mk << ";\n";
-        body << mk.str();
-      }
-      body << global.flush() << seg.str();
-      if (k == K) break;
-      // fused loops of stage k: group rules by the symbolic array cursor
-      std::map<std::string, std::vector<RGen*>> groups;
-      std::vector<std::string> order;
-      for (RGen& g : gs) {
-        if (k >= g.loops.size()) continue;
-        const uint32_t lb = g.loops[k].first;
-        const uint32_t d = (ps.prog[lb].op >> 8) & 0xFF;
-        std::string key = g.expr[d].empty() ? "U" + std::to_string(g.ri) : g.expr[d];
-        if (!groups.count(key)) order.push_back(key);
-        groups[key].push_back(&g);
-      }
-      uint32_t li = 0;
-      for (const std::string& key : order) {
-        std::vector<RGen*>& grp = groups[key];
-        const std::string tag = std::to_string(k) + "_" + std::to_string(li++);
-        const RGen& g0 = *grp[0];
-        const uint32_t d0 = (ps.prog[g0.loops[k].first].op >> 8) & 0xFF;
-        const std::string arr_node = key[0] == 'U' ? "N[c" + std::to_string(d0) + g0.s + "]" : g0.hv[d0].node;
-        if (key[0] == 'U') {
-          for (const auto& cj : g0.csrc.at(d0)) col_mark(cj.first, cj.second, CU_WIDE);
-        } else {
-          col_mark(g0.hv[d0].fam, g0.hv[d0].j, CU_WIDE | CU_B);  // an_.a / .b / .c below
-        }
-        HoistTable T;
-        T.prefix = "l" + tag + "_";
-        const std::string troot = "E" + tag;
-        // the elements' lookups from the columns of the array's family (the array must be a
-        // column itself: its cell carries the offset of its element rows)
-        const uint32_t fam = key[0] == 'R' && fams[0].idx.count(key) ? family(key) : kNoCol;
-        if (fam != kNoCol) {
-          T.fam = (int)fam;
-          T.troot = troot;
-          T.cell0 = "ec" + tag;
-        }
-        std::ostringstream bodies;
-        std::vector<uint32_t> gmask(nw, 0);  // lean rules of the group, per mask word
-        for (RGen* gp : grp) {
-          RGen& g = *gp;
-          const uint32_t lb = g.loops[k].first, le = g.loops[k].second;
-          const uint32_t d = (ps.prog[lb].op >> 8) & 0xFF;
-          g.expr[d + 1] = troot;
-          g.hv[d + 1] = HVar{"el" + tag, "eln" + tag, fam != kNoCol ? (int)fam : -1, fam != kNoCol ? 0u : kNoCol};
-          Region R;
-          R.kind = 1;
-          R.rb = lb + 1;
-          R.re = le;  // LOOP_END emitted below
-          R.jre = le + 1;
-          R.li0 = "fli" + tag;
-          R.T = &T;
-          R.troot = troot;
-          std::ostringstream w;
-          emit_region(g, R, w);
-          const Inst& end = ps.prog[le];
-          if (end.c <= le) throw std::runtime_error("kvjit: loop exit target inside the loop");
-          const std::string ek = "ek" + g.s;
-          if (g.grp) {  // errors were decided where raised: a group with no member left stops
-            const std::string act = g.lean[k] ? mword("am", k, g.q) + " & " + mbit(g.q) : "rs" + g.s + " & ACT_";
-            if (g.lean[k]) gmask[g.q / 32] |= 1u << (g.q % 32);
-            bodies << "    if (" << act << ") {\n      c" << (d + 1) << g.s << " = el" << tag << ";\n"
-                   << w.str() << "R" << g.ri << "_L" << le << ":;\n      if (!al" << g.s << ") ";
-            if (g.lean[k]) bodies << mword("am", k, g.q) << " &= ~" << mbit(g.q) << ";\n    }\n";
-            else bodies << "rs" << g.s << " = FIN_ | ST_STORED_;\n    }\n";
-          } else if (g.lean[k]) {
-            gmask[g.q / 32] |= 1u << (g.q % 32);
-            // element-local error state; an error that leaves the loop decides the status now
-            bodies << "    if (" << mword("am", k, g.q) << " & " << mbit(g.q) << ") {\n      " << ek << " = 0u;";
-            for (uint32_t lv = 0; lv <= g.max_level && lv < 4; lv++) bodies << " ei" << lv << g.s << " = 0u;";
-            if (g.uses_keyglob) bodies << " ekn" << g.s << " = ABSENT;";
-            bodies << "\n      c" << (d + 1) << g.s << " = el" << tag << ";\n"
-                   << w.str() << "R" << g.ri << "_L" << le << ":;\n"
-                   << "      if (" << ek << " & 15u) { if (" << ek << " & " << u32(EF_COND << 4) << ") " << ek
-                   << " = 0u; else {\n        " << mword("am", k, g.q) << " &= ~" << mbit(g.q) << ";\n";
-            const std::string ekx = g.post_flags[k] ? "(" + ek + " | " + u32(g.post_flags[k] << 4) + ")" : ek;
-            bodies << "  " << store_st(g.q, &g, done_status(g, ekx, g.post_alt[k]), ekx) << "      } }\n    }\n";
-          } else {
-            bodies << "    if (rs" << g.s << " & ACT_) {\n      c" << (d + 1) << g.s << " = el" << tag << ";\n"
-                   << w.str() << "R" << g.ri << "_L" << le << ":;\n"
-                   << "      if (" << ek << " & 15u) { if (" << ek << " & " << u32(EF_COND << 4) << ") " << ek
-                   << " = 0u; else rs" << g.s << " = " << u32(end.c) << "; }\n    }\n";
-            g.resume.insert(end.c);
-          }
-          g.resume.insert(le + 1);
-          for (uint32_t x = d + 1; x < g.expr.size(); x++) g.expr[x].clear();  // loop-local exprs end here
-        }
-        body << "  { // fused loop " << tag << " over " << key << " (" << grp.size() << " rules)\n"
-             << "    uint32_t fn" << tag << " = 0u, ff" << tag << " = 0u, fe" << tag << " = 0u;\n    if (((0u";
-        for (RGen* gp : grp)
-          if (!gp->lean[k]) body << " | rs" << gp->s;
-        body << ") & ACT_)";
-        for (uint32_t w = 0; w < nw; w++)
-          if (gmask[w]) body << " | (am" << k << "_" << w << " & " << u32(gmask[w]) << ")";
-        body << ") { const Node an_ = " << arr_node << "; ff" << tag << " = an_.a; fn" << tag << " = an_.b; fe" << tag
-             << " = an_.c; }\n";
-        body << "    for (uint32_t fli" << tag << " = 0u; fli" << tag << " < fn" << tag << "; fli" << tag << "++) {\n"
-             << "      const uint32_t el" << tag << " = ni(ff" << tag << " + fli" << tag << ");\n";
-        if (fam != kNoCol)  // the element's column-0 cell: element row fe + i of its family
-          body << "      const uint32_t ec" << tag << " = fe" << tag << " + fli" << tag << " * KVC_W" << fam
-               << ";\n      const Node eln" << tag << " = " << col_macro("LD", fam, 0) << "(ec" << tag << ");\n";
-        else
-          body << "      const Node eln" << tag << " = N[el" << tag << "];\n";
-        body << T.flush() << bodies.str() << "    }\n";
-        for (RGen* gp : grp)
-          if (!gp->lean[k]) body << "    rs" << gp->s << " &= ~ACT_;\n";
-        body << "  }\n";
-      }
-    }
-    // every resume pc must lie in a segment (else the rule would never finish)
-    for (const RGen& g : gs)
-      for (uint32_t t : g.resume) {
-        bool ok = false;
-        for (size_t k = 0; k <= g.loops.size() && !ok; k++) {
-          const uint32_t sb = k == 0 ? g.b : g.loops[k - 1].second + 1;
-          const uint32_t se = k < g.loops.size() ? g.loops[k].first + 1 : g.e + 1;
-          ok = t >= sb && t < se;
-        }
-        if (!ok) throw std::runtime_error("kvjit: resume target " + std::to_string(t) + " of rule " +
-                                         std::to_string(g.ri) + " is not in a segment");
-      }
+  }
 
+  // ---------------------------------------------------------------- status and record emitters
+  // word / bit of block position q in the stage-k masks `m` ("am": active in the loop, "sk":
+  // jumped past it)
+  static std::string mword(const char* m, size_t k, uint32_t q) {
+    return std::string(m) + std::to_string(k) + "_" + std::to_string(q / 32);
+  }
+  static std::string mbit(uint32_t q) { return u32(1u << (q % 32)); }
+  // status row of block position q: its LDS address and row index
+  static std::string row(const Block& B, uint32_t q) {
+    return "s_w + " + u32(KV_ROW0 + (B.hbase + q) * KV_RSTRIDE) + ", " + u32(B.hbase + q);
+  }
+  // "no error pending" in rule g's registers
+  static std::string clear_err(const RGen& g) {
+    std::string c = "ek" + g.s + " = 0u;";
+    for (uint32_t lv = 0; lv <= g.max_level && lv < 4; lv++) c += " ei" + std::to_string(lv) + g.s + " = 0u;";
+    if (g.uses_keyglob) c += " ekn" + g.s + " = ABSENT;";
+    return c;
+  }
+  // EState of rule g from its registers (error kind / flags / pattern node in `ekx`)
+  static std::string estate(const RGen* g, const std::string& ekx) {
+    if (!g) return "EState e_{0u, 0u, 0u, ABSENT, ABSENT, 0u, 0u, 0u, 0u};";
     std::ostringstream k;
-    // per-rule state (rules of other routes only carry rs = FIN | status); a group's: rs and the
-    // alive members
-    for (uint32_t ri : ch.rules)
-      if (!gof.count(ri)) k << "  uint32_t rs_" << ri << " = FIN_ | ST_NOMATCH;\n";
-    for (const RGen& g : gs) {
+    k << "EState e_{" << ekx << " & 15u, (" << ekx << " >> 4) & 15u, " << ekx << " >> 8, "
+      << (g->uses_keyglob ? "ekn" + g->s : std::string("ABSENT")) << ", ABSENT";
+    for (uint32_t lv = 0; lv < 4; lv++) k << ", " << (lv <= g->max_level ? "ei" + std::to_string(lv) + g->s : "0u");
+    k << "};";
+    return k.str();
+  }
+  // status `st` + error record of the rule at block position q: its LDS status byte (copied to the
+  // status matrix when the kernel ends) and the record (kv_final)
+  std::string store_st(const Block& B, uint32_t q, const RGen* g, const std::string& st, const std::string& ekx) const {
+    std::ostringstream k;
+    k << "  { " << estate(g, ekx) << "\n    kv_final(O, " << B.rules[q] << "u, n_res, r, valid, " << st << ", e_, "
+      << row(B, q) << "); }\n";
+    return k.str();
+  }
+  // the final status in rs of the rule at block position q, unless it was stored already or is
+  // NOMATCH (the rows' prefill)
+  std::string store(const Block& B, uint32_t q) const {
+    const RGen* g = B.at(q);
+    const std::string s = g ? g->s : "_" + std::to_string(B.rules[q]);
+    const std::string st = "rs" + s + " & 0xFFu";
+    if (!g) return store_st(B, q, g, st, "0u");
+    // the members alive at a group's end passed: their PASS was staged by the match code
+    // (a group ends only at DONE, ST_PASS, or with every member decided, ST_STORED_)
+    if (g->grp) return std::string();
+    return "  if ((rs" + s + " & 0xFFu) != ST_STORED_ && (rs" + s + " & 0xFFu) != ST_NOMATCH) {\n" +
+           store_st(B, q, g, st, "ek" + s) + "  }\n";
+  }
+  // match / route of the rule at block position q (rs = its first pc, or FIN | status); of a
+  // group: every member's, the matched ones alive (al), the others stored
+  std::string match_code(const Block& B, uint32_t q) const {
+    const RGen* g = B.at(q);
+    return g && g->grp ? group_match_code(B, *g) : rule_match_code(B, q);
+  }
+  std::string group_match_code(const Block& B, const RGen& g) const {
+    // a group's members are consecutive rows, so their match bits are consecutive bits of the
+    // block's match words: one extract instead of a branch per member. Statuses are staged
+    // here, branch-free: PASS for every member that runs (a failure overwrites its byte where
+    // it is raised, so the group's end stores nothing), CPU for the members an anchor-error
+    // phrase or a panicking labels / annotations shape routes (rows start as NOMATCH; 0xFF
+    // past the batch)
+    std::ostringstream k;
+    const uint32_t p0 = B.kern.mt_kbase * 32u + g.grow, w0 = p0 / 32u, s0 = p0 % 32u;
+    const uint32_t mask = g.gn >= 32 ? 0xFFFFFFFFu : (1u << g.gn) - 1u;
+    k << "  { uint32_t mt_ = ((mw" << w0 << " >> " << s0 << "u)";
+    if (s0 + g.gn > 32u) k << " | (mw" << (w0 + 1) << " << " << (32u - s0) << "u)";
+    k << ") & " << hex32(mask) << ";\n";
+    for (uint32_t j = 0; j < g.gn; j++)
+      if (name_dependent(g.gri[j]))
+        k << "    if (((mt_ >> " << j << "u) & 1u) && !g_match_" << g.gri[j] << "(P, B, R, rkind, rflags)) mt_ &= "
+          << hex32(~(1u << j)) << ";\n";
+    k << "    uint32_t cpu_ = (rflags & RF_MAGIC) ? mt_ : 0u;\n";
+    for (uint32_t j = 0; j < g.gn; j++) {
+      const RuleRec& rr = ps.rules[g.gri[j]];
+      if (rr.flags & RR_META_EXPAND)
+        k << "    cpu_ |= (rflags & " << u32(meta_bad_flags(rr.flags)) << ") ? (mt_ & " << u32(1u << j) << ") : 0u;\n";
+    }
+    for (uint32_t j = 0; j < g.gn; j++)
+      k << "    s_w[" << u32(KV_ROW0 + (g.grow + j) * KV_RSTRIDE) << " + threadIdx.x] = valid ? (uint8_t)(((mt_ >> " << j
+        << "u) & 1u) ? (((cpu_ >> " << j << "u) & 1u) ? ST_CPU : ST_PASS) : ST_NOMATCH) : (uint8_t)0xFFu;\n";
+    k << "    al" << g.s << " = mt_ & ~cpu_; }\n";
+    k << "  rs" << g.s << " = al" << g.s << " ? " << u32(g.b) << " : FIN_ | ST_STORED_;\n";
+    return k.str();
+  }
+  std::string rule_match_code(const Block& B, uint32_t q) const {
+    const uint32_t ri = B.rules[q];
+    const RuleRec& rr = ps.rules[ri];
+    const std::string s = "_" + std::to_string(ri);
+    std::ostringstream k;
+    k << "  if (" << mt_cond(B.kern, ri, B.hbase + q) << ") {\n";
+    switch (rr.route) {
+      case 1: k << "    rs" << s << " = FIN_ | ST_CPU;\n"; break;
+      case 2: k << "    rs" << s << " = FIN_ | ST_NOMATCH;\n"; break;
+      case 3: k << "    rs" << s << " = FIN_ | " << u32(rr.const_status) << ";\n"; break;
+      default:
+        k << "    if (rflags & RF_MAGIC) rs" << s << " = FIN_ | ST_CPU;\n";
+        if (rr.flags & RR_META_EXPAND)
+          k << "    else if (rflags & " << u32(meta_bad_flags(rr.flags)) << ") rs" << s << " = FIN_ | ST_CPU;\n";
+        if (rr.pre)  // preconditions precede pattern substitution (validation.go:175-193)
+          k << "    else if (B.pre_st[(size_t)" << (rr.pre - 1) << "u * n_res + r]) rs" << s << " = FIN_ | B.pre_st[(size_t)"
+            << (rr.pre - 1) << "u * n_res + r];\n";
+        if (rr.dyn)
+          k << "    else if (B.dyn_st[(size_t)" << (rr.dyn - 1) << "u * n_res + r]) rs" << s << " = FIN_ | B.dyn_st[(size_t)"
+            << (rr.dyn - 1) << "u * n_res + r];\n";
+        if (rr.deny)  // validate.deny (validation.go:195-197): the fold's plane is the status
+          k << "    else rs" << s << " = FIN_ | B.deny_st[(size_t)" << (rr.deny - 1) << "u * n_res + r];\n";
+        else
+          k << "    else rs" << s << " = " << u32(rr.prog) << ";\n";
+        break;
+    }
+    k << "  }\n";
+    return k.str();
+  }
+
+  // ---------------------------------------------------------------- stage segments
+  // ops [first, end) of rule g's stage-k segment: from the start (or the end of stage loop k - 1)
+  // to the LOOP_BEGIN of stage loop k (included), or to DONE
+  static std::pair<uint32_t, uint32_t> segment(const RGen& g, size_t k) {
+    return {k == 0 ? g.b : g.loops[k - 1].second + 1, k < g.loops.size() ? g.loops[k].first + 1 : g.e + 1};
+  }
+
+  // Is rule g lean in stage loop k? Decided when its stage-k segment has been emitted, from the
+  // targets past the segment that it jumps to without / with a pending error. Lean when the post
+  // chain of the loop is pure and the segment leaves at most one way past the loop, whose chain is
+  // pure for any pending error (a lane that jumps there with an error is decided at once; one
+  // without resumes there after the loop).
+  struct LeanDecision {
+    bool lean = false;
+    bool alt = false;                                  // the error chains end at the last anyPattern alternative
+    PostChain post;                                    // chain of the loop's own catch target
+    std::set<uint32_t> okset;                          // every way past the loop without an error
+    std::vector<std::pair<uint32_t, PostChain>> errc;  // ... with one: target and its chain
+    std::set<uint32_t> carry_ok, carry_err;            // RGen::carry_ok / carry_err after this stage
+  };
+  LeanDecision lean_decision(const RGen& g, size_t k, const std::set<uint32_t>& jumps,
+                             const std::set<uint32_t>& err_jumps) const {
+    LeanDecision D;
+    const uint32_t se = segment(g, k).second, le = g.loops[k].second;
+    D.post = post_chain(g, ps.prog[le].c);
+    // every way past loop k: this segment's jumps and the targets of earlier stages that lie
+    // beyond this segment (they pass through it)
+    D.okset = jumps;
+    std::set<uint32_t> errset = err_jumps;
+    for (uint32_t t : g.carry_ok)
+      if (t >= se) D.okset.insert(t);
+    for (uint32_t t : g.carry_err)
+      if (t >= se) errset.insert(t);
+    D.lean = D.post.pure && D.okset.size() <= 1;
+    for (uint32_t t : errset) {
+      D.errc.push_back({t, post_chain(g, t, true)});
+      D.lean &= D.errc.back().second.pure;
+    }
+    D.alt = !D.errc.empty() && D.errc[0].second.alt;
+    for (auto& e : D.errc) D.lean &= e.second.alt == D.alt;
+    D.carry_ok = D.okset;
+    if (!D.lean) {  // (a lean rule's errors past the loop are decided at the segment end)
+      D.carry_ok.insert(le + 1);
+      D.carry_err = errset;
+      D.carry_err.insert(ps.prog[le].c);
+    }
+    return D;
+  }
+
+  // the end of a lean rule's stage-k segment: its bit of the stage masks, or its status at once
+  void lean_exit(const Block& B, RGen& g, size_t k, const LeanDecision& D, std::ostream& seg) const {
+    const std::string ek = "ek" + g.s;
+    seg << "  if (rs" << g.s << " & ACT_) " << mword("am", k, g.q) << " |= " << mbit(g.q) << ";\n";
+    if (!D.okset.empty() || !D.errc.empty()) {
+      // past the loop: with an error the status is decided now, else resume there later
+      seg << "  else if (rs" << g.s << " < FIN_) {\n";
+      if (!D.errc.empty()) {
+        std::string fl = "0u";
+        for (auto it = D.errc.rbegin(); it != D.errc.rend(); ++it)
+          fl = "(rs" + g.s + " == " + u32(it->first) + " ? " + u32(it->second.flags << 4) + " : " + fl + ")";
+        const std::string ekx = "(" + ek + " | " + fl + ")";
+        seg << "    if (" << ek << " & 15u) {\n" << store_st(B, g.q, &g, done_status(g, ekx, D.alt), ekx) << "    }\n";
+      }
+      if (!D.okset.empty()) {
+        g.skip_to[k] = *D.okset.begin();
+        seg << "    " << (D.errc.empty() ? "" : "else ") << mword("sk", k, g.q) << " |= " << mbit(g.q) << ";\n";
+      }
+      seg << "  }\n";
+    }
+    seg << "  else {\n" << store(B, g.q) << "  }\n";
+  }
+
+  // rule g's stage-k segment: (stage 0) its match code, (after a lean loop) its resume pc from
+  // the mask bits, the dispatch on rs, the ops; then its status when the rule ends here, else the
+  // lean decision for stage loop k and a lean rule's exit
+  void emit_segment(Block& B, RGen& g, size_t k, std::ostream& seg) {
+    const auto [sb, se] = segment(g, k);
+    Region R;
+    R.kind = 0;
+    R.rb = sb;
+    R.re = se;
+    R.jre = se;
+    R.se = "R" + std::to_string(g.ri) + "_S" + std::to_string(k);
+    std::set<uint32_t> jumps, err_jumps;
+    R.jumps = &jumps;
+    R.err_jumps = &err_jumps;
+    std::ostringstream w;
+    emit_region(B, g, R, w);
+    if (k == 0) seg << match_code(B, g.q);  // just before its first segment: rs is born here
+    if (k > 0 && g.lean[k - 1]) {  // resume pc of a lean rule from its stage-(k-1) bits
+      const uint32_t le = g.loops[k - 1].second;
+      seg << "  rs" << g.s << " = (" << mword("am", k - 1, g.q) << " & " << mbit(g.q) << ") ? " << u32(le + 1) << " : ";
+      if (g.skip_to[k - 1] != 0xFFFFFFFFu)
+        seg << "(" << mword("sk", k - 1, g.q) << " & " << mbit(g.q) << ") ? " << u32(g.skip_to[k - 1]) << " : ";
+      seg << "FIN_ | ST_STORED_;\n";
+      // the error state of a lane that left the loop clean (no register of the rule lives
+      // across the loop)
+      seg << "  " << clear_err(g) << "\n";
+    }
+    seg << "  // rule " << g.ri << " stage " << k << "\n  switch (rs" << g.s << ") {\n";
+    if (k == 0) seg << "    case " << u32(g.b) << ": goto R" << g.ri << "_L" << g.b << ";\n";
+    for (uint32_t t : g.resume)
+      if (t >= sb && t < se) seg << "    case " << u32(t) << ": goto R" << g.ri << "_L" << t << ";\n";
+    seg << "    default: goto " << R.se << ";\n  }\n" << w.str() << R.se << ":;\n";
+    if (k == g.loops.size()) {
+      seg << store(B, g.q);  // the rule has finished for every lane
+      return;
+    }
+    const LeanDecision D = lean_decision(g, k, jumps, err_jumps);
+    g.carry_ok = D.carry_ok;
+    g.carry_err = D.carry_err;
+    g.lean[k] = D.lean;
+    g.post_flags[k] = D.post.flags;
+    g.post_alt[k] = D.post.alt;
+    if (D.lean) lean_exit(B, g, k, D, seg);
+  }
+
+  // ---------------------------------------------------------------- fused loops
+  // One fused loop of stage k: the array its rules walk, the element's names (el / eln / ec / fli
+  // + tag) and the hoist table of the lookups from the element
+  struct Loop {
+    size_t k = 0;
+    std::string tag, troot;
+    uint32_t fam = kNoCol;  // the family of the array's elements (kNoCol: walk the node rows)
+    HoistTable T;
+  };
+
+  // Rule g's body of stage loop k inside fused loop L. Every form tests whether the rule is active
+  // in the loop, points its cursor at the element, runs the region and lands on the LOOP_END's
+  // label; the ending differs: a group stops when no member is left; a lean rule's error is local
+  // to the element and one that leaves the loop decides the status now; a plain rule carries its
+  // error out of the loop in rs.
+  void loop_body(Block& B, RGen& g, Loop& L, std::ostream& out) {
+    const size_t k = L.k;
+    const uint32_t lb = g.loops[k].first, le = g.loops[k].second;
+    const uint32_t d = (ps.prog[lb].op >> 8) & 0xFF;
+    g.expr[d + 1] = L.troot;
+    g.hv[d + 1] = HVar{"el" + L.tag, "eln" + L.tag, L.fam != kNoCol ? (int)L.fam : -1, L.fam != kNoCol ? 0u : kNoCol};
+    Region R;
+    R.kind = 1;
+    R.rb = lb + 1;
+    R.re = le;  // LOOP_END emitted below
+    R.jre = le + 1;
+    R.li0 = "fli" + L.tag;
+    R.T = &L.T;
+    R.troot = L.troot;
+    std::ostringstream w;
+    emit_region(B, g, R, w);
+    const Inst& end = ps.prog[le];
+    if (end.c <= le) throw std::runtime_error("kvjit: loop exit target inside the loop");
+    const bool lean = g.lean[k];
+    const std::string ek = "ek" + g.s, rs = "rs" + g.s, am = mword("am", k, g.q), bit = mbit(g.q);
+    out << "    if (" << (lean ? am + " & " + bit : rs + " & ACT_") << ") {\n";
+    if (lean && !g.grp) out << "      " << clear_err(g) << "\n";  // element-local error state
+    out << "      c" << (d + 1) << g.s << " = el" << L.tag << ";\n" << w.str() << "R" << g.ri << "_L" << le << ":;\n";
+    if (g.grp) {  // errors were decided where raised: a group with no member left stops
+      out << "      if (!al" << g.s << ") " << (lean ? am + " &= ~" + bit : rs + " = FIN_ | ST_STORED_") << ";\n";
+    } else {
+      out << "      if (" << ek << " & 15u) { if (" << ek << " & " << u32(EF_COND << 4) << ") " << ek << " = 0u; else ";
+      if (lean) {  // an error that leaves the loop decides the status now
+        const std::string ekx = g.post_flags[k] ? "(" + ek + " | " + u32(g.post_flags[k] << 4) + ")" : ek;
+        out << "{\n        " << am << " &= ~" << bit << ";\n"
+            << "  " << store_st(B, g.q, &g, done_status(g, ekx, g.post_alt[k]), ekx) << "      } }\n";
+      } else {
+        out << rs << " = " << u32(end.c) << "; }\n";
+        g.resume.insert(end.c);
+      }
+    }
+    out << "    }\n";
+    g.resume.insert(le + 1);
+    for (uint32_t x = d + 1; x < g.expr.size(); x++) g.expr[x].clear();  // loop-local exprs end here
+  }
+
+  // the fused loop `tag` of stage k over the array at symbolic cursor `key` ("U<ri>": unknown,
+  // one rule's own), walked once for the rules `grp`
+  void emit_fused_loop(Block& B, size_t k, const std::string& key, const std::vector<RGen*>& grp, const std::string& tag,
+                       std::ostream& body) {
+    const RGen& g0 = *grp[0];
+    const uint32_t d0 = (ps.prog[g0.loops[k].first].op >> 8) & 0xFF;
+    const std::string arr_node = key[0] == 'U' ? "N[c" + std::to_string(d0) + g0.s + "]" : g0.hv[d0].node;
+    if (key[0] == 'U') {
+      for (const auto& cj : g0.csrc.at(d0)) col_mark(cj.first, cj.second, CU_WIDE);
+    } else {
+      col_mark(g0.hv[d0].fam, g0.hv[d0].j, CU_WIDE | CU_B);  // an_.a / .b / .c below
+    }
+    Loop L;
+    L.k = k;
+    L.tag = tag;
+    L.troot = "E" + tag;
+    L.T.prefix = "l" + tag + "_";
+    // the elements' lookups from the columns of the array's family (the array must be a
+    // column itself: its cell carries the offset of its element rows)
+    L.fam = key[0] == 'R' && fams[0].idx.count(key) ? family(key) : kNoCol;
+    if (L.fam != kNoCol) {
+      L.T.fam = (int)L.fam;
+      L.T.troot = L.troot;
+      L.T.cell0 = "ec" + tag;
+    }
+    std::ostringstream bodies;
+    for (RGen* gp : grp) loop_body(B, *gp, L, bodies);
+    std::vector<uint32_t> gmask(B.mask_words(), 0);  // lean rules of the loop, per mask word
+    for (const RGen* gp : grp)
+      if (gp->lean[k]) gmask[gp->q / 32] |= 1u << (gp->q % 32);
+    body << "  { // fused loop " << tag << " over " << key << " (" << grp.size() << " rules)\n"
+         << "    uint32_t fn" << tag << " = 0u, ff" << tag << " = 0u, fe" << tag << " = 0u;\n    if (((0u";
+    for (const RGen* gp : grp)
+      if (!gp->lean[k]) body << " | rs" << gp->s;
+    body << ") & ACT_)";
+    for (uint32_t w = 0; w < gmask.size(); w++)
+      if (gmask[w]) body << " | (am" << k << "_" << w << " & " << u32(gmask[w]) << ")";
+    body << ") { const Node an_ = " << arr_node << "; ff" << tag << " = an_.a; fn" << tag << " = an_.b; fe" << tag
+         << " = an_.c; }\n";
+    body << "    for (uint32_t fli" << tag << " = 0u; fli" << tag << " < fn" << tag << "; fli" << tag << "++) {\n"
+         << "      const uint32_t el" << tag << " = ni(ff" << tag << " + fli" << tag << ");\n";
+    if (L.fam != kNoCol)  // the element's column-0 cell: element row fe + i of its family
+      body << "      const uint32_t ec" << tag << " = fe" << tag << " + fli" << tag << " * KVC_W" << L.fam
+           << ";\n      const Node eln" << tag << " = " << col_macro("LD", L.fam, 0) << "(ec" << tag << ");\n";
+    else
+      body << "      const Node eln" << tag << " = N[el" << tag << "];\n";
+    body << L.T.flush() << bodies.str() << "    }\n";
+    for (const RGen* gp : grp)
+      if (!gp->lean[k]) body << "    rs" << gp->s << " &= ~ACT_;\n";
+    body << "  }\n";
+  }
+
+  // fused loops of stage k: the rules grouped by the symbolic cursor of the array their k-th
+  // stage loop walks, in order of first use
+  void emit_fused_loops(Block& B, size_t k, std::ostream& body) {
+    std::map<std::string, std::vector<RGen*>> groups;
+    std::vector<std::string> order;
+    for (RGen& g : B.gs) {
+      if (k >= g.loops.size()) continue;
+      const uint32_t d = (ps.prog[g.loops[k].first].op >> 8) & 0xFF;
+      const std::string key = g.expr[d].empty() ? "U" + std::to_string(g.ri) : g.expr[d];
+      if (!groups.count(key)) order.push_back(key);
+      groups[key].push_back(&g);
+    }
+    uint32_t li = 0;
+    for (const std::string& key : order) emit_fused_loop(B, k, key, groups[key], std::to_string(k) + "_" + std::to_string(li++), body);
+  }
+
+  // per-rule state (rules of other routes only carry rs = FIN | status); a group's: rs and the
+  // alive members
+  void emit_rule_state(const Block& B, std::ostream& k) const {
+    for (uint32_t ri : B.rules)
+      if (!B.gof.count(ri)) k << "  uint32_t rs_" << ri << " = FIN_ | ST_NOMATCH;\n";
+    for (const RGen& g : B.gs) {
       const std::string& s = g.s;
       if (g.grp) k << "  uint32_t rs" << s << " = FIN_ | ST_STORED_, al" << s << " = 0u;\n";
       k << "  uint32_t ek" << s << " = 0u";
@@ -2066,9 +2084,46 @@ struct Gen {
         k << (l ? "," : "") << " li" << l << s << " = 0u, lf" << l << s << " = 0u, ll" << l << s << " = 0u";
       k << ";\n";
     }
+  }
+
+  // every resume pc must lie in a segment (else the rule would never finish)
+  static void check_resumes(const Block& B) {
+    for (const RGen& g : B.gs)
+      for (uint32_t t : g.resume) {
+        bool ok = false;
+        for (size_t k = 0; k <= g.loops.size() && !ok; k++) ok = t >= segment(g, k).first && t < segment(g, k).second;
+        if (!ok) throw std::runtime_error("kvjit: resume target " + std::to_string(t) + " of rule " +
+                                         std::to_string(g.ri) + " is not in a segment");
+      }
+  }
+
+  // The code of the fused block of `rules_in` in kernel `kern`, whose status rows start at row
+  // `hbase` of the kernel; `order` receives the block's rules in block position order.
+  std::string fused_block(Kern& kern, const std::vector<uint32_t>& rules_in, uint32_t hbase, std::vector<uint32_t>* order) {
+    Block B(kern, hbase);
+    form_groups(rules_in, &B);
+    *order = B.rules;
+    prepare_rules(&B);
+    std::ostringstream body;  // everything after the per-rule declarations
+    for (size_t k = 0; k <= B.K; k++) {
+      std::ostringstream seg;  // the stage-k segments of every rule
+      for (RGen& g : B.gs)
+        if (k <= g.loops.size()) emit_segment(B, g, k, seg);
+      if (k < B.K) {  // stage-k masks of the lean rules
+        body << "  uint32_t";
+        for (uint32_t w = 0; w < B.mask_words(); w++)
+          body << (w ? "," : "") << " am" << k << "_" << w << " = 0u, sk" << k << "_" << w << " = 0u";
+        body << ";\n";
+      }
+      body << B.global.flush() << seg.str();  // (the segments' hoisted lookups ahead of them)
+      if (k < B.K) emit_fused_loops(B, k, body);
+    }
+    check_resumes(B);
+    std::ostringstream k;
+    emit_rule_state(B, k);
     // rules of other routes are final after match / route
-    for (uint32_t q = 0; q < nr; q++)
-      if (no_program(ps.rules[ch.rules[q]])) k << match_code(q) << store(q);
+    for (uint32_t q = 0; q < B.rules.size(); q++)
+      if (no_program(ps.rules[B.rules[q]])) k << match_code(B, q) << store(B, q);
     k << body.str();
     return k.str();
   }
@@ -2089,23 +2144,23 @@ struct Gen {
     const uint32_t g = 1280u, b = (kernel_lds(nr) + g - 1u) / g * g;
     return (int)std::max<uint32_t>(1u, (160u * 1024u) / std::max(b, g) * KV_RWAVES / 4u);
   }
-  std::vector<uint32_t> group_kernel(const std::string& name, const std::vector<const JitChunk*>& chs, int waves) {
+  // The kernel `name` of the blocks `chs` (each one's rules) at a bound of `waves` per SIMD
+  // (0: none); returns its rules in LDS-row order (blocks reorder rule-group members).
+  std::vector<uint32_t> group_kernel(const std::string& name, const std::vector<std::vector<uint32_t>>& chs, int waves) {
     std::vector<std::string> blocks;
     std::vector<std::pair<uint32_t, uint32_t>> rows;  // LDS rows [first, first + count) of each block
     std::vector<uint32_t> rules;
     uint32_t nr_all = 0;
-    for (const JitChunk* c : chs) nr_all += (uint32_t)c->rules.size();
-    hist_lds = true;
+    for (const auto& c : chs) nr_all += (uint32_t)c.size();
     // (the waves' record counters hold a byte per (wave, row): KV_KROWS rows)
     if (nr_all > KV_KROWS) throw std::runtime_error("kvjit: at most KV_KROWS rules per kernel (KVGPU_JIT_CHUNK)");
-    block_decls.clear();
-    mt_kbase = (uint32_t)(mt_bits.size() / 32u);
-    k_gs0 = (uint32_t)(gs_desc.size() / 4u);
-    k_gsn = 0;
-    for (const JitChunk* c : chs) {
+    Kern kern;
+    kern.mt_kbase = (uint32_t)(mt_bits.size() / 32u);
+    kern.gs0 = (uint32_t)(gs_desc.size() / 4u);
+    for (const auto& c : chs) {
       std::vector<uint32_t> ord;
-      rows.push_back({(uint32_t)rules.size(), (uint32_t)c->rules.size()});
-      blocks.push_back(fused_block(*c, (uint32_t)rules.size(), &ord));
+      rows.push_back({(uint32_t)rules.size(), (uint32_t)c.size()});
+      blocks.push_back(fused_block(kern, c, (uint32_t)rules.size(), &ord));
       rules.insert(rules.end(), ord.begin(), ord.end());
     }
     mt_bits.insert(mt_bits.end(), rules.begin(), rules.end());
@@ -2113,9 +2168,9 @@ struct Gen {
     const uint32_t nr = (uint32_t)rules.size();
     // a wave's lane l zeroes / writes the site-record counters of the kernel's group l (groups have
     // 2+ members and a kernel at most KV_KROWS rules: at most 64 groups)
-    if (k_gsn > 64u) throw std::runtime_error("kvjit: more than 64 site-record groups in one kernel");
-    KernelText kt(*this, name);
-    o << block_decls;
+    if (kern.gsn > 64u) throw std::runtime_error("kvjit: more than 64 site-record groups in one kernel");
+    std::ostringstream o;
+    o << kern.decls;
     if (opt.stamps) o << "__device__ unsigned long long* kvj_stamps;\n";
     o << "__device__ const uint32_t " << name << "_rules[" << nr << "] = {";
     for (uint32_t q = 0; q < nr; q++) o << (q ? ", " : "") << u32(rules[q]);
@@ -2128,7 +2183,7 @@ struct Gen {
       << "(const DevPS* __restrict__ Pp, const DevBatch* __restrict__ Bp, const Node* __restrict__ N, "
          "const Val* __restrict__ V, const uint8_t* __restrict__ S, DevOut O, uint32_t r0) {\n"
       << "  constexpr uint32_t FIN_ = " << u32(FIN) << ", ACT_ = " << u32(ACT) << ", ST_STORED_ = 0x7Eu;\n"
-      << "  __shared__ unsigned long long s_stq[" << kernel_lds(nr) / 8 + (KV_RWAVES * k_gsn + 1u) / 2u
+      << "  __shared__ unsigned long long s_stq[" << kernel_lds(nr) / 8 + (KV_RWAVES * kern.gsn + 1u) / 2u
       << "];\n  uint32_t* s_stw = (uint32_t*)s_stq;\n"
       << "  const DevPS& P = *Pp;\n  const DevBatch& B = *Bp;\n  const uint8_t* __restrict__ pstr = P.pstr;\n";
     // Workgroup b runs tile (b % 8) * n/8 + b / 8, so each XCD (blocks b, b+8, ... share one)
@@ -2155,7 +2210,7 @@ struct Gen {
       // site-record counters of the kernel's groups, [group][wave] after the rows (zeroed before
       // the prefill's barrier)
       << "  uint32_t* const s_gc_ = s_stw + " << u32(kernel_lds(nr) / 4u) << ";\n"
-      << (k_gsn ? "  for (uint32_t t_ = threadIdx.x; t_ < " + u32(KV_RWAVES * k_gsn) + "; t_ += KV_RWG) s_gc_[t_] = 0u;\n"
+      << (kern.gsn ? "  for (uint32_t t_ = threadIdx.x; t_ < " + u32(KV_RWAVES * kern.gsn) + "; t_ += KV_RWG) s_gc_[t_] = 0u;\n"
                 : std::string())
       << "  kv_prefill_rows(s_stw, " << nr << "u, r - threadIdx.x, n_res);\n";
     // diagnostics (KVGPU_JIT_STAMPS): a wave's shader clock at the start, after each block and
@@ -2171,7 +2226,7 @@ struct Gen {
       // the block's match words (bits of its rules, kv_mtup_kernel); a wave none of whose resources
       // matches any rule of the block skips it whole (every rule NOMATCH on every lane)
       const uint32_t r0 = rows[bi].first, rn = rows[bi].second;
-      const uint32_t p0 = mt_kbase * 32u + r0, p1 = p0 + rn;  // bit positions [p0, p1)
+      const uint32_t p0 = kern.mt_kbase * 32u + r0, p1 = p0 + rn;  // bit positions [p0, p1)
       o << "  {\n";
       std::string any = "0u";
       for (uint32_t w = p0 / 32u; w * 32u < p1; w++) {
@@ -2188,16 +2243,16 @@ struct Gen {
     // statuses to the status matrix, per-rule (and per-scope) histograms
     o << "  const uint32_t wg0_ = r - threadIdx.x;\n";
     // each wave's site-record counts (lane l: the kernel's group l)
-    if (k_gsn)
-      o << "#ifndef KVEMU\n  if ((KV_OFULL(O) & 2u) && !(KV_OFULL(O) & 4u) && (threadIdx.x & 63u) < " << u32(k_gsn)
-        << " && r - (threadIdx.x & 63u) < n_res)\n    O.gcnt[(size_t)(" << u32(k_gs0)
+    if (kern.gsn)
+      o << "#ifndef KVEMU\n  if ((KV_OFULL(O) & 2u) && !(KV_OFULL(O) & 4u) && (threadIdx.x & 63u) < " << u32(kern.gsn)
+        << " && r - (threadIdx.x & 63u) < n_res)\n    O.gcnt[(size_t)(" << u32(kern.gs0)
         << " + (threadIdx.x & 63u)) * ((n_res + 63u) >> 6) + (r >> 6)] = s_gc_[(threadIdx.x & 63u) * KV_RWAVES + (threadIdx.x >> 6)];\n#endif\n";
     o << "  kv_end_flush(O, s_stw, " << nr << "u, " << name << "_rules, n_res, r, valid, "
          "(KV_OFULL(O) & 8u) && valid ? O.scope[r] : 0xFFFFFFFFu, (KV_OFULL(O) & 8u) && wg0_ < n_res ? O.scope[wg0_] : 0xFFFFFFFFu, "
          "P.n_rules);\n";
     stamp(std::min<size_t>(blocks.size() + 1, kJitStamps - 1));
     o << "}\n\n";
-    hist_lds = false;
+    kernels.push_back({name, o.str()});
     return rules;
   }
 
@@ -2300,22 +2355,21 @@ struct Gen {
   }
   std::vector<uint32_t> initial_blocks_w(const std::vector<uint32_t>& sorted, uint32_t a, uint32_t e, uint32_t budget) {
     std::vector<uint32_t> out;
-    std::set<std::string> forms;
+    std::set<std::string> seen;  // forms of the run
     uint32_t cur = 0, w = 0;
     for (uint32_t q = a; q < e; q++) {
       const uint32_t ri = sorted[q];
-      std::vector<uint32_t> pr, pn, lp;
-      const std::string f = group_form(ri, &pr, &pn, &lp);
-      const uint32_t rw = !f.empty() && forms.count(f) ? 0u : rule_weight(ri);
-      if (cur > 0 && w + rw > budget) {
+      const std::string& f = form_of(ri).text;
+      const uint32_t rw = rule_weight(ri);
+      if (cur > 0 && w + (seen.count(f) ? 0u : rw) > budget) {  // the run is full: a new one
         out.push_back(cur);
         cur = 0;
         w = 0;
-        forms.clear();
+        seen.clear();
       }
       cur++;
-      w += !f.empty() && forms.count(f) ? 0u : rule_weight(ri);
-      if (!f.empty()) forms.insert(f);
+      if (!seen.count(f)) w += rw;
+      if (!f.empty()) seen.insert(f);
     }
     if (cur) out.push_back(cur);
     return out;
@@ -2391,6 +2445,93 @@ std::string rule_kind_key(const PolicySet& ps, uint32_t ri) {
   return key;
 }
 
+// The rules in kernel order: rules that walk the same arrays and leaves share a kernel (and its
+// hoisted lookups). Grouped by the kinds they match first, walk signature second (round 3: C5
+// 4.07 -> 3.72 ms against signature only, C3 10.19 -> 10.32); rules without a program last.
+std::vector<uint32_t> rule_order(const PolicySet& ps) {
+  std::vector<std::pair<std::string, uint32_t>> order;
+  for (uint32_t ri = 0; ri < ps.rules.size(); ri++)
+    order.push_back({!no_program(ps.rules[ri]) ? "0" + rule_kind_key(ps, ri) + "#" + rule_signature(ps, ri) : "1", ri});
+  std::stable_sort(order.begin(), order.end());
+  std::vector<uint32_t> sorted;
+  for (auto& o : order) sorted.push_back(o.second);
+  return sorted;
+}
+
+// The first plan: one kernel per range of the rule order, ceil(n / chunk_rules) ranges of
+// near-equal size, each cut into its first blocks (Gen::initial_blocks).
+// KVGPU_JIT_WAVES: launch bound in waves per SIMD (default 8, 0: none)
+std::vector<JitKernelPlan> first_plan(Gen& g, const std::vector<uint32_t>& sorted, uint32_t chunk_rules) {
+  // first bound: about 160 KB / (256 B x rules) waves, at most 8 and at most what the
+  // kernel's LDS (kernel_lds) leaves of a CU's 160 KB (one workgroup = one wave per SIMD);
+  // the spill plan splits blocks (or lowers the bound) until the compiler meets it. A kernel
+  // of many rules keeps more state live across its fused blocks, and trading occupancy for
+  // fewer, larger blocks (fewer walks of the resource tree) wins there: C2 (100 rules, one
+  // kernel) 6 waves 4 blocks 0.697 ms, 7 waves 16 blocks 0.902 ms, 8 waves 35 blocks
+  // 1.224 ms per pass (round 4, gpurun_out/r4b/ab); C4's ~70-rule kernels run at 8.
+  const uint32_t n = (uint32_t)sorted.size();
+  if (chunk_rules == 0 || chunk_rules > KV_KROWS) chunk_rules = KV_KROWS;
+  uint32_t parts = (n + chunk_rules - 1) / chunk_rules;
+  // one more range while the longest ranges would get fewer workgroups per CU than the
+  // shortest (C3: 1 973 rules in 16 ranges of 123/124 -> 17 of 116/117)
+  while (parts < n && Gen::lds_waves((n + parts - 1) / parts) < Gen::lds_waves(n / parts)) parts++;
+  std::vector<JitKernelPlan> plan;
+  for (uint32_t k = 0; k < parts; k++) {
+    const uint32_t a = (uint32_t)((uint64_t)n * k / parts), e = (uint32_t)((uint64_t)n * (k + 1) / parts);
+    std::vector<uint32_t> bl = g.initial_blocks(sorted, a, e);
+    // workgroups of 4 waves: waves per SIMD = workgroups per CU the LDS admits
+    const int lds_waves = Gen::lds_waves(e - a);
+    const int rule_waves = (int)std::max<uint32_t>(1u, (160u * 1024u) / std::max<uint32_t>(1u, (e - a) * 256u));
+    plan.push_back({a, e - a, g.opt.has_waves ? g.opt.waves : std::min({8, lds_waves, rule_waves}), bl});
+  }
+  return plan;
+}
+
+// Each kernel program = the column macros + the helper functions it reaches + the kernel: the
+// helpers (Gen::helpers, one record per function) are selected by a transitive scan of the names
+// they use and kept in generation order (which is dependency order). out->source: all of it.
+void assemble_programs(const Gen& g, const std::string& prelude, const std::string& cdefs, JitImage* out) {
+  const std::vector<std::pair<std::string, std::string>>& defs = g.helpers;  // (name, text)
+  std::unordered_map<std::string, size_t> def_index;
+  for (size_t i = 0; i < defs.size(); i++) def_index[defs[i].first] = i;
+  auto refs = [&](const std::string& text, std::vector<size_t>* out_ids) {
+    static const char* prefixes[] = {"g_glob_", "g_atom_", "g_pred_", "g_blk_", "g_match_",
+                                     "g_dleaf_", "q_glob_", "q_atom_", "q_pred_", "r_glob_", "r_atom_", "r_pred_"};
+    for (const char* pf : prefixes) {
+      const size_t pl = strlen(pf);
+      for (size_t q = text.find(pf); q != std::string::npos; q = text.find(pf, q + pl)) {
+        size_t e = q + pl;
+        while (e < text.size() && isdigit((unsigned char)text[e])) e++;
+        auto it = def_index.find(text.substr(q, e - q));
+        if (it != def_index.end()) out_ids->push_back(it->second);
+      }
+    }
+  };
+  out->common = prelude;
+  out->kernel_name.clear();
+  out->kernel_src.clear();
+  out->source = prelude + cdefs;
+  for (const auto& d : defs) out->source += d.second;
+  for (auto& k : g.kernels) {
+    std::vector<char> used(defs.size(), 0);
+    std::vector<size_t> stack;
+    refs(k.second, &stack);
+    while (!stack.empty()) {
+      const size_t d = stack.back();
+      stack.pop_back();
+      if (used[d]) continue;
+      used[d] = 1;
+      refs(defs[d].second, &stack);
+    }
+    std::string prog;
+    for (size_t d = 0; d < defs.size(); d++)
+      if (used[d]) prog += defs[d].second;
+    out->kernel_name.push_back(k.first);
+    out->kernel_src.push_back(cdefs + prog + k.second);
+    out->source += k.second;
+  }
+}
+
 }  // namespace
 
 uint32_t jit_chunk_rules() {
@@ -2411,63 +2552,25 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
   for (uint32_t ri = 0; ri < ps.rules.size(); ri++) g.match_fn(ri);
   out->chunks.clear();
   const uint32_t n = (uint32_t)ps.rules.size();
-  if (chunk_rules == 0 || chunk_rules > KV_KROWS) chunk_rules = KV_KROWS;
-  {
-    // rules that walk the same arrays and leaves share a kernel (and its hoisted lookups)
-    std::vector<std::pair<std::string, uint32_t>> order;
-    // rules grouped by the kinds they match first, walk signature second (round 3: C5 4.07 ->
-    // 3.72 ms against signature only, C3 10.19 -> 10.32)
-    for (uint32_t ri = 0; ri < n; ri++)
-      order.push_back({!no_program(ps.rules[ri]) ? "0" + rule_kind_key(ps, ri) + "#" + rule_signature(ps, ri) : "1", ri});
-    std::stable_sort(order.begin(), order.end());
-    // One kernel per range of the signature order: its rules run as one fused block (every
-    // array they walk is walked once per resource, all rules of the range in one loop over
-    // it). Default: ceil(n / chunk_rules) ranges of near-equal size.
-    // KVGPU_JIT_WAVES: launch bound in waves per SIMD (default 8, 0: none)
-    if (out->plan.empty() && n) {
-      // first bound: about 160 KB / (256 B x rules) waves, at most 8 and at most what the
-      // kernel's LDS (kernel_lds) leaves of a CU's 160 KB (one workgroup = one wave per SIMD);
-      // the spill plan splits blocks (or lowers the bound) until the compiler meets it. A kernel
-      // of many rules keeps more state live across its fused blocks, and trading occupancy for
-      // fewer, larger blocks (fewer walks of the resource tree) wins there: C2 (100 rules, one
-      // kernel) 6 waves 4 blocks 0.697 ms, 7 waves 16 blocks 0.902 ms, 8 waves 35 blocks
-      // 1.224 ms per pass (round 4, gpurun_out/r4b/ab); C4's ~70-rule kernels run at 8.
-      uint32_t parts = (n + chunk_rules - 1) / chunk_rules;
-      // one more range while the longest ranges would get fewer workgroups per CU than the
-      // shortest (C3: 1 973 rules in 16 ranges of 123/124 -> 17 of 116/117)
-      while (parts < n && Gen::lds_waves((n + parts - 1) / parts) < Gen::lds_waves(n / parts)) parts++;
-      std::vector<uint32_t> sorted;
-      for (auto& o : order) sorted.push_back(o.second);
-      for (uint32_t k = 0; k < parts; k++) {
-        const uint32_t a = (uint32_t)((uint64_t)n * k / parts), e = (uint32_t)((uint64_t)n * (k + 1) / parts);
-        std::vector<uint32_t> bl = g.initial_blocks(sorted, a, e);
-        // workgroups of 4 waves: waves per SIMD = workgroups per CU the LDS admits
-        const int lds_waves = Gen::lds_waves(e - a);
-        const int rule_waves = (int)std::max<uint32_t>(1u, (160u * 1024u) / std::max<uint32_t>(1u, (e - a) * 256u));
-        out->plan.push_back({a, e - a, g.opt.has_waves ? g.opt.waves : std::min({8, lds_waves, rule_waves}), bl});
-      }
+  const std::vector<uint32_t> sorted = rule_order(ps);
+  if (out->plan.empty() && n) out->plan = first_plan(g, sorted, chunk_rules);
+  for (const JitKernelPlan& kp : out->plan) {
+    JitChunk kc;
+    // named by its rule range and block count: stable when other ranges are re-planned
+    kc.name = "kvj_r" + std::to_string(kp.first) + "_" + std::to_string(kp.count) +
+              (kp.blocks.size() > 1 ? "_b" + std::to_string(kp.blocks.size()) : "") + (kp.waves ? "" : "u");
+    for (uint32_t q = kp.first; q < kp.first + kp.count; q++) kc.rules.push_back(sorted.at(q));
+    std::vector<std::vector<uint32_t>> bl;
+    uint32_t at = 0;
+    for (uint32_t c : kp.blocks) {
+      if (at + c > kp.count) break;
+      bl.emplace_back(kc.rules.begin() + at, kc.rules.begin() + at + c);
+      at += c;
     }
-    for (const JitKernelPlan& kp : out->plan) {
-      JitChunk kc;
-      // named by its rule range and block count: stable when other ranges are re-planned
-      kc.name = "kvj_r" + std::to_string(kp.first) + "_" + std::to_string(kp.count) +
-                (kp.blocks.size() > 1 ? "_b" + std::to_string(kp.blocks.size()) : "") + (kp.waves ? "" : "u");
-      for (uint32_t q = kp.first; q < kp.first + kp.count; q++) kc.rules.push_back(order.at(q).second);
-      std::vector<JitChunk> bl;
-      uint32_t at = 0;
-      for (uint32_t c : kp.blocks) {
-        JitChunk b;
-        b.rules.assign(kc.rules.begin() + at, kc.rules.begin() + at + c);
-        at += c;
-        bl.push_back(std::move(b));
-      }
-      if (at != kp.count) throw std::runtime_error("kvjit: kernel plan blocks do not cover its rules");
-      std::vector<const JitChunk*> bp;
-      for (auto& b : bl) bp.push_back(&b);
-      // the kernel's rules in LDS-row order (blocks reorder rule-group members)
-      kc.rules = g.group_kernel(kc.name, bp, kp.waves);
-      out->chunks.push_back(kc);
-    }
+    if (at != kp.count) throw std::runtime_error("kvjit: kernel plan blocks do not cover its rules");
+    // the kernel's rules in LDS-row order (blocks reorder rule-group members)
+    kc.rules = g.group_kernel(kc.name, bl, kp.waves);
+    out->chunks.push_back(kc);
   }
   out->mtup_words = (uint32_t)(g.mt_bits.size() / 32u);
   if (out->mtup_words && !out->probe) g.build_fac(out);
@@ -2487,62 +2590,7 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
     out->memo_words = (uint32_t)((g.mpreds.size() + 31) / 32);
     out->ptab_row = g.ptab_row_out();
   }
-  // Each kernel program = prelude + the helper functions it reaches + the kernel:
-  // helpers (g_glob_/g_atom_/g_pred_/m_pred_/g_blk_/g_match_/g_rule_) are split at
-  // their definitions and selected by a transitive scan of the identifiers they
-  // use, in generation order (which is dependency order).
-  const std::string helpers = g.o.str();
-  std::vector<std::pair<std::string, std::string>> defs;  // (name, text)
-  {
-    const std::string mark = "__device__ __forceinline__ ";
-    size_t at = helpers.find(mark);
-    while (at != std::string::npos) {
-      size_t next = helpers.find("\n" + mark, at + 1);
-      const size_t end = next == std::string::npos ? helpers.size() : next + 1;
-      const std::string text = helpers.substr(at, end - at);
-      const size_t nb = text.find(' ', mark.size() + 1) + 1;  // after the return type
-      const size_t ne = text.find('(', nb);
-      defs.push_back({text.substr(nb, ne - nb), text});
-      at = next == std::string::npos ? std::string::npos : next + 1;
-    }
-  }
-  std::unordered_map<std::string, size_t> def_index;
-  for (size_t i = 0; i < defs.size(); i++) def_index[defs[i].first] = i;
-  auto refs = [&](const std::string& text, std::vector<size_t>* out_ids) {
-    static const char* prefixes[] = {"g_glob_", "g_atom_", "g_pred_", "g_blk_", "g_match_",
-                                     "g_dleaf_", "q_glob_", "q_atom_", "q_pred_", "r_glob_", "r_atom_", "r_pred_"};
-    for (const char* pf : prefixes) {
-      const size_t pl = strlen(pf);
-      for (size_t q = text.find(pf); q != std::string::npos; q = text.find(pf, q + pl)) {
-        size_t e = q + pl;
-        while (e < text.size() && isdigit((unsigned char)text[e])) e++;
-        auto it = def_index.find(text.substr(q, e - q));
-        if (it != def_index.end()) out_ids->push_back(it->second);
-      }
-    }
-  };
-  out->common = prelude;
-  out->kernel_name.clear();
-  out->kernel_src.clear();
-  out->source = prelude + cdefs + helpers;
-  for (auto& k : g.kernels) {
-    std::vector<char> used(defs.size(), 0);
-    std::vector<size_t> stack;
-    refs(k.second, &stack);
-    while (!stack.empty()) {
-      const size_t d = stack.back();
-      stack.pop_back();
-      if (used[d]) continue;
-      used[d] = 1;
-      refs(defs[d].second, &stack);
-    }
-    std::string prog;
-    for (size_t d = 0; d < defs.size(); d++)
-      if (used[d]) prog += defs[d].second;
-    out->kernel_name.push_back(k.first);
-    out->kernel_src.push_back(cdefs + prog + k.second);
-    out->source += k.second;
-  }
+  assemble_programs(g, prelude, cdefs, out);
   out->gen_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 

@@ -3,7 +3,9 @@ without a compile, under ASan/UBSan: tools/kvemu/jitbuild_check checks the regis
 priv {0, 16} x calls x waves {0, 1, 6, 8} x vgprs {64, 72, 88, 512} against the rules of the spill
 plan, the variants and the block probes written out; every rung of the spill plan's ladder on
 hand-built images with injected verdicts; and the plan file's round trip, with malformed files
-rejected."""
+rejected. On the generator's side (kvjitgen.cpp) it generates a small hand-written policy set, two
+rules per kernel, and checks that every kernel program ends with its own kernel and defines every
+g_ / q_ / r_ helper it uses before the use."""
 import json
 import os
 import subprocess

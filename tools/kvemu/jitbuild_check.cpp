@@ -5,11 +5,16 @@
 //   jitbuild_check <empty directory>
 //
 // checks the register verdict over its domain against the three callers' rules written out, the
-// spill plan's ladder on hand-built images with injected verdicts, and the plan file's round trip
-// in the given directory (as KVGPU_JIT_CACHE). Prints the number of checks; a failed check
+// spill plan's ladder on hand-built images with injected verdicts, the plan file's round trip
+// in the given directory (as KVGPU_JIT_CACHE), and, on the generator's side (kvjitgen.cpp), that
+// every kernel program of a small policy set ends with its own kernel and defines each helper it
+// uses before the use. Prints the number of checks; a failed check
 // prints its line to stderr and the program exits 1.
+#include <algorithm>
+#include <cctype>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <stdexcept>
 
@@ -158,6 +163,87 @@ void plan_file(const std::string& dir) {
   CHECK(!jit_load_plan("missing", &back) && same(back.plan, before));
 }
 
+// ---- the generator's programs (kvjitgen.cpp): helper records into kernel programs
+
+// Every helper name (g_ / q_ / r_ + glob / atom / pred / blk / match / dleaf + _<n>) in `text`:
+// a definition must be the first of its name and every use must follow its definition.
+// `defs` receives the defined names in order, `uses` the number of uses.
+bool helper_names_ok(const std::string& text, std::vector<std::string>* defs, size_t* uses) {
+  static const char* kinds[] = {"glob_", "atom_", "pred_", "blk_", "match_", "dleaf_"};
+  const std::string fn = "__device__ __forceinline__ bool ";
+  auto ident = [](char c) { return isalnum((unsigned char)c) || c == '_'; };
+  *uses = 0;
+  defs->clear();
+  for (size_t at = 0; at + 2 < text.size(); at++) {
+    if ((text[at] != 'g' && text[at] != 'q' && text[at] != 'r') || text[at + 1] != '_' || (at && ident(text[at - 1]))) continue;
+    size_t e = 0;
+    for (const char* k : kinds)
+      if (text.compare(at + 2, strlen(k), k) == 0) e = at + 2 + strlen(k);
+    if (!e || e >= text.size() || !isdigit((unsigned char)text[e])) continue;
+    while (e < text.size() && isdigit((unsigned char)text[e])) e++;
+    const std::string name = text.substr(at, e - at);
+    const bool known = std::find(defs->begin(), defs->end(), name) != defs->end();
+    const bool def = at >= fn.size() && text.compare(at - fn.size(), fn.size(), fn) == 0;
+    if (def ? known : !known) {
+      fprintf(stderr, "%s of %s at offset %zu\n", def ? "second definition" : "use before the definition", name.c_str(), at);
+      return false;
+    }
+    if (def) defs->push_back(name);
+    else ++*uses;
+    at = e - 1;
+  }
+  return true;
+}
+
+// A small hand-written policy set through compile_policies and jit_generate (no compile): two
+// image globs of one structural form (a rule group), a quantity comparison, a name filter (its
+// match function is called from the kernel), a pattern variable (the dynamic leaf's two functions
+// are one record); two rules per kernel, so every program selects its own helpers.
+void programs() {
+  auto rule = [](const std::string& name, const std::string& match, const std::string& pattern) {
+    return "{\"name\": \"" + name + "\", \"match\": {\"resources\": {" + match + "}}, \"validate\": {\"message\": \"m\", \"pattern\": " +
+           pattern + "}}";
+  };
+  const std::string pod = "\"kinds\": [\"Pod\"]";
+  const std::string policies =
+      "[{\"apiVersion\": \"kyverno.io/v1\", \"kind\": \"ClusterPolicy\", \"metadata\": {\"name\": \"p\"}, "
+      "\"spec\": {\"validationFailureAction\": \"Audit\", \"rules\": [" +
+      rule("tag", pod, "{\"spec\": {\"containers\": [{\"image\": \"!*:latest\"}]}}") + ", " +
+      rule("registry", pod, "{\"spec\": {\"containers\": [{\"image\": \"registry.example/*\"}]}}") + ", " +
+      rule("memory", pod, "{\"spec\": {\"containers\": [{\"resources\": {\"limits\": {\"memory\": \"<=1Gi\"}}}]}}") + ", " +
+      rule("named", pod + ", \"name\": \"pod-1*\"", "{\"metadata\": {\"name\": \"?*\"}}") + ", " +
+      rule("label", pod, "{\"metadata\": {\"labels\": {\"app\": \"{{request.object.metadata.name}}\"}}}") + "]}}]";
+  PolicySet ps;
+  compile_policies(policies.data(), policies.size(), &ps, 0u);
+  JitImage img;
+  jit_generate(ps, 2, &img);
+  CHECK(ps.rules.size() == 5 && img.kernel_src.size() == img.kernel_name.size() && img.kernel_src.size() >= 3);
+  std::vector<std::string> all, defs;
+  size_t uses = 0, fewer = 0, calling = 0;
+  CHECK(helper_names_ok(img.source, &all, &uses) && uses > 0 && !all.empty());
+  for (size_t i = 0; i < img.kernel_src.size(); i++) {
+    const std::string& src = img.kernel_src[i];
+    // the program ends with its kernel's own text: one kernel, of its name, and no helper after it
+    const size_t k = src.find("extern \"C\" __global__");
+    CHECK(k != std::string::npos && src.find("extern \"C\" __global__", k + 1) == std::string::npos);
+    if (k == std::string::npos) continue;
+    CHECK(src.find(" void " + img.kernel_name[i] + "(", k) != std::string::npos);
+    CHECK(src.find("__device__ __forceinline__", k) == std::string::npos && src.compare(src.size() - 3, 3, "}\n\n") == 0);
+    CHECK(img.source.find(src.substr(k)) != std::string::npos);
+    // every helper it uses is defined in it, before the use
+    CHECK(helper_names_ok(src, &defs, &uses));
+    CHECK(defs.empty() == (uses == 0));  // (it takes helpers only if it uses some)
+    calling += uses > 0;
+    fewer += defs.size() < all.size();
+    // (the dynamic leaf's wrapper and its evaluator travel together)
+    const bool wrapper = std::find(defs.begin(), defs.end(), "g_dleaf_0") != defs.end();
+    CHECK(wrapper == (src.find("__noinline__ bool kv_dleaf_impl") != std::string::npos));
+  }
+  // (kvj_ptab and the kernel of the name filter and the pattern variable call helpers; some program
+  // leaves helpers out: the selection is per program)
+  CHECK(calling >= 2 && fewer > 0);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -168,6 +254,7 @@ int main(int argc, char** argv) {
   verdict_domain();
   ladder();
   plan_file(argv[1]);
+  programs();
   printf("{\"checks\": %d, \"failed\": %d}\n", checks, failed);
   return failed ? 1 : 0;
 }
