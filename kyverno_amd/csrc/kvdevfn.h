@@ -757,43 +757,70 @@ __device__ __forceinline__ uint32_t kv_count_bytes(uint32_t w, uint32_t b4) {
 // ------------------------------------------------------------------ value-predicate table
 // column of the table holding the predicates of leaf node n: its Val for a scalar, else the
 // pseudo column of its type (null / map / array; an absent cursor reads as null)
-__device__ __forceinline__ uint32_t kv_ptab_col(const DevPS& P, uint32_t type, uint32_t a) {
+__device__ __forceinline__ uint32_t kv_ptab_col(uint32_t n_vals, uint32_t type, uint32_t a) {
   if (type - 1u < 4u) return a;
-  return P.n_vals - KV_PTAB_PSEUDO + (type == NT_NULL ? 0u : type == NT_MAP ? 1u : 2u);
+  return n_vals - KV_PTAB_PSEUDO + (type == NT_NULL ? 0u : type == NT_MAP ? 1u : 2u);
+}
+__device__ __forceinline__ uint32_t kv_ptab_col(const DevPS& P, uint32_t type, uint32_t a) {
+  return kv_ptab_col(P.n_vals, type, a);
 }
 
-// table word `w` of the leaf predicates on node n: for an array every element must pass
-// (validateValueWithPattern per element), i.e. the AND of the elements' words (all ones
-// for an empty array)
+// AND of table word `w` over the `count` elements from row `first` of an array at a leaf
+// position: every element must pass (validateValueWithPattern per element; all ones for an
+// empty array; a nested array or a map element reads its pseudo column). The one element loop:
+// kv_leaf_word and the hoisted leaves' fix-up (kv_leaf_fix) both run it.
+__device__ __forceinline__ uint32_t kv_arr_word(const uint32_t* __restrict__ ptab, uint32_t n_vals,
+                                                const Node* __restrict__ N, uint32_t first, uint32_t count, uint32_t w) {
+  uint32_t x = 0xFFFFFFFFu;
+  for (uint32_t k = 0; k < count; k++) {
+    const Node e = N[ni(first + k)];
+    x &= kv_gld(ptab, (size_t)w * n_vals + kv_ptab_col(n_vals, node_type(e.kt), e.a));
+  }
+  return x;
+}
+
+// table word `w` of the leaf predicates on node n (an array: kv_arr_word of its elements)
 __device__ __forceinline__ uint32_t kv_leaf_word(const DevPS& P, const Node* __restrict__ N, const Node& n, uint32_t w) {
   const uint32_t t = node_type(n.kt);
 #ifdef KV_DIAG_XPTAB
   if (t != NT_ARR) return (n.a * 0x9E3779B9u) ^ (w * 0x85EBCA6Bu);  // (diagnostics: no table read)
 #endif
   if (t != NT_ARR) return kv_gld(P.ptab, (size_t)w * P.n_vals + kv_ptab_col(P, t, n.a));
-  uint32_t x = 0xFFFFFFFFu;
-  for (uint32_t k = 0; k < n.b; k++) {
-    const Node e = N[ni(n.a + k)];
-    x &= kv_gld(P.ptab, (size_t)w * P.n_vals + kv_ptab_col(P, node_type(e.kt), e.a));
-  }
-  return x;
+  return kv_arr_word(P.ptab, P.n_vals, N, n.a, n.b, w);
 }
 
-// table word `w` of the leaf predicates on the node of a narrow cell n. An array at a leaf
-// position (rare, divergent) needs its first element and its count, which the cell does not
-// hold: its payload is the array node's row (a lane's nodes all lie in the lane's column of
-// the node rows, so row x 64 + lane is the node), read here.
-__device__ __forceinline__ uint32_t kv_leaf_word_n(const DevPS& P, const Node* __restrict__ N, const Node& n, uint32_t w) {
-  const uint32_t t = node_type(n.kt);
-  if (t != NT_ARR) return kv_leaf_word(P, N, n, w);
-  const uint32_t ai = ni(n.a);
-  const uint32_t first = kv_gld(&N[ai].a, 0), count = kv_gld(&N[ai].b, 0);
-  uint32_t x = 0xFFFFFFFFu;
-  for (uint32_t k = 0; k < count; k++) {
-    const Node e = N[ni(first + k)];
-    x &= kv_gld(P.ptab, (size_t)w * P.n_vals + kv_ptab_col(P, node_type(e.kt), e.a));
+// Hoisted leaves of a region in three parts (kvjitgen.cpp HoistTable) read their words in two
+// steps, so that the gathers of a region issue back to back behind its cell loads.
+// kv_leaf_gather: the word of the cell's own column, whatever its type, without a branch: an
+// array cell reads the array pseudo column (in bounds) and an absent one the null column.
+// kv_leaf_fix, under the region's one wave-uniform "some hoisted leaf cell is an array" test:
+// the word of an array cell, replacing the gathered one. A narrow cell (`narrow`) holds neither
+// the array's first element nor its count: its payload `a` is the array node's row (a lane's
+// nodes all lie in the lane's column of the node rows, so row x 64 + lane is the node), read
+// here. It is inlined into the region's cold block, off the path every wave runs: as a real
+// call (__noinline__) it took the element loops out of the kernel, but its call-clobbered
+// registers made the block probes spill and C2's plan went from 3 blocks to 5.
+__device__ __forceinline__ uint32_t kv_leaf_gather(const DevPS& P, const Node& n, uint32_t w) {
+#ifdef KV_DIAG_XPTAB
+  if (node_type(n.kt) != NT_ARR) return (n.a * 0x9E3779B9u) ^ (w * 0x85EBCA6Bu);  // (diagnostics: no table read)
+#endif
+  return kv_gld(P.ptab, (size_t)w * P.n_vals + kv_ptab_col(P, node_type(n.kt), n.a));
+}
+__device__ __forceinline__ uint32_t kv_leaf_fix(const uint32_t* __restrict__ ptab, uint32_t n_vals, const Node* __restrict__ N,
+                                             uint32_t a, uint32_t b, bool narrow, uint32_t w) {
+  if (narrow) {
+    const uint32_t ai = ni(a);
+    a = kv_gld(&N[ai].a, 0);
+    b = kv_gld(&N[ai].b, 0);
   }
-  return x;
+  return kv_arr_word(ptab, n_vals, N, a, b, w);
+}
+
+// table word `w` of the leaf predicates on the node of a narrow cell n (an array: through
+// kv_leaf_fix, which reads the array's node)
+__device__ __forceinline__ uint32_t kv_leaf_word_n(const DevPS& P, const Node* __restrict__ N, const Node& n, uint32_t w) {
+  if (node_type(n.kt) != NT_ARR) return kv_leaf_word(P, N, n, w);
+  return kv_leaf_fix(P.ptab, P.n_vals, N, n.a, 0u, true, w);
 }
 
 // record `e` of rule ri on resource r at `slot` of its wave's segment of the rule's record row

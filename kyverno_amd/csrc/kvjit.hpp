@@ -28,6 +28,11 @@ struct JitKernelPlan {
   uint32_t first, count;
   int waves;
   std::vector<uint32_t> blocks;
+  // its hoist regions in three parts (cell loads, word gathers, array fix-up) instead of first-use
+  // order: more loads in flight, more registers live. The first plan asks for it; the build keeps
+  // it for the kernels that meet their register rules with it at the plan they settle on in
+  // first-use order (kvjitbuild.cpp jit_group_regions)
+  bool grouped = false;
 };
 
 struct JitImage {

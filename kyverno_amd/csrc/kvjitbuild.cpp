@@ -322,7 +322,9 @@ bool jit_plan_spills(JitImage* img, const std::vector<RegVerdict>& verdicts) {
     changed = true;
     JitKernelPlan np = kp;
     const size_t big = (size_t)(std::max_element(np.blocks.begin(), np.blocks.end()) - np.blocks.begin());  // (the first)
-    if (v.calls && v.fits) {  // (its scratch is the call frame: it drops its bound instead of splitting blocks)
+    if (kp.grouped) {  // (the plan comes first: the three-part layout goes before a block or a wave does)
+      np.grouped = false;
+    } else if (v.calls && v.fits) {  // (its scratch is the call frame: it drops its bound instead of splitting blocks)
       np.waves = 0;
     } else if (kp.waves > 6 && np.blocks.size() > 1) {
       // the blocks met the bound alone (jit_refine_blocks) and the kernel still does not: the
@@ -465,10 +467,10 @@ bool jit_load_plan(const std::string& key, JitImage* img) {
   std::vector<JitKernelPlan> plan;
   std::istringstream in(std::string(text.begin(), text.end()));
   for (std::string line; std::getline(in, line);) {
-    if (line.rfind("kernel ", 0) != 0) continue;  // kernel <first> <count> <waves> <block sizes...>
+    if (line.rfind("kernel ", 0) != 0) continue;  // kernel <first> <count> <waves> <grouped> <block sizes...>
     std::istringstream ls(line.substr(7));
     JitKernelPlan kp{0, 0, 0, {}};
-    ls >> kp.first >> kp.count >> kp.waves;
+    ls >> kp.first >> kp.count >> kp.waves >> kp.grouped;
     uint32_t sum = 0;
     for (uint32_t b; ls >> b; sum += b) kp.blocks.push_back(b);
     if (sum != kp.count || kp.blocks.empty()) return false;
@@ -484,7 +486,8 @@ void jit_save_plan(const std::string& key, const JitImage& img) {
   if (dir.empty()) return;
   std::string t;
   for (const JitKernelPlan& kp : img.plan) {
-    t += "kernel " + std::to_string(kp.first) + " " + std::to_string(kp.count) + " " + std::to_string(kp.waves);
+    t += "kernel " + std::to_string(kp.first) + " " + std::to_string(kp.count) + " " + std::to_string(kp.waves) + " " +
+         (kp.grouped ? "1" : "0");
     for (uint32_t b : kp.blocks) t += " " + std::to_string(b);
     t += "\n";
   }
@@ -500,6 +503,29 @@ void jit_save_plan(const std::string& key, const JitImage& img) {
   write_file_atomic(dir, dir + "/plan-" + key + ".txt", t);
 }
 
+// The layout of every kernel's hoist regions, over the settled plan: all of them in three parts
+// (JitKernelPlan::grouped), compiled once; a kernel that no longer meets its register rules that
+// way (the loads grouped at the top of a region are in flight together) goes back to first-use
+// order, in which it settled, instead of giving up blocks or waves for the layout.
+static void jit_group_regions(const PolicySet& ps, uint32_t chunk, JitImage* img) {
+  for (JitKernelPlan& kp : img->plan) kp.grouped = true;
+  jit_generate(ps, chunk, img);
+  jit_compile(img);
+  bool back = false;
+  for (size_t k = 0; k < img->plan.size(); k++) {
+    RegVerdict v;
+    if (!reg_verdict(*img, program_of(*img, img->chunks[k].name), img->plan[k].waves, &v))
+      throw std::runtime_error("kvjit: no kernel descriptor for " + img->chunks[k].name);
+    if (!v.ships()) {
+      img->plan[k].grouped = false;
+      back = true;
+    }
+  }
+  if (!back) return;
+  jit_generate(ps, chunk, img);
+  jit_compile(img);  // (the kernels that went back: from the cache, or compiled again)
+}
+
 void jit_build(const PolicySet& ps, JitImage* img) {
   const uint32_t chunk = jit_chunk_rules();
   const char* dump = getenv("KVGPU_JIT_DUMP");
@@ -507,7 +533,13 @@ void jit_build(const PolicySet& ps, JitImage* img) {
   if (dump) write_file(dump, img->source);
   if (!getenv("KVGPU_JIT_SKIP_COMPILE")) {  // (dump-only analysis runs skip it)
     const std::string pkey = jit_plan_key(*img);
-    if (!jit_load_plan(pkey, img)) jit_refine_blocks(ps, chunk, img);  // block sizes from probe compiles
+    // (a stored plan is final, and if the ladder below still has to change it, a kernel's three-part
+    // layout is the first thing to go; a new one is made in first-use order, then given its layouts)
+    const bool stored = jit_load_plan(pkey, img);
+    if (!stored) {
+      for (JitKernelPlan& kp : img->plan) kp.grouped = false;
+      jit_refine_blocks(ps, chunk, img);  // block sizes from probe compiles
+    }
     jit_generate(ps, chunk, img);
     // register budget: re-plan kernels that spill until the compiled plan is the final one
     // (the codes must belong to the last generated image: a plan still changing when the
@@ -520,6 +552,7 @@ void jit_build(const PolicySet& ps, JitImage* img) {
     }
     if (!settled)
       throw std::runtime_error("kvjit: the register plan did not settle (kernels still spill after 64 re-plans)");
+    if (!stored) jit_group_regions(ps, chunk, img);
     jit_compile_variants(img);  // (output-mode variants of the final kernels)
     jit_save_plan(pkey, *img);
     if (dump) write_file(dump, img->source);  // (the source of the final plan)

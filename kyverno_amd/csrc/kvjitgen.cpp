@@ -152,6 +152,7 @@ struct Gen {
     uint32_t mt_kbase = 0;      // first match word of the kernel: LDS row q has bit 32 * mt_kbase + q
     uint32_t gs0 = 0, gsn = 0;  // site-record groups: the kernel's first (of the image) and its count
     std::string decls;          // declarations its blocks need ahead of the kernel (member tables)
+    bool grouped = false;       // hoist regions in three parts (JitKernelPlan::grouped)
   };
 
   explicit Gen(const PolicySet& p) : ps(p), rec_slot(p.rules.size(), 0) {
@@ -181,7 +182,7 @@ struct Gen {
   // emitted, reads more of a cell than its presence, its type and a scalar's Val id. CU_WIDE: a
   // field of the node (.a / .b / .c) or a map's own node index is read; CU_B: the node's b is
   // (an array's element count); CU_LEAF: a leaf predicate reads it (its array case needs a and b
-  // when the cell is wide, and reads the array's node when it is narrow: kv_leaf_word_n). The uses of every
+  // when the cell is wide, and reads the array's node when it is narrow: kv_leaf_fix). The uses of every
   // rule of the policy set decide, whatever the kernel plan; KVGPU_JIT_NARROW=0 makes every
   // column wide (GenOpts).
   enum ColUse : uint32_t { CU_WIDE = 1u, CU_B = 2u, CU_LEAF = 4u };
@@ -234,7 +235,9 @@ struct Gen {
   }
   // the plan (JitImage::cols / fam_*) and the macro block of the kernel programs: per family
   // the words of a row (KVC_W<f>), per column its load from the row at word `b` (KVC_LD), the
-  // node index of a map cell (KVC_IX) and the table word of a leaf on it (KVC_LW)
+  // node index of a map cell (KVC_IX) and the table word of a leaf on it: whole, array case
+  // inline (KVC_LO, regions in first-use order), or as the gather (KVC_LW) and the word of an
+  // array cell (KVC_LA, the fix-up) of a region in three parts
   void col_plan(JitImage* out, std::string* defs) const {
     out->cols.clear();
     out->fam_arr.clear();
@@ -244,6 +247,10 @@ struct Gen {
     out->fam_nn.clear();
     out->col_use.clear();
     std::ostringstream d;
+    // (a hoisted leaf on a node read from the node rows: the whole node is there)
+    d << "#define KVC_LO_ROW(n, w) kv_leaf_word(P, N, n, w)\n"
+      << "#define KVC_LW_ROW(n, w) kv_leaf_gather(P, n, w)\n"
+      << "#define KVC_LA_ROW(n, w) kv_leaf_fix(P.ptab, P.n_vals, N, (n).a, (n).b, false, w)\n";
     for (uint32_t f = 0; f < fams.size(); f++) {
       const Fam& F = fams[f];
       out->fam_arr.push_back(f ? fams[0].idx.at(F.arr) : 0u);  // (family 0 columns come first)
@@ -289,7 +296,9 @@ struct Gen {
         if (c.fmt == KV_COLF_NARROW) {
           d << "kv_ldn(PC, (b) + " << u32((3u * nw + nb + c.pos) * KV_LANES) << " + ln_)\n"
             << "#define " << col_macro("IX", f, j) << "(n) (node_type((n).kt) == NT_MAP ? KV_NARROW_IDX : 0u)\n"
-            << "#define " << col_macro("LW", f, j) << "(n, w) kv_leaf_word_n(P, N, n, w)\n";
+            << "#define " << col_macro("LO", f, j) << "(n, w) kv_leaf_word_n(P, N, n, w)\n"
+            << "#define " << col_macro("LW", f, j) << "(n, w) kv_leaf_gather(P, n, w)\n"
+            << "#define " << col_macro("LA", f, j) << "(n, w) kv_leaf_fix(P.ptab, P.n_vals, N, (n).a, 0u, true, w)\n";
         } else {
           if (c.fmt == KV_COLF_WIDEB)
             d << "kv_ldwb(PC, (b) + " << u32(c.pos * 3u * KV_LANES) << " + 3u * ln_, (b) + "
@@ -297,7 +306,9 @@ struct Gen {
           else
             d << "kv_ldw(PC, (b) + " << u32(c.pos * 3u * KV_LANES) << " + 3u * ln_)\n";
           d << "#define " << col_macro("IX", f, j) << "(n) (node_type((n).kt) == NT_MAP ? (n).c : 0u)\n"
-            << "#define " << col_macro("LW", f, j) << "(n, w) kv_leaf_word(P, N, n, w)\n";
+            << "#define " << col_macro("LO", f, j) << "(n, w) kv_leaf_word(P, N, n, w)\n"
+            << "#define " << col_macro("LW", f, j) << "(n, w) kv_leaf_gather(P, n, w)\n"
+            << "#define " << col_macro("LA", f, j) << "(n, w) kv_leaf_fix(P.ptab, P.n_vals, N, (n).a, (n).b, false, w)\n";
         }
       }
     }
@@ -983,11 +994,17 @@ struct Gen {
   // node << 8), loop indices of the raise (ei0..), anchor bitsets when used.
   static constexpr uint32_t FIN = 0x7F000000u, ACT = 0x80000000u;
 
-  // Leaves on a hoisted scalar read their table word(s) through a load hoisted with the
-  // cursor (issued with the other lookups of the region instead of one dependent load
-  // per rule). Hoisted lookups are branch-free (a failed guard reads cell 0 and discards
-  // it) and are placed at the top of their chunk / fused-loop body, so the loads of one
-  // tree level issue together instead of one dependent wait per lookup.
+  // Leaves on a hoisted node read their table word(s) through a load hoisted with the cursor
+  // instead of one dependent load per rule. A hoist region (the root table of a block, the
+  // element table of a fused loop) is emitted at the top of its block stage / loop body, in one
+  // of two layouts per kernel (HoistTable::flush, JitKernelPlan::grouped). First-use order:
+  // cells and words as the rules ask for them, each word with its array case inline; every
+  // word's branch cuts the loads behind it off from the ones before. Three parts: every
+  // path-column cell load with its index select, then every table-word gather, then one fix-up
+  // for leaf cells that are arrays; the first two have no branch, so the compiler is free to
+  // issue the cell loads together and the gathers together (what it does with that, loop by
+  // loop: DESIGN.md section 4, Hoist regions). It needs more registers, so a kernel keeps it
+  // only if it fits at the plan made in first-use order (kvjitbuild.cpp jit_group_regions).
   //
   // hoisted cursor: node index var + Node var, and the path column the node is read from
   // (fam -1: none). The index var of a column's node is a node index for a map only.
@@ -996,21 +1013,65 @@ struct Gen {
     int fam = -1;
     uint32_t j = kNoCol;
   };
+  struct HWord {  // table word `word` of the leaf on hoisted node `hv`, in variable `var`
+    std::string var;
+    HVar hv;
+    uint32_t word = 0;
+  };
   struct HoistTable {
     std::string prefix;
     std::map<std::string, HVar> vars;
-    std::vector<std::string> code;  // one statement group per entry, dependency order
-    std::set<std::string> words;    // hoisted table-word loads (Gen::pw)
-    size_t flushed = 0;
+    // the lookups, one statement group per entry, in call order (a walk of the node rows stays
+    // behind the cell it starts from), and the leaf words on them, in order of first use
+    std::vector<std::string> cells;
+    std::vector<HWord> words;
+    std::vector<char> order;     // first-use order of both: 'c' the next cell, 'w' the next word
+    std::set<std::string> have;  // (the words' variables)
+    size_t cflushed = 0, wflushed = 0, oflushed = 0;
+    void add_cell(const std::string& c) { cells.push_back(c); order.push_back('c'); }
+    void add_word(const HWord& w) { words.push_back(w); order.push_back('w'); }
     uint32_t n = 0;
     // path columns: the family its lookups read (-1: none, walk the node rows), the root token
     // of its exprs (an element family) and the word offset of its lane's row in the pool
     int fam = -1;
     std::string troot, cell0;
-    std::string flush() {
+    // What was hoisted since the last flush. grouped: in three parts, the cell loads, the gathers
+    // of the leaf words (kv_leaf_gather: no branch, so they issue behind the cell loads' one wait),
+    // and the fix-up of the words whose cell is an array (kv_leaf_fix), under one wave-uniform
+    // test. Otherwise in first-use order, each word whole (kv_leaf_word: its array case inline).
+    std::string flush(bool grouped) {
       std::string s;
-      for (; flushed < code.size(); flushed++) s += code[flushed];
-      return s;
+      if (!grouped) {
+        for (; oflushed < order.size(); oflushed++) {
+          if (order[oflushed] == 'c') {
+            s += cells[cflushed++];
+            continue;
+          }
+          const HWord& x = words[wflushed++];
+          s += "  const uint32_t " + x.var + " = " +
+               (x.hv.fam >= 0 ? col_macro("LO", (uint32_t)x.hv.fam, x.hv.j) : std::string("KVC_LO_ROW")) + "(" + x.hv.node +
+               ", " + std::to_string(x.word) + "u);\n";
+        }
+        return s;
+      }
+      oflushed = order.size();
+      for (; cflushed < cells.size(); cflushed++) s += cells[cflushed];
+      if (wflushed == words.size()) return s;
+      std::vector<std::string> nodes;  // the words' nodes, each once
+      std::string fix;
+      for (size_t i = wflushed; i < words.size(); i++) {
+        const HWord& x = words[i];
+        const bool col = x.hv.fam >= 0;
+        const std::string args = "(" + x.hv.node + ", " + std::to_string(x.word) + "u);\n";
+        s += "  uint32_t " + x.var + " = " + (col ? col_macro("LW", (uint32_t)x.hv.fam, x.hv.j) : std::string("KVC_LW_ROW")) + args;
+        if (std::find(nodes.begin(), nodes.end(), x.hv.node) == nodes.end()) nodes.push_back(x.hv.node);
+        fix += "    if (node_type(" + x.hv.node + ".kt) == NT_ARR) " + x.var + " = " +
+               (col ? col_macro("LA", (uint32_t)x.hv.fam, x.hv.j) : std::string("KVC_LA_ROW")) + args;
+      }
+      wflushed = words.size();
+      s += "  if (__ballot(";
+      for (size_t i = 0; i < nodes.size(); i++) s += (i ? " || " : "") + ("node_type(" + nodes[i] + ".kt) == NT_ARR");
+      return s + ") != 0ull) {  // some leaf cell is an array (rare)\n" + fix + "  }\n";
     }
   };
 
@@ -1064,7 +1125,7 @@ struct Gen {
       c << "  const Node " << h.node << " = " << col_macro("LD", (uint32_t)T.fam, j) << "(" << T.cell0 << ");\n"
         << "  const uint32_t " << h.idx << " = " << h.node << ".kt == 0u ? ABSENT : "
         << col_macro("IX", (uint32_t)T.fam, j) << "(" << h.node << ");\n";
-      T.code.push_back(c.str());
+      T.add_cell(c.str());
       T.vars.emplace(ex, h);
       return h;
     }
@@ -1083,7 +1144,7 @@ struct Gen {
         << h.idx << " = hit_ ? c_ : ABSENT; " << h.node << " = Node{__builtin_amdgcn_perm(t_.kt, 0u, m_), "
         << "__builtin_amdgcn_perm(t_.a, 0u, m_), __builtin_amdgcn_perm(t_.b, 0u, m_), __builtin_amdgcn_perm(t_.c, 0u, m_)}; }\n";
     }
-    T.code.push_back(c.str());
+    T.add_cell(c.str());
     T.vars.emplace(ex, h);
     return h;
   }
@@ -1318,8 +1379,8 @@ struct Gen {
           break;
         case OP_LEAF: {
           // one bit of the leaf's table word (a group: one bit per member, consecutive): hoisted
-          // leaves read the word loaded (and, for an array, AND-ed over its elements) once per
-          // region; others load it here
+          // leaves read the word gathered (and, for an array, replaced by the AND over its
+          // elements) once per region (HoistTable::flush); others load it here
           const uint32_t slot = G ? g.gslot.at(pc) : slot_for(in.a);
           const uint32_t word = slot / 32;
           HoistTable* T = known(d) ? table_for(d) : nullptr;
@@ -1329,11 +1390,7 @@ struct Gen {
             const std::string hn = hvd.node;
             wx = hn + "_w" + std::to_string(word);
             col_mark(hvd.fam, hvd.j, CU_LEAF);
-            if (T->words.insert(wx).second)
-              T->code.push_back("  const uint32_t " + wx + " = " +
-                                (hvd.fam >= 0 ? col_macro("LW", (uint32_t)hvd.fam, hvd.j) + "(" + hn + ", "
-                                              : "kv_leaf_word(P, N, " + hn + ", ") +
-                                u32(word) + ");\n");
+            if (T->have.insert(wx).second) T->add_word(HWord{wx, hvd, word});
           } else {
             IDX(d);
             wx = "kv_leaf_word(P, N, (" + cd + " != ABSENT ? N[" + cd + "] : Node{0u, 0u, 0u, 0u}), " + u32(word) + ")";
@@ -2041,7 +2098,7 @@ struct Gen {
            << ";\n      const Node eln" << tag << " = " << col_macro("LD", L.fam, 0) << "(ec" << tag << ");\n";
     else
       body << "      const Node eln" << tag << " = N[el" << tag << "];\n";
-    body << L.T.flush() << bodies.str() << "    }\n";
+    body << L.T.flush(B.kern.grouped) << bodies.str() << "    }\n";
     for (const RGen* gp : grp)
       if (!gp->lean[k]) body << "    rs" << gp->s << " &= ~ACT_;\n";
     body << "  }\n";
@@ -2115,7 +2172,7 @@ struct Gen {
           body << (w ? "," : "") << " am" << k << "_" << w << " = 0u, sk" << k << "_" << w << " = 0u";
         body << ";\n";
       }
-      body << B.global.flush() << seg.str();  // (the segments' hoisted lookups ahead of them)
+      body << B.global.flush(B.kern.grouped) << seg.str();  // (the segments' hoisted lookups ahead of them)
       if (k < B.K) emit_fused_loops(B, k, body);
     }
     check_resumes(B);
@@ -2146,7 +2203,8 @@ struct Gen {
   }
   // The kernel `name` of the blocks `chs` (each one's rules) at a bound of `waves` per SIMD
   // (0: none); returns its rules in LDS-row order (blocks reorder rule-group members).
-  std::vector<uint32_t> group_kernel(const std::string& name, const std::vector<std::vector<uint32_t>>& chs, int waves) {
+  std::vector<uint32_t> group_kernel(const std::string& name, const std::vector<std::vector<uint32_t>>& chs, int waves,
+                                     bool grouped) {
     std::vector<std::string> blocks;
     std::vector<std::pair<uint32_t, uint32_t>> rows;  // LDS rows [first, first + count) of each block
     std::vector<uint32_t> rules;
@@ -2157,6 +2215,7 @@ struct Gen {
     Kern kern;
     kern.mt_kbase = (uint32_t)(mt_bits.size() / 32u);
     kern.gs0 = (uint32_t)(gs_desc.size() / 4u);
+    kern.grouped = grouped;
     for (const auto& c : chs) {
       std::vector<uint32_t> ord;
       rows.push_back({(uint32_t)rules.size(), (uint32_t)c.size()});
@@ -2482,7 +2541,7 @@ std::vector<JitKernelPlan> first_plan(Gen& g, const std::vector<uint32_t>& sorte
     // workgroups of 4 waves: waves per SIMD = workgroups per CU the LDS admits
     const int lds_waves = Gen::lds_waves(e - a);
     const int rule_waves = (int)std::max<uint32_t>(1u, (160u * 1024u) / std::max<uint32_t>(1u, (e - a) * 256u));
-    plan.push_back({a, e - a, g.opt.has_waves ? g.opt.waves : std::min({8, lds_waves, rule_waves}), bl});
+    plan.push_back({a, e - a, g.opt.has_waves ? g.opt.waves : std::min({8, lds_waves, rule_waves}), bl, true});
   }
   return plan;
 }
@@ -2569,7 +2628,7 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
     }
     if (at != kp.count) throw std::runtime_error("kvjit: kernel plan blocks do not cover its rules");
     // the kernel's rules in LDS-row order (blocks reorder rule-group members)
-    kc.rules = g.group_kernel(kc.name, bl, kp.waves);
+    kc.rules = g.group_kernel(kc.name, bl, kp.waves, kp.grouped);
     out->chunks.push_back(kc);
   }
   out->mtup_words = (uint32_t)(g.mt_bits.size() / 32u);

@@ -8,6 +8,16 @@ spills (into VGPR lanes), private segment, code bytes, and the static instructio
 nearly all of their code in every wave (some lane of 64 takes almost every branch), so the
 static mix tracks the dynamic issue load (SQ_INSTS_SALU / SQ_INSTS_VALU).
 
+Memory waits: per kernel the static counts of vector-memory loads (`ld`) and of `s_waitcnt`
+with a vmcnt field (`wait`), and one line per fused-loop body (an outermost loop of at least
+LOOP_MIN instructions): its loads, waits and rounds, and those of its head. A round is a wait
+with a load issued since the wait before it: the waits of one round drain loads that were in
+flight together, so rounds, not waits, count the memory round trips a wave sits through. The
+head is the code from the body's first load up to the next instruction that touches the exec
+mask. A hoist region (kvjitgen.cpp HoistTable::flush) has no branch before its first rule
+body, so the head holds the region's cell loads and word gathers: one round for the cells in
+the head, and one for the words where the first rule reads one.
+
     python tools/jit_isa.py [c2|c3|c4|c5] [--env K=V ...]
 """
 import collections
@@ -38,9 +48,61 @@ pols = workloads.c3_policies(1000) if wl == "c3" else getattr(workloads, wl + "_
 ps = batch.PolicySet(pols, specialize=True)
 CTRL = {"s_and_saveexec_b64", "s_or_saveexec_b64", "s_andn2_saveexec_b64", "s_cbranch_execz", "s_cbranch_execnz",
         "s_cbranch_scc0", "s_cbranch_scc1", "s_cbranch_vccz", "s_cbranch_vccnz", "s_branch"}
+LOOP_MIN = 300
+INST = re.compile(r"^\s+([a-z][a-z0-9_]+)([^/\n]*)//\s*([0-9A-F]+):[^<\n]*(?:<[^+>]+\+0x([0-9a-f]+)>)?", re.M)
+
+
+def is_load(o):
+    return o.startswith(("global_load", "flat_load", "buffer_load", "scratch_load"))
+
+
+def is_wait(o, rest):
+    return o == "s_waitcnt" and "vmcnt" in rest
+
+
+def loop_report(dis):
+    """[(instructions, (loads, waits, rounds), the same of the head)] of the outermost large loops"""
+
+    def lwr(xs):
+        ld = wt = rd = 0
+        fresh = False  # a load was issued since the last wait
+        for _, o, rest, _ in xs:
+            if is_load(o):
+                ld, fresh = ld + 1, True
+            elif is_wait(o, rest):
+                wt, rd, fresh = wt + 1, rd + fresh, False
+        return ld, wt, rd
+
+    ins = [(int(a, 16), o, rest, int(t, 16) if t else None) for o, rest, a, t in INST.findall(dis)]
+    if not ins:
+        return []
+    base = ins[0][0]
+    at = {a: i for i, (a, _, _, _) in enumerate(ins)}
+    span = {}  # loop header -> last backward branch to it
+    for i, (a, o, _, t) in enumerate(ins):
+        if t is not None and o.startswith(("s_cbranch", "s_branch")) and base + t <= a and base + t in at:
+            h = at[base + t]
+            span[h] = max(span.get(h, i), i)
+    loops = sorted((h, e) for h, e in span.items() if e - h >= LOOP_MIN)
+    out, end = [], -1
+    for h, e in loops:
+        if h <= end:  # nested in the previous outermost loop
+            continue
+        end = e
+        body = ins[h:e + 1]
+        head = []
+        for x in body:
+            if head and "exec" in x[1] + x[2]:
+                break
+            if head or is_load(x[1]):
+                head.append(x)
+        out.append((len(body), lwr(body), lwr(head)))
+    return out
+
+
 tot = collections.Counter()
 print(f"{'kernel':24s} {'vgpr':>4s} {'sgpr':>4s} {'spill':>5s} {'priv':>4s} {'KB':>6s} {'salu':>6s} {'exec':>6s} "
-      f"{'valu':>6s} {'lane':>5s} {'vmem':>5s} {'lds':>5s}")
+      f"{'valu':>6s} {'lane':>5s} {'vmem':>5s} {'lds':>5s} {'ld':>5s} {'wait':>5s}")
 for f in sorted(glob.glob(os.path.join(d, "k.*.co"))):
     label = f.split("k.", 1)[1][:-3]
     name = label.split(".m")[0]  # (output-mode variants: <name>.m<full>)
@@ -57,6 +119,8 @@ for f in sorted(glob.glob(os.path.join(d, "k.*.co"))):
                      dis, re.M)
     c = collections.Counter()
     for o, rest in ops:
+        c["ld"] += is_load(o)
+        c["wait"] += is_wait(o, rest)
         if o in CTRL or (o.startswith("s_") and "exec" in o + rest):
             c["exec"] += 1
         elif o.startswith("s_"):
@@ -73,5 +137,8 @@ for f in sorted(glob.glob(os.path.join(d, "k.*.co"))):
     tot.update(c)
     print(f"{label[:24]:24s} {meta('vgpr_count'):4d} {meta('sgpr_count'):4d} {meta('sgpr_spill_count'):5d} "
           f"{meta('private_segment_fixed_size'):4d} {size / 1024:6.0f} {c['salu']:6d} {c['exec']:6d} {c['valu']:6d} "
-          f"{c['lane']:5d} {c['vmem']:5d} {c['lds']:5d}")
+          f"{c['lane']:5d} {c['vmem']:5d} {c['lds']:5d} {c['ld']:5d} {c['wait']:5d}")
+    for k, (n, b, h) in enumerate(loop_report(dis)):
+        print(f"  loop {k}: {n:5d} instructions, {b[0]:3d} loads {b[1]:3d} waits {b[2]:3d} rounds; "
+              f"head: {h[0]:2d} loads {h[1]:2d} waits {h[2]:2d} rounds")
 print("total", dict(tot))
