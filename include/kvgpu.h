@@ -64,7 +64,20 @@ enum {
    * element passed, SKIP "rule skipped" when the list is missing or empty or every element is
    * gated by the entry's preconditions. CPU also when the list is not a list of maps (or a
    * map), holds a null anywhere, or has more than 65536 elements. */
-  KV_COMPILE_FOREACH = 4
+  KV_COMPILE_FOREACH = 4,
+  /* also evaluate validate.foreach entries that carry a `pattern` on the device (opt-in; needs
+   * KV_COMPILE_FOREACH, else kv_compile returns KV_E_INVALID; without it such a rule is
+   * KV_ROUTE_CPU, reason "foreach"). In scope: one entry {list, preconditions?, pattern}, the
+   * pattern a map without {{ }} variables and without a `metadata` key, inside what the pattern
+   * compiler accepts for a rule's pattern. Per element the pattern is matched with the element as
+   * the whole resource (validate.MatchPattern): no error is PASS, a conditional / global anchor
+   * skip is SKIP (ignored by foreach), an error without a path ERROR, any other FAIL with a path
+   * relative to the element (kv_result_foreach_path); the first FAIL / ERROR / CPU element
+   * decides as for deny entries. The reference compares every number of an element as float64;
+   * an element holding an int64-typed number where that typing could change the verdict (a
+   * string pattern compared on the number's text form, |n| >= 2^53) is CPU, as is an error
+   * record that does not fit 8 bytes. */
+  KV_COMPILE_FOREACH_PATTERN = 8
 };
 
 /* kv_validate modes (bit set). KV_MODE_SCOPES adds per-scope counts
@@ -137,11 +150,16 @@ int kv_policyset_foreach_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* 
 /* *set = 1 + the foreach set of rule `rule`, 0 for a rule that is not a device foreach rule
  * (kv_rule_deny_set is 0 for a foreach rule) */
 int kv_rule_foreach_set(const kv_policyset* ps, uint32_t rule, uint32_t* set);
+/* *on = 1 when rule `rule` is a device foreach rule whose entry carries a pattern
+ * (KV_COMPILE_FOREACH_PATTERN), else 0 */
+int kv_rule_foreach_pattern(const kv_policyset* ps, uint32_t rule, uint32_t* on);
 /* The foreach fold of foreach set `set` (0-based) over an ingested batch, on the host: the twin
  * of kv_foreach_elem_kernel and kv_foreach_fin_kernel. status[i] of resource i (caller order) is
  * KV_STATUS_PASS / _FAIL / _ERROR / _SKIP / _CPU before match / exclude and the rule's
  * preconditions are applied; elem[i] (may be NULL) the index of the deciding element in its list,
- * 0xFFFFFFFF without one. `n` must be the batch's resource count. Needs no GPU. */
+ * 0xFFFFFFFF without one. `n` must be the batch's resource count. Needs no GPU. KV_E_INVALID for
+ * a set whose entry carries a pattern (KV_COMPILE_FOREACH_PATTERN): its elements are walked on the
+ * device only. */
 int kv_batch_foreach_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint32_t* elem,
                           uint64_t n);
 int kv_rule_info_get(const kv_policyset* ps, uint32_t rule, kv_rule_info* out);
@@ -257,6 +275,20 @@ int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char
  * (kv_result_deny_message is 0 for foreach rules). Negative codes as kv_result_subst_error. */
 int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* index);
 int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
+/* Pattern entries (KV_COMPILE_FOREACH_PATTERN). A result fetched with statuses carries, per
+ * pattern set and resource, the reduction key (the deciding element and its code) and the deciding
+ * element's 8-byte error record; kv_result_foreach_element reads the key for these rules, and
+ * kv_result_foreach_message gives only "rule skipped" for them.
+ * kv_result_foreach_path: the failing path of a FAIL pair, relative to the deciding element
+ * ("/image/", "/ports/1/containerPort/"); returns its length, KV_E_INVALID for any other pair.
+ * kv_result_foreach_error_message: err.Error() of the deciding element's PatternError (FAIL and
+ * ERROR pairs), formatted from `element_json`, the caller's document of that element, with every
+ * number typed float64 as the reference's element is ("8.08e+06", "float64"); returns its length,
+ * KV_E_INVALID for any other pair, KV_E_PARSE for bad JSON. The caller composes the RuleResponse
+ * message: "validation failed in foreach rule for " + buildErrorMessage. */
+int kv_result_foreach_path(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
+int kv_result_foreach_error_message(const kv_result* r, uint32_t rule, uint64_t res, const char* element_json, size_t len,
+                                    char* buf, size_t cap);
 double kv_result_kernel_ms(const kv_result* r);
 
 /* Bulk export of the failing pairs (KV_MODE_ERRORS): every FAIL / ERROR / SKIP pair,

@@ -95,6 +95,9 @@ def lib():
         L.kv_batch_foreach_fold.argtypes = [vp, vp, u32, ctypes.c_void_p, ctypes.c_void_p, u64]
         L.kv_result_foreach_element.argtypes = [vp, u32, u64, ctypes.POINTER(u32)]
         L.kv_result_foreach_message.argtypes = [vp, u32, u64, ctypes.c_char_p, sz]
+        L.kv_rule_foreach_pattern.argtypes = [vp, u32, ctypes.POINTER(u32)]
+        L.kv_result_foreach_path.argtypes = [vp, u32, u64, ctypes.c_char_p, sz]
+        L.kv_result_foreach_error_message.argtypes = [vp, u32, u64, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
         L.kv_result_kernel_ms.argtypes = [vp]
         L.kv_result_kernel_ms.restype = ctypes.c_double
         L.kv_bench.argtypes = [vp, vp, ctypes.c_char_p, i32, u32, i32, i32, ctypes.POINTER(ctypes.c_double), errpp]
@@ -140,7 +143,7 @@ EXPORTED_SYMBOLS = [
     "kv_result_kernel_ms", "kv_result_precond_message", "kv_condition_eval", "kv_policyset_cond_sets",
     "kv_result_deny_message", "kv_policyset_deny_sets", "kv_rule_deny_set", "kv_batch_deny_fold",
     "kv_policyset_foreach_sets", "kv_rule_foreach_set", "kv_batch_foreach_fold", "kv_result_foreach_element",
-    "kv_result_foreach_message",
+    "kv_result_foreach_message", "kv_rule_foreach_pattern", "kv_result_foreach_path", "kv_result_foreach_error_message",
     "kv_bench", "kv_synth", "kv_synth_range", "kv_free_policyset", "kv_free_batch", "kv_free_result", "kv_free_error",
     "kv_free_buffer", "kv_session_create", "kv_session_run", "kv_session_counts", "kv_free_session",
     "kv_session_scope_counts", "kv_result_scope_counts", "kv_batch_namespaces", "kv_batch_namespace",

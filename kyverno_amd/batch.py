@@ -19,6 +19,10 @@ a variable does not resolve (``Result.deny_message``). ``PolicySet(..., foreach=
 block over ``{{element...}}`` the same way, one lane per list element (``kv_foreach_elem_kernel``):
 the first ``FAIL`` / ``ERROR`` element decides (``Result.foreach_element``), else ``PASS`` when an
 element passed, else ``SKIP`` "rule skipped" (``Result.foreach_message``).
+``PolicySet(..., foreach=True, foreach_pattern=True)`` (``KV_COMPILE_FOREACH_PATTERN``, opt-in) also
+evaluates entries that carry a ``pattern``: the pattern is matched per element with the element as
+the whole resource (``kv_foreach_pat_kernel``); the deciding element's failing path and pattern
+error are ``Result.foreach_path`` / ``Result.foreach_error_message``.
 """
 from __future__ import annotations
 
@@ -35,7 +39,7 @@ PASS, FAIL, WARN, ERROR, SKIP, NOMATCH, CPU = range(7)
 STATUS_NAMES = ["pass", "fail", "warn", "error", "skip", "nomatch", "cpu"]
 
 MODE_STATUS, MODE_ERRORS, MODE_COUNTS, MODE_SCOPES = 1, 2, 4, 8
-COMPILE_SPECIALIZE, COMPILE_DENY, COMPILE_FOREACH = 1, 2, 4
+COMPILE_SPECIALIZE, COMPILE_DENY, COMPILE_FOREACH, COMPILE_FOREACH_PATTERN = 1, 2, 4, 8
 ROUTE_GPU, ROUTE_CPU, ROUTE_NORESPONSE, ROUTE_CONSTANT = range(4)
 
 
@@ -73,6 +77,7 @@ class Rule:
     const_message: str
     deny: bool = False  # a validate.deny rule evaluated on the device (PolicySet(deny=True))
     foreach: bool = False  # a validate.foreach rule evaluated on the device (PolicySet(foreach=True))
+    foreach_pattern: bool = False  # ... whose entry carries a pattern (PolicySet(foreach_pattern=True))
 
 
 class PolicySet:
@@ -92,20 +97,26 @@ class PolicySet:
     ``validate.foreach`` rules of one entry ``{list, preconditions?, deny}`` to the GPU: ``list`` a
     ``request.object`` path, the conditions over ``{{element...}}`` / ``{{request.object...}}``
     variables. Without it every foreach rule is CPU-routed, reason ``"foreach"``.
+
+    ``foreach_pattern=True`` (``KV_COMPILE_FOREACH_PATTERN``, opt-in, needs ``foreach``) also routes
+    entries ``{list, preconditions?, pattern}`` to the GPU: the pattern a map without ``{{ }}``
+    variables or a ``metadata`` key. Without it such a rule stays CPU-routed, reason ``"foreach"``.
     """
 
-    def __init__(self, policies, specialize: bool = False, deny: bool = False, foreach: bool = False):
+    def __init__(self, policies, specialize: bool = False, deny: bool = False, foreach: bool = False,
+                 foreach_pattern: bool = False):
         L = lib()
         data = _dumps(policies)
         h = ctypes.c_void_p()
         err = new_err()
         flags = ((COMPILE_SPECIALIZE if specialize else 0) | (COMPILE_DENY if deny else 0)
-                 | (COMPILE_FOREACH if foreach else 0))
+                 | (COMPILE_FOREACH if foreach else 0) | (COMPILE_FOREACH_PATTERN if foreach_pattern else 0))
         check(L.kv_compile(data, len(data), flags, ctypes.byref(h), ctypes.byref(err)), err)
         self._h = h
         self.specialize = specialize
         self.deny = deny
         self.foreach = foreach
+        self.foreach_pattern = foreach_pattern
         np_, nr = ctypes.c_uint32(), ctypes.c_uint32()
         L.kv_policyset_info(h, ctypes.byref(np_), ctypes.byref(nr))
         self.n_policies, self.n_rules = np_.value, nr.value
@@ -120,6 +131,9 @@ class PolicySet:
             L.kv_rule_deny_set(h, i, ctypes.byref(ds))
             self.rules[-1].deny = ds.value != 0
             self.rules[-1].foreach = ri.foreach_set != 0
+            on = ctypes.c_uint32()
+            L.kv_rule_foreach_pattern(h, i, ctypes.byref(on))
+            self.rules[-1].foreach_pattern = on.value != 0
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -192,11 +206,18 @@ class PolicySet:
     def foreach_fold(self, b: "Batch") -> tuple[np.ndarray, np.ndarray]:
         """(u8 status, u32 element) [foreach sets][n_res]: the foreach fold of every set over batch
         ``b`` on the host (``kv_batch_foreach_fold``, no GPU), the twin of the two kernels, before
-        match / exclude and the rule's preconditions; element 0xFFFFFFFF: no deciding element."""
-        n_sets = self.foreach_info["sets"]
+        match / exclude and the rule's preconditions; element 0xFFFFFFFF: no deciding element. The
+        rows of pattern sets (``foreach_pattern=True``) stay unset, status 255: their elements are
+        walked on the device only."""
+        info = self.foreach_info
+        n_sets = info["sets"]
+        pattern_sets = {info["rule_sets"][r.index] - 1 for r in self.rules if r.foreach_pattern}
         st = np.zeros((n_sets, b.n_res), dtype=np.uint8)
         el = np.full((n_sets, b.n_res), 0xFFFFFFFF, dtype=np.uint32)
         for s in range(n_sets):
+            if s in pattern_sets:
+                st[s] = 255
+                continue
             rc = lib().kv_batch_foreach_fold(self._h, b._h, s, st[s].ctypes.data, el[s].ctypes.data, b.n_res)
             if rc != 0:
                 raise RuntimeError(f"kv_batch_foreach_fold: code {rc}")
@@ -366,6 +387,22 @@ class Result:
         device foreach rule, "rule skipped" for a SKIP the fold decided
         (``kv_result_foreach_message``), else None."""
         return self._text(lib().kv_result_foreach_message, rule, res)
+
+    def foreach_path(self, rule: int, res: int) -> str | None:
+        """The failing path of a FAIL pair of a device foreach rule with a pattern entry, relative to
+        the deciding element (``kv_result_foreach_path``), else None."""
+        return self._text(lib().kv_result_foreach_path, rule, res, empty_ok=True)
+
+    def foreach_error_message(self, rule: int, res: int, element) -> str | None:
+        """err.Error() of the pattern error of the deciding element of a FAIL / ERROR pair of a device
+        foreach rule with a pattern entry (``kv_result_foreach_error_message``), else None.
+        ``element`` is the caller's document of that element (dict or JSON text); its numbers are
+        formatted as float64, as the reference's element is typed."""
+        doc = element if isinstance(element, (bytes, str)) else _dumps(element)
+        if isinstance(doc, str):
+            doc = doc.encode("utf-8")
+        return self._text(lib().kv_result_foreach_error_message, rule, res, doc, len(doc), errors="replace",
+                          empty_ok=True)
 
     def subst_error(self, rule: int, res: int) -> str | None:
         """The RuleResponse message of an ERROR pair caused by the pattern's variables failing to

@@ -25,9 +25,12 @@ pair whose preconditions do not hold is `skip`, "preconditions not met"; a Go ho
 ``--device-deny`` (``evaluate(deny=True)``, ``KV_COMPILE_DENY``) also evaluates ``validate.deny`` rules
 whose conditions are of those forms on the device, with the messages of ``validateDeny``.
 ``--device-foreach`` (``evaluate(foreach=True)``, ``KV_COMPILE_FOREACH``) does the same for single-entry
-``validate.foreach`` rules with a ``deny`` block, with the messages of ``validateForEach``.
+``validate.foreach`` rules with a ``deny`` block, with the messages of ``validateForEach``;
+``--device-foreach-pattern`` (``evaluate(foreach_pattern=True)``, ``KV_COMPILE_FOREACH_PATTERN``; implies
+``--device-foreach``) also for entries that carry a ``pattern``.
 
     python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N] [--device-deny] [--device-foreach]
+        [--device-foreach-pattern]
     python -m kyverno_amd test test/cli/test/simple
 """
 from __future__ import annotations
@@ -110,6 +113,8 @@ class Evaluation:
     deny: dict = field(default_factory=dict)    # (rule, res) -> message of an ERROR of a deny rule's substitution
     foreach: dict = field(default_factory=dict)  # (rule, res) -> message of an ERROR / SKIP of a foreach rule
     foreach_elem: dict = field(default_factory=dict)  # (rule, res) -> index of the deciding element (FAIL)
+    foreach_path: dict = field(default_factory=dict)  # (rule, res) -> failing path in the deciding element (pattern entries)
+    foreach_err: dict = field(default_factory=dict)   # (rule, res) -> pattern error of the deciding element (pattern entries, ERROR)
     anypattern: dict = field(default_factory=dict)  # (rule, res) -> [(status, path)] per pattern
     warnings: list = field(default_factory=list)    # host-side limits met while rendering messages
 
@@ -119,17 +124,19 @@ class Evaluation:
 
 def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messages: bool = True,
              namespace_labels: dict | None = None, specialize: bool = False, gpus: int = 1,
-             deny: bool = False, foreach: bool = False) -> Evaluation:
+             deny: bool = False, foreach: bool = False, foreach_pattern: bool = False) -> Evaluation:
     """All (rule, resource) pairs on the GPU (``kv_compile`` → ``kv_ingest`` → ``kv_validate``).
     ``specialize`` selects the per-policy-set specialized kernels (worth their hiprtc compile on
     large batches) over the bytecode interpreter; both write the same statuses and error records.
     ``gpus`` > 1 shards the resources over devices [device, device + gpus) (kv_validate_devices).
     ``deny`` evaluates ``validate.deny`` rules of the device forms on the GPU (``KV_COMPILE_DENY``)
     instead of routing them to the reference engine; ``foreach`` does the same for
-    ``validate.foreach`` rules (``KV_COMPILE_FOREACH``)."""
+    ``validate.foreach`` rules (``KV_COMPILE_FOREACH``), ``foreach_pattern`` (which implies
+    ``foreach``) also for entries that carry a ``pattern`` (``KV_COMPILE_FOREACH_PATTERN``)."""
     from . import batch
 
-    ps = batch.PolicySet(policies, specialize=specialize, deny=deny, foreach=foreach)
+    ps = batch.PolicySet(policies, specialize=specialize, deny=deny, foreach=foreach or foreach_pattern,
+                         foreach_pattern=foreach_pattern)
     b = batch.Batch(ps, resources, namespace_labels)
     mask = ((1 << gpus) - 1) << device if gpus > 1 else None
     r = batch.validate(ps, b, device=device, device_mask=mask)
@@ -138,6 +145,8 @@ def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messa
         for ri, res in zip(*np.nonzero(r.status == FAIL)):
             if ps.rules[ri].foreach:  # (no failing path either: the deciding element instead)
                 ev.foreach_elem[(int(ri), int(res))] = r.foreach_element(int(ri), int(res))
+                if getattr(ps.rules[ri], "foreach_pattern", False):  # (a pattern entry: the path inside that element)
+                    ev.foreach_path[(int(ri), int(res))] = r.foreach_path(int(ri), int(res))
             elif not ps.rules[ri].any_pattern and not ps.rules[ri].deny:  # (a deny FAIL has no failing path)
                 ev.paths[(int(ri), int(res))] = r.path(int(ri), int(res))
         collect_errors(ev, ps, r, resources)
@@ -164,6 +173,14 @@ def collect_errors(ev: Evaluation, ps, r, resources: list) -> None:
             if m is not None:
                 ev.precond[key] = m
                 continue
+        if getattr(ps.rules[ri], "foreach_pattern", False) and r.status[ri, res] == ERROR:
+            # a pattern entry: the pattern error of the deciding element, formatted from that element
+            ev.foreach_elem[key] = r.foreach_element(*key)
+            el = _foreach_element(ev, ps.rules[ri], key[1])
+            m = r.foreach_error_message(key[0], key[1], el) if el is not None else None
+            if m is not None:
+                ev.foreach_err[key] = m
+            continue
         if getattr(ps.rules[ri], "foreach", False):
             m = r.foreach_message(*key)
             if m is not None:
@@ -224,12 +241,12 @@ def _with_dot(s: str) -> str:
     return s if s.endswith(".") else s + "."
 
 
-def _message(ev: Evaluation, rule, res: int) -> str:
-    """The rule's message after SubstituteAll (msgvars). A JMESPath form the host does not evaluate
-    leaves the message as written and is reported in ``ev.warnings``; a form on which the reference
-    panics raises ``msgvars.MessageVariableError``."""
+def _message(ev: Evaluation, rule, res: int, element: dict | None = None) -> str:
+    """The rule's message after SubstituteAll (msgvars), with ``element`` in the context of a foreach
+    entry. A JMESPath form the host does not evaluate leaves the message as written and is reported
+    in ``ev.warnings``; a form on which the reference panics raises ``msgvars.MessageVariableError``."""
     try:
-        return msgvars.substitute_message(rule.message, ev.resources[res])
+        return msgvars.substitute_message(rule.message, ev.resources[res], element)
     except msgvars.UnsupportedMessageVariable as e:
         w = f"rule {rule.name}: message variables not rendered: {e}"
         if w not in ev.warnings:
@@ -261,6 +278,17 @@ def rule_message(ev: Evaluation, rule, res: int) -> str:
     if getattr(rule, "foreach", False):  # validateForEach (validation.go:204-283)
         if st == PASS:
             return "rule passed"
+        if getattr(rule, "foreach_pattern", False) and st in (FAIL, ERROR):
+            # the element's validatePatterns message: buildErrorMessage in the element's context
+            # (validation.go:421-445,510-534)
+            head = "validation failed in foreach rule for "
+            path = ev.foreach_path.get((rule.index, res)) or ""
+            tail = (f"failed at path {path}" if st == FAIL else
+                    f"execution error: {ev.foreach_err.get((rule.index, res), '')}")
+            if not rule.message:
+                return head + f"validation error: rule {rule.name} {tail}"
+            msg = _message(ev, rule, res, _foreach_element(ev, rule, res))
+            return head + f"validation error: {_with_dot(msg)} Rule {rule.name} {tail}"
         if st == FAIL:  # the element's validateDeny message, in the element's context
             head = "validation failed in foreach rule for "
             if not rule.message:
@@ -393,18 +421,18 @@ def policy_has_validate(policy: dict) -> bool:
 
 def apply(policy_paths: list[str], resource_paths: list[str], policy_report: bool = False, device: int = 0,
           out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
-          foreach: bool = False) -> tuple[ResultCounts, list]:
+          foreach: bool = False, foreach_pattern: bool = False) -> tuple[ResultCounts, list]:
     """applyCommandHelper (apply_command.go:147-310) for resource files. Returns counts and the
     policyreport infos. ``evaluation_fn(policies, resources) -> Evaluation`` replaces the device
     evaluation (tests of the host logic)."""
     policies = load_policies(policy_paths)
     resources = load_resources(resource_paths)
-    return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny, foreach)
+    return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny, foreach, foreach_pattern)
 
 
 def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool = False, device: int = 0,
                out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
-          foreach: bool = False) -> tuple[ResultCounts, list]:
+          foreach: bool = False, foreach_pattern: bool = False) -> tuple[ResultCounts, list]:
     mutated = autogen.mutate_policies(policies)
     if len(mutated) > 0 and len(resources) > 0:
         msg_p = "1 policy" if len(mutated) <= 1 else f"{len(policies)} policies"
@@ -416,7 +444,8 @@ def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool 
     active = [p for p in mutated if not has_unset_variables(p)]
     infos = []
     if active and resources:
-        ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus, deny=deny, foreach=foreach)))(active, resources)
+        ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus, deny=deny, foreach=foreach,
+                                                          foreach_pattern=foreach_pattern)))(active, resources)
         for pi, pol in enumerate(active):
             if not policy_has_validate(pol):
                 continue
@@ -524,6 +553,9 @@ def main(argv: list[str] | None = None) -> int:
                    help="evaluate validate.deny rules of the device forms on the GPU (KV_COMPILE_DENY)")
     a.add_argument("--device-foreach", action="store_true",
                    help="evaluate validate.foreach rules of the device forms on the GPU (KV_COMPILE_FOREACH)")
+    a.add_argument("--device-foreach-pattern", action="store_true",
+                   help="also evaluate validate.foreach entries that carry a pattern on the GPU "
+                        "(KV_COMPILE_FOREACH_PATTERN; implies --device-foreach)")
     t = sub.add_parser("test", help="run tests from a directory holding test.yaml")
     t.add_argument("dir")
     t.add_argument("--device", type=int, default=0)
@@ -531,7 +563,8 @@ def main(argv: list[str] | None = None) -> int:
     if args.cmd == "apply":
         try:
             rc, _ = apply(args.policies, args.resource, args.policy_report, args.device, gpus=args.gpus, deny=args.device_deny,
-                          foreach=args.device_foreach)
+                          foreach=args.device_foreach or args.device_foreach_pattern,
+                          foreach_pattern=args.device_foreach_pattern)
         except msgvars.MessageVariableError as e:
             # the Go CLI dies in buildErrorMessage (msgRaw.(string), validation.go:519-524): a
             # panic, exit status 2

@@ -17,6 +17,7 @@ namespace kvh {
 struct DevPolicySet {
   DevBuf prog, preds, alts, conjs, atoms, rules, filters, kinds, strrefs, strpairs, sels, sellabels, selexprs, kgs,
       gsegs, gwords, pstr, fword, fbit, flist, frule, rcompact, gsdesc, gsmem;
+  DevBuf view_dev;  // `view` on the device (without the per-session tables): what kv_foreach_pat_kernel walks
   // site-record groups of the specialized kernels (kvdevtypes.h GSiteDesc)
   uint32_t gs_groups = 0, gs_members = 0;
   DevPS view{};
@@ -67,7 +68,8 @@ struct DevBatchRes {
   // (its gate and deny blocks, its own five tables, the reduction keys fe_acc[set][res]), each
   // list in its host struct's order; the plane kv_precond_kernel wrote, and the one kv_deny_kernel
   // (rows of the deny sets) and the foreach kernels (rows after them) wrote; HIP-event times
-  DevBuf pre[5], dn[7], feg[2], fed[7], fe[5], feacc, prest, dnst;
+  // pattern sets (KV_COMPILE_FOREACH_PATTERN): their three tables and fe_rec[pattern set][res]
+  DevBuf pre[5], dn[7], feg[2], fed[7], fe[5], fep[3], feacc, ferec, prest, dnst;
   double pre_ms = 0, deny_ms = 0, fe_ms = 0;
   DevBatch view{};
 };
@@ -195,6 +197,7 @@ DevPolicySet& dev_ps(kv_policyset* s, int device) {
       d->ptab_rows = (uint32_t)((J.memo_preds.size() + J.ptab_row - 1) / J.ptab_row);
     }
   }
+  if (!ps.fpats.empty()) d->view_dev.upload_raw(&d->view, sizeof(DevPS), device);
   auto& ref = *d;
   s->dev[device] = std::move(d);
   return ref;
@@ -266,7 +269,8 @@ void build_pcol(const JitImage& J, const Batch& b, DevBatchRes* d, int device) {
             b.res.empty() ? 0.0 : (double)(words * sizeof(uint32_t)) / (double)b.res.size(), d->pcol_ms);
 }
 
-std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int device) {
+// pdev: the policy set's device view (DevPolicySet::view_dev), read by the pattern sets' kernel
+std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int device, const DevPS* pdev) {
   std::lock_guard<std::mutex> g(bt->mu);
   auto it = bt->dev.find(device);
   if (it != bt->dev.end()) return it->second;
@@ -387,8 +391,10 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
   FeHost fh;
   CondBlocks pt{}, dt{};
   FeTables ft{};
+  FePatTables qt{};
+  DevBuf erec;  // the pattern sets' per-element records: needed until the fold's kernels are done
   const uint32_t n_sets = (uint32_t)ps.csets.size(), n_dsets = (uint32_t)ps.dsets.size(),
-                 n_fsets = (uint32_t)ps.fsets.size();
+                 n_fsets = (uint32_t)ps.fsets.size(), n_pats = (uint32_t)ps.fpats.size();
   if (n_sets && !b.res.empty()) {
     build_pre(ps, b, &pre);
     pt = up_blocks(d->pre, pre, false);
@@ -411,6 +417,13 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     up(d->fe + 2, {&fh.el_res, &fh.el_ord, &fh.lstate}, dp + 2);
     ft.sets = dp[0]; ft.lists = dp[1]; ft.el_res = dp[2]; ft.el_ord = dp[3]; ft.lstate = dp[4];
     d->feacc.alloc((size_t)n_fsets * b.res.size() * sizeof(uint32_t), device);
+    if (n_pats) {
+      const uint32_t* qp[3];
+      up(d->fep, {&fh.pats, &fh.chain, &fh.first}, qp);
+      qt = FePatTables{qp[0], qp[1], qp[2], n_pats};
+      erec.alloc(std::max<size_t>((size_t)n_pats * fh.max_el * sizeof(ErrRec8), 16), device);
+      d->ferec.alloc((size_t)n_pats * b.res.size() * sizeof(ErrRec8), device);
+    }
   }
   if ((n_dsets || n_fsets) && !b.res.empty()) {
     d->dnst.alloc((size_t)(n_dsets + n_fsets) * b.res.size(), device);
@@ -422,7 +435,9 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     timed_launch(&d->deny_ms, [&]() { return launch_cond(true, dt, v.n_res, n_dsets, (uint8_t*)d->dnst.p, us); });
   if (v.deny_st && n_fsets)
     timed_launch(&d->fe_ms, [&]() {
-      return launch_foreach(ft, v.n_res, (uint32_t*)d->feacc.p, (uint8_t*)d->dnst.p + (size_t)n_dsets * v.n_res, us);
+      return launch_foreach(ft, v.n_res, (uint32_t*)d->feacc.p, (uint8_t*)d->dnst.p + (size_t)n_dsets * v.n_res, us,
+                            n_pats ? &qt : nullptr, pdev, (const DevBatch*)d->view_dev.p, (uint2*)erec.p,
+                            (uint2*)d->ferec.p);
     });
   HIPCHK(hipStreamSynchronize(us));
   for (const Timed& t : timed) {
@@ -507,7 +522,7 @@ struct DevSession {
     HIPCHK(hipSetDevice(device));
     const auto tc0 = std::chrono::steady_clock::now();
     DevPolicySet& dp = dev_ps(ps, device);
-    batch_ref = dev_batch(bt, ps->ps, device);
+    batch_ref = dev_batch(bt, ps->ps, device, (const DevPS*)dp.view_dev.p);
     DevBatchRes& db = *batch_ref;
     upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count();
     if (getenv("KVGPU_VERBOSE")) fprintf(stderr, "[kvgpu] session: policy set + batch upload %.1f ms\n", upload_ms);
@@ -1144,6 +1159,19 @@ struct DevSession {
         lap("records_wide_rerun");
       }
     }
+    // pattern sets of foreach rules: per (pattern set, resource) the reduction key and the deciding
+    // element's record, as the batch's fold left them (kvforeach.h)
+    if (want_st && !ps->ps.fpats.empty() && batch_ref && batch_ref->ferec.p) {
+      const std::vector<uint32_t>& fp = ps->ps.fpats;
+      part->fe_key.alloc(fp.size() * nres);
+      part->fe_rec.alloc(fp.size() * nres);
+      for (size_t k = 0; k < fp.size(); k++)
+        HIPCHK(hipMemcpyAsync(part->fe_key.data() + k * nres, (const uint32_t*)batch_ref->feacc.p + (size_t)fp[k] * nres,
+                              nres * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(part->fe_rec.data(), batch_ref->ferec.p, fp.size() * nres * sizeof(ErrRec8),
+                            hipMemcpyDeviceToHost, stream));
+      lap("foreach_rows_d2h");
+    }
     if (packed) {  // the statuses' transfer form (kv_status_pack_kernel above; the re-run leaves it)
       HIPCHK(hipMemcpyAsync(part->sflag.data(), O.sflag, part->sflag.size(), hipMemcpyDeviceToHost, stream));
       if (spack_bytes) HIPCHK(hipMemcpyAsync(part->spack.data(), s_pack.p, spack_bytes, hipMemcpyDeviceToHost, stream));
@@ -1492,9 +1520,11 @@ extern "C" {
 
 int kv_compile(const char* policies_json, size_t len, uint32_t flags, kv_policyset** out, kv_error** err) {
   if (!policies_json || !out) return fail(err, KV_E_INVALID, "null argument");
+  if ((flags & KV_COMPILE_FOREACH_PATTERN) && !(flags & KV_COMPILE_FOREACH))
+    return fail(err, KV_E_INVALID, "KV_COMPILE_FOREACH_PATTERN needs KV_COMPILE_FOREACH");
   return guarded(KV_E_PARSE, err, [&]() -> int {
     auto s = std::make_unique<kv_policyset>();
-    compile_policies(policies_json, len, &s->ps, flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH));
+    compile_policies(policies_json, len, &s->ps, flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN));
     if (flags & KV_COMPILE_SPECIALIZE) {
       s->jit = std::make_unique<JitImage>();
       jit_build(s->ps, s->jit.get());  // (kvjitbuild.cpp: generate, plan, compile, variants)

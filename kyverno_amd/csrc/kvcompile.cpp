@@ -23,6 +23,8 @@
 
 #include "kvcond.h"
 #include "kvinternal.hpp"
+#include "kvblocks.h"
+#include "kvforeach.h"
 
 namespace kvh {
 
@@ -895,7 +897,32 @@ struct Compiler {
       emit(OP_VLEAF, d, 0, dl, pn, cs);
       return;
     }
-    emit(OP_LEAF, d, 0, pred(P), pn, cs);
+    const uint32_t pi = pred(P);
+    // a foreach entry's pattern (kvwalk.h): aux 1 marks a leaf whose verdict on a number depends
+    // on its int64 / float64 typing
+    emit(OP_LEAF, d, fe_pattern && !pred_type_agnostic(pi) ? 1u : 0u, pi, pn, cs);
+  }
+
+  // Compiling the pattern of a validate.foreach entry (KV_COMPILE_FOREACH_PATTERN): the element
+  // comes out of the JSON context, so the reference compares every number of it as float64,
+  // where the store types a literal int64. The two agree under a number, bool or null pattern and
+  // under string atoms that compare quantities or match everything; they differ where the string
+  // forms are compared (validateString on FormatFloat 'E' against decimal, the wildcard branch of
+  // validateNumberWithStr on %f against decimal).
+  bool fe_pattern = false;
+  bool pred_type_agnostic(uint32_t pi) const {
+    const Pred& pr = ps.preds[pi];
+    if (pr.kind != PK_STRING) return true;
+    for (uint32_t a = pr.first; a < pr.first + pr.count; a++)
+      for (uint32_t c = ps.alts[a].first; c < ps.alts[a].first + ps.alts[a].count; c++) {
+        const Conj& cj = ps.conjs[c];
+        for (uint32_t k = 0; k < (cj.kind == CJ_ATOM ? 1u : 2u); k++) {  // (a range has two atoms)
+          const Atom& at = ps.atoms[k ? cj.a1 : cj.a0];
+          const bool glob = at.kind == AT_GLOB_E || at.kind == AT_GLOB_N;
+          if (glob && !(at.gflags & G_ALL)) return false;
+        }
+      }
+    return true;
   }
 
   void children(const PV& P, uint32_t d, uint32_t pn, uint32_t cs, int meta_idx, int expand_tag, uint32_t t) {
@@ -1372,7 +1399,10 @@ static void compile_block(Compiler& C, const JDoc& d, int64_t blk, bool is_match
 }
 
 // Emits the full pattern program of one rule; returns false (with reason) if CPU-routed.
-static bool compile_pattern_program(Compiler& C, const std::vector<PV>& patterns, bool any, RuleRec& rr, RuleHost& rh) {
+// trie_root: the projection-trie node the pattern's root stands at (0: the resource; the element
+// node of a foreach list for an entry's pattern).
+static bool compile_pattern_program(Compiler& C, const std::vector<PV>& patterns, bool any, RuleRec& rr, RuleHost& rh,
+                                    uint32_t trie_root = 0) {
   PolicySet& ps = C.ps;
   rr.prog = (uint32_t)ps.prog.size();
   C.scopes.clear();
@@ -1392,8 +1422,8 @@ static bool compile_pattern_program(Compiler& C, const std::vector<PV>& patterns
     uint32_t root = C.pnode(0xFFFFFFFFu, SEG_ROOT, 0, "");
     if (any) rh.alt_roots.push_back(root);
     else rh.root_pnode = root;
-    C.trie_of(patterns[ai], 0);  // before emission: key ops resolve their trie slots
-    C.elem(patterns[ai], 0, root, alt_scope, 0);
+    C.trie_of(patterns[ai], trie_root);  // before emission: key ops resolve their trie slots
+    C.elem(patterns[ai], 0, root, alt_scope, trie_root);
     if (!C.cpu_reason.empty()) {
       ps.prog.resize(rr.prog);
       rh.route_reason = C.cpu_reason;
@@ -1410,6 +1440,67 @@ static bool compile_pattern_program(Compiler& C, const std::vector<PV>& patterns
   for (auto& f : C.skip_fix) ps.prog[f.first].b = C.scopes[f.second].end_pc;
   rr.flags |= C.rule_flags;
   for (auto& f : C.slot_fix) ps.slot_fix.push_back(f);
+  return true;
+}
+
+static bool has_metadata_key(const PV& p) {
+  for (size_t i = 0; i < p.mk.size(); i++)
+    if (remove_anchor(p.mk[i], nullptr) == "metadata" || has_metadata_key(p.mv[i])) return true;
+  for (const PV& e : p.a)
+    if (has_metadata_key(e)) return true;
+  return false;
+}
+
+// The `pattern` of a validate.foreach entry (kvcond.h FePatternCompiler): the pattern program of
+// MatchPattern(element, pattern), rooted at the projection-trie node of the elements of `list`.
+// Outside the scope (false): {{ }} variables, an anchor-error phrase, a failing $() reference, a
+// `metadata` key (MatchPattern runs ExpandInMetadata on the element at the top; below it the
+// pattern compiler's metadata sites read the resource's flags, which say nothing about an element)
+// and whatever the pattern compiler refuses. A refused pattern leaves no instruction, slot fix-up
+// or foreach set behind; the trie nodes of the list path and of the pattern's keys, interned
+// keys, predicates and (where the pattern compiler itself refused) pattern nodes stay, as they do
+// for a refused rule pattern: they only widen the projection.
+static bool compile_foreach_pattern(Compiler& C, const JDoc& d, uint32_t pn, const std::string& list, uint32_t li, FeSet* s) {
+  PolicySet& ps = C.ps;
+  PV doc = to_pv(d, pn);
+  if (doc.t != J_MAP || doc_has_variable(doc) || doc_has_magic(doc) || has_metadata_key(doc)) return false;
+  PV orig = doc;
+  std::string err;
+  if (!subst_tree(orig, doc, "", &err)) return false;
+  unescape_vars(doc);
+  if (has_metadata_key(doc) || doc_has_variable(doc)) return false;  // (a $() reference may have brought one in)
+  // the list's path in the projection trie: fields are children, arrays transparent (the element
+  // trie). The elements of a list a field step ends in stand at that field's element node; an
+  // index step ends in the one element itself.
+  FeChain ch;
+  if (!list_query_steps(list, &ch.steps) || ch.steps.empty()) return false;
+  uint32_t t = 0;
+  for (const ListStep& st : ch.steps) {
+    ch.trie.push_back(t);
+    if (!st.index) ps.intern(st.key);  // (its id: the step of a keep-all map looks the key up by id)
+    t = st.index ? ps.trie.elem(t) : ps.trie.child(t, st.key);
+  }
+  ch.elem_trie = ch.steps.back().index ? t : ps.trie.elem(t);
+  RuleRec rr{};
+  RuleHost rh;
+  const size_t fix0 = ps.slot_fix.size(), pn0 = ps.pnodes.size();
+  C.fe_pattern = true;
+  const bool ok = compile_pattern_program(C, {doc}, false, rr, rh, ch.elem_trie);
+  C.fe_pattern = false;
+  if (!ok) return false;
+  // (no metadata site can be left: no `metadata` key); the walk's cursor stack holds 16 levels
+  uint32_t depth = 0;
+  for (size_t pc = rr.prog; pc < ps.prog.size(); pc++) depth = std::max(depth, ((ps.prog[pc].op >> 8) & 0xFFu) + 2u);
+  if (rr.flags != 0 || depth > 16u) {
+    ps.prog.resize(rr.prog);
+    ps.slot_fix.resize(fix0);
+    ps.pnodes.resize(pn0);
+    return false;
+  }
+  s->prog = rr.prog;
+  s->root_pnode = rh.root_pnode;
+  if (ps.fchains.size() <= li) ps.fchains.resize(li + 1);
+  if (ps.fchains[li].steps.empty()) ps.fchains[li] = std::move(ch);
   return true;
 }
 
@@ -1478,9 +1569,17 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
         // validate.foreach on the device (KV_COMPILE_FOREACH, kvcond.h): nothing beside it in
         // validate, no rule-level context
         const bool feD = (flags & 4u /* KV_COMPILE_FOREACH */) && feP && !patP && !anyP && !denyP && !ctxP;
+        // an entry's `pattern` on the device (KV_COMPILE_FOREACH_PATTERN): compiled here, rooted at
+        // the list's elements. A rule whose name holds an anchor-error phrase stays on the CPU, as
+        // for rule patterns: it gets no pattern compiler, whether or not its set is interned already
+        const FePatternCompiler fe_pat = [&](uint32_t pnode, const std::string& list, uint32_t li, FeSet* s) {
+          return compile_foreach_pattern(C, d, pnode, list, li, s);
+        };
+        const FePatternCompiler* fe_patp =
+            (flags & 8u /* KV_COMPILE_FOREACH_PATTERN */) && !has_magic(rh.name) ? &fe_pat : nullptr;
         rr.route = 0;
         if (!has_validate) { rr.route = 2; rh.route_reason = "no validate"; }
-        else if (feP && (!feD || (rh.foreach_set = compile_foreach(*ps, d, (uint32_t)fen)) == 0)) {
+        else if (feP && (!feD || (rh.foreach_set = compile_foreach(*ps, d, (uint32_t)fen, fe_patp)) == 0)) {
           rr.route = 1;
           rh.route_reason = "foreach";
         }
@@ -1575,6 +1674,34 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
   // foreach rules read their status from the rows of the deny plane after the deny sets'
   for (size_t i = 0; i < ps->rules.size(); i++)
     if (ps->rhost[i].foreach_set) ps->rules[i].deny = (uint32_t)ps->dsets.size() + ps->rhost[i].foreach_set;
+  // The one-element rule of evaluateList (utils.go:445-472): a list query that a field step ends
+  // in a single map makes that map the one element, and the map stands at the field's own trie
+  // node, not at its element node. The two nodes get the same keys, all the way down, so both map
+  // layouts have the slots the pattern program was resolved with and one program serves both.
+  {
+    Trie& tr = ps->trie;
+    std::function<void(uint32_t, uint32_t, bool)> mirror = [&](uint32_t a, uint32_t b, bool top) {
+      std::vector<std::string> keys;
+      for (auto& kv : tr.nodes[a].kids) keys.push_back(kv.first);
+      for (auto& kv : tr.nodes[b].kids) keys.push_back(kv.first);
+      for (const std::string& k : keys) {
+        const uint32_t ca = tr.child(a, k), cb = tr.child(b, k);
+        mirror(ca, cb, false);
+      }
+      const bool ka = tr.nodes[a].keep_all || tr.nodes[b].keep_all;
+      tr.nodes[a].keep_all = tr.nodes[b].keep_all = ka;
+      // (at the top b is a's element node: a's own elements are not the map's concern)
+      if (!top && (tr.nodes[a].elem >= 0 || tr.nodes[b].elem >= 0)) {
+        const uint32_t ea = tr.elem(a), eb = tr.elem(b);
+        mirror(ea, eb, false);
+      }
+    };
+    for (const FeChain& ch : ps->fchains)
+      if (!ch.steps.empty() && !ch.steps.back().index) {
+        const ListStep& st = ch.steps.back();
+        mirror(tr.child(ch.trie.back(), st.key), ch.elem_trie, true);
+      }
+  }
   // Slot-addressed map layout: every non-keep-all trie node gets a byte-sorted
   // key list; key-lookup ops get the slot index (keep-all maps: key id + AUX_SCAN).
   for (auto& tn : ps->trie.nodes) {
@@ -1592,6 +1719,25 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
     auto it = tn.slot.find(std::get<2>(f));
     if (it == tn.slot.end()) throw std::runtime_error("compiler: key missing from projection trie: " + std::get<2>(f));
     in.a = it->second;
+  }
+  // the list paths of the pattern sets, as the device walks them: a field is a slot of its map
+  // (a key id under a keep-all map)
+  for (FeChain& ch : ps->fchains) {
+    for (size_t i = 0; i < ch.steps.size(); i++) {
+      const ListStep& st = ch.steps[i];
+      if (st.index) {
+        ch.words.insert(ch.words.end(), {FE_STEP_INDEX, (uint32_t)(int32_t)st.idx});
+        continue;
+      }
+      const Trie::N& tn = ps->trie.nodes[ch.trie[i]];
+      if (tn.keep_all) {
+        ch.words.insert(ch.words.end(), {FE_STEP_SCAN, ps->lookup(st.key)});
+        continue;
+      }
+      auto it = tn.slot.find(st.key);
+      if (it == tn.slot.end()) throw std::runtime_error("compiler: list key missing from projection trie: " + st.key);
+      ch.words.insert(ch.words.end(), {FE_STEP_SLOT, it->second});
+    }
   }
 }
 

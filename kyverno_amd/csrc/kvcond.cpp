@@ -592,28 +592,56 @@ uint32_t compile_deny(PolicySet& ps, const JDoc& d, uint32_t node) {
   return it->second + 1;
 }
 
-uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node) {
-  // validate.foreach: a list of exactly one entry {list, preconditions?, deny} (with several, keys
-  // of entry k-1's last element leak into entry k's `element`: kvcond.h)
+namespace {
+// interning text of a pattern document (key order as written)
+void pattern_text(const PV& p, std::string* o) {
+  switch (p.t) {
+    case J_MAP:
+      *o += '{';
+      for (size_t i = 0; i < p.mk.size(); i++) {
+        *o += std::to_string(p.mk[i].size()) + ":" + p.mk[i] + "=";
+        pattern_text(p.mv[i], o);
+      }
+      *o += '}';
+      break;
+    case J_ARR:
+      *o += '[';
+      for (const PV& e : p.a) {
+        pattern_text(e, o);
+        *o += ',';
+      }
+      *o += ']';
+      break;
+    default: *o += pv_key(p); break;
+  }
+}
+}  // namespace
+
+uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern) {
+  // validate.foreach: a list of exactly one entry {list, preconditions?, deny | pattern} (with
+  // several, keys of entry k-1's last element leak into entry k's `element`: kvcond.h)
   if (d.at(node).t != J_ARR || d.at(node).count != 1) return 0;
   const uint32_t en = d.at(node).first;
   if (d.at(en).t != J_MAP) return 0;
-  int64_t ln = -1, pn = -1, dn = -1;
+  int64_t ln = -1, pn = -1, dn = -1, tn = -1;
   for (uint32_t c = d.at(en).first; c < d.at(en).first + d.at(en).count; c++) {
     const std::string_view k = d.key(d.at(c));
     if (k == "list") ln = c;
     else if (k == "preconditions") pn = c;
     else if (k == "deny") dn = c;
-    else return 0;  // pattern, anyPattern, context, ...
+    else if (k == "pattern" && pattern) tn = c;
+    else return 0;  // anyPattern, context, ... (and pattern without KV_COMPILE_FOREACH_PATTERN)
   }
-  if (ln < 0 || dn < 0 || d.at((uint32_t)ln).t != J_STR) return 0;
+  // a pattern entry: the pattern a map, no deny beside it
+  if (tn >= 0 && (dn >= 0 || d.at((uint32_t)tn).t != J_MAP)) return 0;
+  if (ln < 0 || (dn < 0 && tn < 0) || d.at((uint32_t)ln).t != J_STR) return 0;
   const std::string list(d.sval(d.at((uint32_t)ln)));
   if (!list_query_in_scope(list)) return 0;
   if (pn >= 0 && d.at((uint32_t)pn).t == J_NULL) pn = -1;
   // the old list form of an entry's preconditions fails common.ToMap and is dropped by the
   // reference (validation.go:260-266): left to it
   if (pn >= 0 && d.at((uint32_t)pn).t != J_MAP) return 0;
-  const int64_t cn = deny_conditions(d, (uint32_t)dn);
+  const int64_t cn = tn >= 0 ? 0 : deny_conditions(d, (uint32_t)dn);
   if (cn < 0) return 0;
   // checkpoint: an entry outside the scope leaves nothing behind
   const size_t l0 = ps.flists.size(), k0 = ps.elem.keys.size(), c0 = ps.elem.conds.size();
@@ -645,7 +673,21 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node) {
   }
   sp.tag = "d" + std::to_string(s.list) + ":";
   std::string did;
-  if (!compile_deny_block(sp, d, (uint32_t)cn, &s.deny, &did)) return rollback();
+  if (tn >= 0) {
+    did = "P";
+    pattern_text(to_pv(d, (uint32_t)tn), &did);
+  } else if (!compile_deny_block(sp, d, (uint32_t)cn, &s.deny, &did)) {
+    return rollback();
+  }
+  const std::string id = std::to_string(s.list) + "|" + (s.has_pre ? set_key(s.pre) : std::string("none")) + "|" + did;
+  auto it = ps.fset_id.find(id);
+  // a pattern entry met for the first time: its program, rooted at the list's element
+  if (tn >= 0 && it == ps.fset_id.end()) {
+    if (!(*pattern)((uint32_t)tn, list, s.list, &s)) return rollback();
+    s.pattern = true;
+    s.pat = (uint32_t)ps.fpats.size();
+    ps.fpats.push_back((uint32_t)ps.fsets.size());
+  }
   // the strings this entry added: their list, resolver mode and column in the list's element rows
   for (size_t i = ps.fkeys.size(); i < ps.elem.keys.size(); i++) {
     const std::string& t = ps.elem.keys[i];
@@ -657,8 +699,6 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node) {
     ps.flist_keys[s.list].push_back((uint32_t)i);
     ps.fkeys.push_back(std::move(k));
   }
-  const std::string id = std::to_string(s.list) + "|" + (s.has_pre ? set_key(s.pre) : std::string("none")) + "|" + did;
-  auto it = ps.fset_id.find(id);
   if (it == ps.fset_id.end()) {
     it = ps.fset_id.emplace(id, (uint32_t)ps.fsets.size()).first;
     ps.fsets.push_back(std::move(s));
@@ -875,12 +915,20 @@ void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out) {
   // the sets: row s of gate / deny is foreach set s; entries carry the string's column
   std::vector<BlockRef> gate, deny;
   for (const FeSet& s : ps.fsets) {
-    h.sets.insert(h.sets.end(), {s.list, s.has_pre ? 1u : 0u, 0u, 0u});
+    // (a pattern set: an empty deny row, never folded; word 2 names its pattern set)
+    h.sets.insert(h.sets.end(), {s.list, s.has_pre ? 1u : 0u, s.pattern ? 1u + s.pat : 0u, 0u});
     gate.push_back({&s.pre, nullptr});
     deny.push_back({&s.deny.fold, &s.deny.strs});
   }
   pack_sets(ps.elem.conds, gate, key_col, &h.gate);
   pack_sets(ps.elem.conds, deny, key_col, &h.deny);
+  // the pattern sets: their program and the path to their list's elements
+  for (uint32_t fs : ps.fpats) {
+    const FeSet& s = ps.fsets[fs];
+    const FeChain& c = ps.fchains.at(s.list);
+    h.pats.insert(h.pats.end(), {fs, s.prog, (uint32_t)(h.chain.size() / 2), (uint32_t)(c.words.size() / 2)});
+    h.chain.insert(h.chain.end(), c.words.begin(), c.words.end());
+  }
 }
 
 FeTables FeHost::view() const {
@@ -897,7 +945,13 @@ FeTables FeHost::view() const {
   return t;
 }
 
+FePatTables FeHost::pat_view() const {
+  return FePatTables{pats.data(), chain.data(), first.data(), (uint32_t)(pats.size() / 4)};
+}
+
 uint8_t foreach_fold_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_t r, uint32_t* elem) {
+  // (a pattern set's elements are walked on the device only: no host evaluator)
+  if (h.sets[4 * set + 2]) throw std::runtime_error("foreach_fold_host: a pattern set has no host fold");
   const FeTables t = h.view();
   const uint32_t list = h.sets[4 * set];
   const uint32_t n_el = h.lists[4 * list + 1], el0 = h.lists[4 * list + 3];

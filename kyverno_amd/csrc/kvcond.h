@@ -20,6 +20,7 @@
 // entry packer, one plane filler and one fold serve all three.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -28,6 +29,7 @@
 namespace kv {
 struct CondBlocks;  // kvblocks.h
 struct FeTables;    // kvforeach.h
+struct FePatTables;
 }
 
 namespace kvh {
@@ -117,22 +119,44 @@ std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, u
 //  * device (kvforeach.h, kv_foreach_elem_kernel, kv_foreach_fin_kernel): a lane per element, a
 //    segmented first-decisive-element reduction into 32-bit keys, a byte per (set, resource) in
 //    the rows of DevBatch::deny_st after the deny sets'.
+// Pattern entries (KV_COMPILE_FOREACH_PATTERN; validation.go:187-193,341-345,421-445: with
+// `pattern` set the element's validate() ends in MatchPattern(element, pattern), the element map as
+// the whole resource). Scope: one entry {list, preconditions?, pattern}, the pattern a map without
+// {{ }} variables and without a `metadata` key, inside what the pattern compiler accepts.
+//  * compile: the pattern is compiled by the pattern compiler (kvcompile.cpp) rooted at the
+//    projection-trie node of the list's elements, so the projection keeps the pattern's keys under
+//    them; a foreach set is then (list, gate, pattern program + root pattern node), interned like
+//    the others; PolicySet::fchains holds the list's path as the device walks it;
+//  * device (kvwalk.h, kv_foreach_pat_kernel): a lane per element finds its element's node along
+//    the list path, runs the entry gate and the bytecode walk of kv_validate_kernel with the element
+//    as the root, and feeds its code into the reduction of kv_foreach_elem_kernel; the deciding
+//    element's 8-byte error record goes to fe_rec[pattern set][res] (kv_foreach_rec_kernel).
+//  * An element whose verdict the int64 / float64 typing of a number could change (the element
+//    comes out of the JSON context: every number float64) is ST_CPU: kvwalk.h.
 // Parses the `validate.foreach` node of a rule: 0 when it is outside the device scope (the rule
-// stays CPU-routed, reason "foreach"), else 1 + the interned foreach set's index.
-uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node);
+// stays CPU-routed, reason "foreach"), else 1 + the interned foreach set's index. `pattern`
+// (KV_COMPILE_FOREACH_PATTERN; null: pattern entries stay outside the scope) compiles the entry's
+// pattern node for list `list` (index `list_index`) into s->prog / s->root_pnode and records the
+// list's path (PolicySet::fchains); false: outside the scope (no instruction or set is left behind; kvcompile.cpp).
+using FePatternCompiler = std::function<bool(uint32_t pattern_node, const std::string& list, uint32_t list_index, FeSet* s)>;
+uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern = nullptr);
 
 struct FeHost {
   // row s of gate / deny: the entry preconditions / the deny block of foreach set s. deny holds the
   // outcome ids and every plane; gate only sets and entries (its view reads deny's outc, truth, unk)
   CondHost gate, deny;
   std::vector<uint32_t> sets, lists, el_res, el_ord, lstate;  // kvforeach.h FeTables
-  std::vector<uint32_t> first;  // [list][res]: the resource's first element in the list's block (host only)
+  std::vector<uint32_t> first;  // [list][res]: the resource's first element in the list's block (the host
+                                // accessors; on the device only kv_foreach_rec_kernel reads it)
+  std::vector<uint32_t> pats, chain;  // kvforeach.h FePatTables: the pattern sets and their lists' paths
   uint32_t max_el = 0;
   kv::FeTables view() const;
+  kv::FePatTables pat_view() const;
 };
 void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out);
 // one (foreach set, store resource) on the host, as the two kernels: ST_PASS, ST_FAIL, ST_ERROR,
-// ST_SKIP or ST_CPU; *elem the deciding element's index in its list, 0xFFFFFFFF without one
+// ST_SKIP or ST_CPU; *elem the deciding element's index in its list, 0xFFFFFFFF without one.
+// Throws for a pattern set (its elements are walked on the device only)
 uint8_t foreach_fold_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_t r, uint32_t* elem);
 // the error of the first unresolved deny string of element `elem` of store resource r, in the
 // order of deny_error_host

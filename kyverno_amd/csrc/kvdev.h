@@ -24,8 +24,16 @@ hipError_t launch_cond(bool strict, const CondBlocks& T, uint32_t n_res, uint32_
 
 // The foreach fold of a batch (kvforeach.h): clears fe_acc[set][res] (32-bit keys), reduces every
 // set's elements into it and writes fe_st[set][res], with the deny fold. T holds device pointers.
+// With pattern sets (Q, kvforeach.h FePatTables; KV_COMPILE_FOREACH_PATTERN): their elements go
+// through kv_foreach_pat_kernel (kvwalk.h: the pattern walk over the policy set's and the batch's
+// device views P and B, whose node rows must be in place on `stream`), the 8-byte records of
+// their FAIL / ERROR elements into the transient erec[pattern set][T.max_el], the deciding
+// element's into fe_rec[pattern set][res].
 struct FeTables;
-hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream);
+struct FePatTables;
+hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream,
+                          const FePatTables* Q = nullptr, const DevPS* P = nullptr, const DevBatch* B = nullptr,
+                          uint2* erec = nullptr, uint2* fe_rec = nullptr);
 
 // Match tables of a pass (DevPS::mt_*): `words` = mt_ns_words + mt_ann_words +
 // mt_sel_words rows, max_entities = max(n_nsm, n_asets, n_lsets).

@@ -1,7 +1,7 @@
 // validate.foreach on the device (kvcond.h): the list states, the per-element verdict and the
-// reduction keys, shared by kv_foreach_elem_kernel / kv_foreach_fin_kernel (kvkernel.hip) and the
-// host fold (kvcond.cpp foreach_fold_host). Plain code over the tables of kvcond.h FeHost; needs
-// kv_layout.h and kvblocks.h.
+// reduction keys, shared by kv_foreach_elem_kernel / kv_foreach_pat_kernel / kv_foreach_fin_kernel
+// (kvkernel.hip) and the host fold (kvcond.cpp foreach_fold_host). Plain code over the tables of
+// kvcond.h FeHost; needs kv_layout.h and kvblocks.h.
 #pragma once
 
 namespace kv {
@@ -21,7 +21,7 @@ constexpr uint32_t FE_KEY_NONE = 0xFFFFFFFFu;
 // The device view of FeHost (32-bit words throughout). Row s of gate / deny is foreach set s; the
 // two share outc and the truth / unknown planes, and their string rows are columns of the set's list.
 struct FeTables {
-  const uint32_t* sets;    // 4 words per foreach set: list, has_pre, 0, 0
+  const uint32_t* sets;    // 4 words per foreach set: list, has_pre, 1 + pattern set (0: a deny block), 0
   const uint32_t* lists;   // 4 words per list: first word of its outc block, elements, first plane row, first element
   CondBlocks gate;         // the entry preconditions of every set (preconditions resolver: no err / oos)
   CondBlocks deny;         // the deny block of every set; outc: per list a block [string of the list][element
@@ -30,6 +30,18 @@ struct FeTables {
   const uint32_t* el_ord;  // per list block: the element's index in its list
   const uint32_t* lstate;  // [list][res]: FE_LIST_*
   uint32_t n_sets, n_lists, max_el;
+};
+
+// Pattern sets (KV_COMPILE_FOREACH_PATTERN, kvwalk.h): the foreach sets whose entry carries a
+// `pattern`. A lane finds its element's node from the resource's root along the list's path.
+constexpr uint32_t FE_STEP_SLOT = 0;   // a field: the slot of the key in the map's slot list
+constexpr uint32_t FE_STEP_INDEX = 1;  // an index (a negative one counts from the end)
+constexpr uint32_t FE_STEP_SCAN = 2;   // a field of a keep-all map: the key id
+struct FePatTables {
+  const uint32_t* pats;   // 4 words per pattern set: foreach set, first instruction, first step, steps
+  const uint32_t* chain;  // 2 words per step of a list path: FE_STEP_*, slot | index | key id
+  const uint32_t* first;  // [list][res]: the resource's first element in the list's block
+  uint32_t n_pats;
 };
 
 // One element of foreach set `set`: element e of the set's list (e < its element count).

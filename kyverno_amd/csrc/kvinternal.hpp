@@ -107,12 +107,32 @@ struct FeKey {
 };
 // One interned foreach set: the list, the entry's preconditions (has_pre: a gate is left after
 // constant folding) and its deny block; CondRec indices into PolicySet::elem.conds, string indices
-// into PolicySet::fkeys.
+// into PolicySet::fkeys. A pattern set (KV_COMPILE_FOREACH_PATTERN) has the entry's `pattern`
+// instead of a deny block: a pattern program rooted at the list's element (`prog`, its root
+// pattern node `root_pnode`) and its index among the pattern sets (`pat`, PolicySet::fpats).
 struct FeSet {
   uint32_t list = 0;
   bool has_pre = false;
   CondSet pre;
   DenySet deny;
+  bool pattern = false;
+  uint32_t prog = 0, root_pnode = 0, pat = 0;
+};
+// One step of a foreach list path (kvvars.cpp list_query_steps): a field or an index
+struct ListStep {
+  bool index = false;
+  std::string key;
+  long idx = 0;
+};
+// The list path of a foreach list with pattern sets, as the device walks it from the resource's
+// root node: per step the projection-trie node of the map it is looked up in (fields; resolved to
+// a slot or a key id once the slots are assigned, compile_policies) or the index.
+struct FeChain {
+  std::vector<ListStep> steps;
+  std::vector<uint32_t> trie;  // per step: the trie node the step starts from
+  uint32_t elem_trie = 0;      // the trie node of the list's elements (the pattern's root)
+  // resolved: 2 words per step, (FE_STEP_*, slot | key id | index)
+  std::vector<uint32_t> words;
 };
 
 // Projection trie over resource key paths referenced by any compiled pattern
@@ -257,13 +277,19 @@ struct PolicySet {
   std::vector<std::vector<uint32_t>> flist_keys;
   std::vector<FeSet> fsets;
   std::unordered_map<std::string, uint32_t> flist_id, fset_id;
+  // pattern entries (KV_COMPILE_FOREACH_PATTERN): the foreach sets that carry a pattern, in order
+  // (FeSet::pat indexes it), and per list the path the device walks to its elements (empty steps:
+  // no pattern set reads the list)
+  std::vector<uint32_t> fpats;
+  std::vector<FeChain> fchains;
   // columns of a Batch::vout row: the pattern-variable keys, then the condition strings of the
   // preconditions, then those of the deny blocks
   size_t vout_width() const { return vkeys.size() + gate.keys.size() + deny.keys.size(); }
 };
 
 // Compiles a JSON list of (already autogen-expanded) ClusterPolicy/Policy
-// objects (flags: kv_compile's KV_COMPILE_DENY | KV_COMPILE_FOREACH). Throws std::runtime_error on malformed input.
+// objects (flags: kv_compile's KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN). Throws
+// std::runtime_error on malformed input.
 void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flags = 0);
 
 // Host memory of the large store arrays of an ingested batch. libkvgpu (kvmem.cpp)
@@ -456,6 +482,8 @@ std::string resolve_var_string(const std::string& tmpl, const std::string& path,
 bool cond_string_in_scope(const std::string& s, bool element = false);
 // a foreach entry's `list`: a bare request.object field / quoted-field / index chain
 bool list_query_in_scope(const std::string& q);
+// its steps after `request.object` (false: outside the scope)
+bool list_query_steps(const std::string& q, std::vector<ListStep>* out);
 // One foreach list on resource `d` (pkg/engine/validation.go:225-283 evaluateList and the element
 // loop): returns the list state (kv::FE_LIST_*); for FE_LIST_OK appends the nodes of the elements
 // (all maps) to *elems.

@@ -26,8 +26,6 @@
 
 using namespace kv;
 
-#define KV_MAXD 16
-#define KV_MAXL 4
 #define KV_RCHUNK 64
 
 #include "kvdevfn.h"
@@ -35,6 +33,7 @@ using namespace kv;
 #include "kvcol.h"
 #include "kvblocks.h"
 #include "kvforeach.h"
+#include "kvwalk.h"
 
 // ------------------------------------------------------------------ kernel
 extern "C" __global__ __launch_bounds__(KV_WG) __attribute__((amdgpu_waves_per_eu(4))) void kv_validate_kernel(const DevPS* __restrict__ Pp,
@@ -96,231 +95,14 @@ extern "C" __global__ __launch_bounds__(KV_WG) __attribute__((amdgpu_waves_per_e
         else if (uni(rr.deny)) st = B.deny_st[(size_t)(uni(rr.deny) - 1u) * n_res + r];
         else run = true;
       }
-      uint32_t ekind = 0, eflags = 0, epn = 0, ekey = ABSENT, eres = ABSENT;
-      uint32_t eidx0 = 0, eidx1 = 0, eidx2 = 0, eidx3 = 0;
-      if (__ballot(run)) {
-        uint64_t areg = 0, apres = 0;
-        uint32_t keynode = ABSENT;
-        uint32_t wait = run ? 0u : KV_SENT;
-        uint32_t pc = uni(rr.prog);
-        s_cur[0][lane] = rroot;
-        auto raise = [&](uint32_t kind, uint32_t pn, uint32_t rn, uint32_t cpc) {
-          ekind = kind;
-          eflags = 0;
-          epn = pn;
-          eres = rn;
-          ekey = keynode;
-          eidx0 = s_li[wv][0];
-          eidx1 = s_li[wv][1];
-          eidx2 = s_li[wv][2];
-          eidx3 = s_li[wv][3];
-          wait = cpc;
-        };
-        uint32_t guard = 0;
-        while (true) {
-          // every program terminates (forward pcs, loops bounded by array lengths);
-          // the guard only turns an interpreter bug into a CPU-routed verdict instead of a hung wave
-          if (++guard > (1u << 24)) {
-            if (wait != KV_SENT) st = ST_CPU;
-            break;
-          }
-          if (wait == pc) wait = 0;
-          if (!__ballot(wait == 0)) {
-            const uint32_t m = uni(wave_min(wait));
-            if (m == KV_SENT) break;
-            pc = m;
-            continue;
-          }
-          const Inst& in = P.prog[pc];
-          const uint32_t opw = uni(in.op);
-          const uint32_t op = opw & 0xFF;
-          const uint32_t d = (opw >> 8) & 0xFF;
-          const uint32_t aux = (opw >> 16) & 0xFF;
-          const uint32_t ia = uni(in.a), ib = uni(in.b), ic = uni(in.c);
-          const bool A = wait == 0;
-          uint32_t next = pc + 1;
-          switch (op) {
-            case OP_MAPCHK:
-            case OP_ARRCHK:
-              if (A) {
-                const uint32_t v = s_cur[d][lane];
-                const uint32_t want = op == OP_MAPCHK ? NT_MAP : NT_ARR;
-                if (v == ABSENT || node_type(N[v].kt) != want) raise(op == OP_MAPCHK ? E_TYPE_MAP : E_TYPE_ARR, ia, v, ic);
-              }
-              break;
-            case OP_AREG:
-              if (A) {
-                areg |= 1ull << (aux & 63);
-                if (lookup_op(N, s_cur[d][lane], ia, aux) != ABSENT) apres |= 1ull << (aux & 63);
-              }
-              break;
-            case OP_KEY:
-            case OP_KEYV:
-              if (A) {
-                const uint32_t c = lookup_op(N, s_cur[d][lane], ia, aux);
-                s_cur[d + 1][lane] = c;
-                if (op == OP_KEY && c == ABSENT) wait = ib;
-              }
-              break;
-            case OP_KEYGLOB:
-              if (A) {
-                uint32_t node;
-                if (keyglob_op(P, B, N, s_cur[d][lane], opw, ia, ic, &node, &keynode)) s_cur[d + 1][lane] = node;
-                else wait = ib;
-              }
-              break;
-            case OP_SCOPE_END:
-            case OP_POS_END:
-              if (A && ekind) {
-                if (op == OP_POS_END) {
-                  if (eflags & EF_COND) ekind = 0;
-                  else wait = ic;
-                } else {
-                  eflags |= aux;
-                  wait = ic;
-                }
-              }
-              break;
-            case OP_NEG:
-              if (A && lookup_op(N, s_cur[d][lane], ia, aux) != ABSENT) raise(E_NEG, ib, ABSENT, ic);
-              break;
-            case OP_STAR:
-              if (A) {
-                const uint32_t v = s_cur[d + 1][lane];
-                if (v == ABSENT || node_type(N[v].kt) == NT_NULL) raise(E_STAR, ib, ABSENT, ic);
-              }
-              break;
-            case OP_LEAF:
-              if (A) {
-                const uint32_t v = s_cur[d][lane];
-                Node vn{NT_NULL, 0, 0, 0};
-                if (v != ABSENT) vn = N[v];
-                const uint32_t vt = node_type(vn.kt);
-                bool ok;
-                if (vt == NT_ARR) {
-                  ok = true;
-                  for (uint32_t k = 0; k < vn.b && ok; k++) ok = pred_node(P, B, N, ia, ni(vn.a + k));
-                } else {
-                  ok = pred_eval(P, B, ia, vt, vn);
-                }
-                if (!ok) raise(E_VALUE, ib, v, ic);
-              }
-              break;
-            case OP_VLEAF:  // the resource's substituted pattern value (kvvars.cpp): batch predicate table
-              if (A) {
-                const uint32_t v = s_cur[d][lane];
-                const uint32_t dp = B.dleaf[(size_t)ia * n_res + r];
-                Node vn{NT_NULL, 0, 0, 0};
-                if (v != ABSENT) vn = N[v];
-                const uint32_t vt = node_type(vn.kt);
-                bool ok;
-                if (vt == NT_ARR) {
-                  ok = true;
-                  for (uint32_t k = 0; k < vn.b && ok; k++) ok = pred_node(*B.dps, B, N, dp, ni(vn.a + k));
-                } else {
-                  ok = pred_eval(*B.dps, B, dp, vt, vn);
-                }
-                if (!ok) raise(E_VALUE, ib, v, ic);
-              }
-              break;
-            case OP_RAISE:
-              if (A) raise(ib, ia, s_cur[d][lane], ic);
-              break;
-            case OP_EXISTCHK:
-              if (A) {
-                const uint32_t v = s_cur[d][lane];
-                if (v == ABSENT || node_type(N[v].kt) != NT_ARR) raise(E_EXIST_RESTYPE, ia, v, ic);
-              }
-              break;
-            case OP_LENCHK:
-              if (A && N[s_cur[d][lane]].b < ia) raise(E_LEN, ib, s_cur[d][lane], ic);
-              break;
-            case OP_INDEX:
-              if (A) s_cur[d + 1][lane] = ni(N[s_cur[d][lane]].a + ia);
-              break;
-            case OP_LOOP_BEGIN:
-            case OP_EXIST_BEGIN: {
-              if (A) {
-                const Node an = N[s_cur[d][lane]];
-                s_lfirst[aux][lane] = an.a;
-                s_llen[aux][lane] = an.b;
-                if (an.b == 0) {
-                  if (op == OP_LOOP_BEGIN) wait = ia + 1;
-                  else raise(E_EXIST_FAIL, ib, s_cur[d][lane], ic);
-                } else {
-                  s_cur[d + 1][lane] = ni(an.a);
-                }
-              }
-              if (lane % 64 == 0) s_li[wv][aux] = 0;
-              break;
-            }
-            case OP_LOOP_END:
-            case OP_EXIST_END: {
-              bool cont = false;
-              if (A) {
-                if (op == OP_LOOP_END) {
-                  if (ekind) {
-                    if (eflags & EF_COND) { ekind = 0; cont = true; }
-                    else wait = ic;
-                  } else {
-                    cont = true;
-                  }
-                } else {
-                  if (ekind) { ekind = 0; cont = true; }  // element failed: try the next one
-                  else wait = pc + 1;                       // found
-                }
-                if (cont) {
-                  const uint32_t i = s_li[wv][aux] + 1;
-                  if (i < s_llen[aux][lane]) {
-                    s_cur[d + 1][lane] = ni(s_lfirst[aux][lane] + i);
-                  } else {
-                    cont = false;
-                    if (op == OP_LOOP_END) wait = pc + 1;
-                    else raise(E_EXIST_FAIL, ib, s_cur[d][lane], ic);
-                  }
-                }
-              }
-              if (__ballot(cont)) {
-                if (lane % 64 == 0) s_li[wv][aux] += 1;
-                next = ia + 1;
-              }
-              break;
-            }
-            case OP_ALT_BEGIN:
-              if (A) { ekind = 0; eflags = 0; areg = 0; apres = 0; }
-              break;
-            case OP_ALT_END:
-              if (A) {
-                if (ekind == 0) { st = ST_PASS; wait = KV_SENT; }
-                else if (ekind == E_CPU) { st = ST_CPU; wait = KV_SENT; }
-                else if (ib) { st = ST_FAIL; wait = KV_SENT; }
-                else { ekind = 0; eflags = 0; areg = 0; apres = 0; }
-              }
-              break;
-            case OP_DONE:
-              if (A) {
-                if (ekind == 0) st = ST_PASS;
-                else if (ekind == E_CPU) st = ST_CPU;
-                else if (eflags & (EF_COND | EF_GLOBAL)) st = ST_SKIP;
-                else if (areg & ~apres) st = ST_ERROR;
-                else if (ekind == E_LEN) st = ST_ERROR;
-                else st = ST_FAIL;
-                wait = KV_SENT;
-              }
-              next = KV_SENT;
-              break;
-            default:
-              break;
-          }
-          if (next == KV_SENT) break;
-          pc = next;
-        }
-      }
+      EState e{0, 0, 0, ABSENT, ABSENT, 0, 0, 0, 0};
+      bool cpu = false;  // (the element walk's)
+      kv_walk<false>(P, B, N, &rr.prog, rroot, run, r, n_res, 0u, s_cur, s_lfirst, s_llen, s_li, st, e, cpu);
       if (valid && (O.full & 1)) {
         const size_t o = (size_t)ri * n_res + r;
         O.status[o] = (uint8_t)st;
         if ((O.full & 2) && (st == ST_FAIL || st == ST_ERROR || st == ST_SKIP))
-          store_err(O, ri, n_res, r, ekind, eflags, epn, ekey, eres, eidx0, eidx1, eidx2, eidx3);
+          store_err(O, ri, n_res, r, e.kind, e.flags, e.pn, e.key, e.res, e.i0, e.i1, e.i2, e.i3);
       }
       // histogram: one LDS atomic per (wave, status) via ballot popcount
       for (uint32_t s = 0; s < 7; s++) {
@@ -412,11 +194,38 @@ hipError_t launch_cond(bool strict, const CondBlocks& T, uint32_t n_res, uint32_
 // of a resource is its first decisive element whatever waves and workgroups the segment
 // straddles. Lanes past the list's end form pieces with nothing to write. No lane leaves before
 // the wave operations.
+// (kv_fe_reduce: that reduction, shared with kv_foreach_pat_kernel; `row` = fe_acc + set * n_res)
+__device__ __forceinline__ void kv_fe_reduce(uint32_t lane, bool valid, uint32_t res, uint32_t ord, uint32_t code,
+                                             uint32_t n_res, uint32_t* __restrict__ row) {
+  const uint32_t prev = __shfl_up(res, 1);
+  const bool head = lane == 0u || prev != res;
+  const uint64_t heads = __ballot(head);
+  const uint64_t mf = __ballot(code == ST_FAIL), me = __ballot(code == ST_ERROR), mc = __ballot(code == ST_CPU);
+  const uint64_t mp = __ballot(valid && code == ST_PASS);
+  if (head && valid) {
+    // the piece: lanes [lane, next head)
+    const uint64_t above = lane == 63u ? 0ull : heads & (~0ull << (lane + 1u));
+    const uint64_t upto = above ? (1ull << __builtin_ctzll(above)) - 1ull : ~0ull;
+    const uint64_t piece = upto & (~0ull << lane);
+    const uint64_t dec = (mf | me | mc) & piece;
+    uint32_t key = FE_KEY_NONE;
+    if (dec) {
+      const uint32_t l = (uint32_t)__builtin_ctzll(dec);
+      const uint32_t c = (mf >> l) & 1ull ? ST_FAIL : (me >> l) & 1ull ? ST_ERROR : ST_CPU;
+      key = (ord + (l - lane)) << 3 | c;
+    } else if (mp & piece) {
+      key = FE_KEY_PASS;
+    }
+    if (key != FE_KEY_NONE && res < n_res) atomicMin(&row[res], key);
+  }
+}
+
 extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_elem_kernel(FeTables T, uint32_t n_res,
                                                                             uint32_t* __restrict__ fe_acc) {
   const uint32_t e = blockIdx.x * KV_WG + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
   for (uint32_t s = blockIdx.y; s < T.n_sets; s += gridDim.y) {
+    if (T.sets[4u * s + 2u]) continue;  // (a pattern set: kv_foreach_pat_kernel's)
     const uint32_t* L = T.lists + 4u * T.sets[4u * s];
     const uint32_t n_el = L[1], el0 = L[3];
     if (blockIdx.x * KV_WG >= n_el) continue;  // (workgroup-uniform)
@@ -427,27 +236,48 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_elem_kernel(FeTab
       ord = T.el_ord[el0 + e];
       code = kv_foreach_elem(T, s, e);
     }
-    const uint32_t prev = __shfl_up(res, 1);
-    const bool head = lane == 0u || prev != res;
-    const uint64_t heads = __ballot(head);
-    const uint64_t mf = __ballot(code == ST_FAIL), me = __ballot(code == ST_ERROR), mc = __ballot(code == ST_CPU);
-    const uint64_t mp = __ballot(valid && code == ST_PASS);
-    if (head && valid) {
-      // the piece: lanes [lane, next head)
-      const uint64_t above = lane == 63u ? 0ull : heads & (~0ull << (lane + 1u));
-      const uint64_t upto = above ? (1ull << __builtin_ctzll(above)) - 1ull : ~0ull;
-      const uint64_t piece = upto & (~0ull << lane);
-      const uint64_t dec = (mf | me | mc) & piece;
-      uint32_t key = FE_KEY_NONE;
-      if (dec) {
-        const uint32_t l = (uint32_t)__builtin_ctzll(dec);
-        const uint32_t c = (mf >> l) & 1ull ? ST_FAIL : (me >> l) & 1ull ? ST_ERROR : ST_CPU;
-        key = (ord + (l - lane)) << 3 | c;
-      } else if (mp & piece) {
-        key = FE_KEY_PASS;
-      }
-      if (key != FE_KEY_NONE && res < n_res) atomicMin(&fe_acc[(size_t)s * n_res + res], key);
-    }
+    kv_fe_reduce(lane, valid, res, ord, code, n_res, fe_acc + (size_t)s * n_res);
+  }
+}
+
+// kv_foreach_pat_kernel (KV_COMPILE_FOREACH_PATTERN, kvwalk.h): the elements of the pattern sets.
+// The launch shape of kv_foreach_elem_kernel with grid.y = pattern sets. A lane finds its
+// element's node from its resource's root along the list's path (FePatTables::chain: a slot or
+// key-id lookup per field, child k per index; the node the path ends in is the list, the element
+// child el_ord of it, or a single map, the one element itself), runs the entry gate, then
+// the pattern walk with the element as the root (MatchPattern(element, pattern)), and feeds its
+// code into kv_fe_reduce. ST_CPU where the device cannot show parity: an undecided gate, a path
+// that does not end in a map or a list of maps, an int64-typed number where the float64 typing of
+// the reference's element could change the verdict (kvwalk.h), an error record that does not fit
+// 8 bytes. The 8-byte record of a FAIL / ERROR element goes to erec[pattern set][element];
+// kv_foreach_rec_kernel picks the deciding element's. No lane leaves before the wave operations: lanes past the list's end and
+// lanes without an element node go through the walk parked.
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_pat_kernel(FeTables T, FePatTables Q,
+                                                                           const DevPS* __restrict__ Pp,
+                                                                           const DevBatch* __restrict__ Bp,
+                                                                           uint32_t n_res, uint32_t* __restrict__ fe_acc,
+                                                                           uint2* __restrict__ erec) {
+  __shared__ uint32_t s_cur[KV_MAXD][KV_WG];
+  __shared__ uint32_t s_lfirst[KV_MAXL][KV_WG];
+  __shared__ uint32_t s_llen[KV_MAXL][KV_WG];
+  __shared__ uint32_t s_li[KV_WG / 64][KV_MAXL];
+  const DevPS& P = *Pp;
+  const DevBatch& B = *Bp;
+  const Node* __restrict__ N = B.nodes;
+  const uint32_t e = blockIdx.x * KV_WG + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t p = blockIdx.y; p < Q.n_pats; p += gridDim.y) {
+    const uint32_t* PT = Q.pats + 4u * p;
+    const uint32_t s = uni(PT[0]);
+    const uint32_t* L = T.lists + 4u * T.sets[4u * s];
+    const uint32_t n_el = L[1], el0 = L[3];
+    if (blockIdx.x * KV_WG >= n_el) continue;  // (workgroup-uniform)
+    const bool valid = e < n_el;
+    uint32_t res, ord;
+    uint2 w;
+    const uint32_t code = kv_fe_pat_lane(T, Q, P, B, N, p, e, valid, n_res, s_cur, s_lfirst, s_llen, s_li, &res, &ord, &w);
+    if (valid && (code == ST_FAIL || code == ST_ERROR)) erec[(size_t)p * T.max_el + e] = w;
+    kv_fe_reduce(lane, valid, res, ord, code, n_res, fe_acc + (size_t)s * n_res);
   }
 }
 
@@ -464,17 +294,46 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_fin_kernel(FeTabl
         (uint8_t)kv_fe_final(T.lstate[(size_t)T.sets[4u * s] * n_res + r], fe_acc[(size_t)s * n_res + r]);
 }
 
+// kv_foreach_rec_kernel: one lane per resource, grid.y = pattern sets; the 8-byte record of the
+// element that decided a FAIL / ERROR key (element FePatTables::first[list][res] + its index, of
+// erec) into fe_rec[pattern set][res], zero for every other resource.
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_rec_kernel(FeTables T, FePatTables Q, uint32_t n_res,
+                                                                           const uint32_t* __restrict__ fe_acc,
+                                                                           const uint2* __restrict__ erec,
+                                                                           uint2* __restrict__ fe_rec) {
+  const uint64_t r = (uint64_t)blockIdx.x * KV_WG + threadIdx.x;
+  if (r >= n_res) return;
+  for (uint32_t p = blockIdx.y; p < Q.n_pats; p += gridDim.y) {
+    const uint32_t s = Q.pats[4u * p], list = T.sets[4u * s];
+    const uint32_t key = fe_acc[(size_t)s * n_res + r], c = key & 7u;
+    uint2 w = make_uint2(0u, 0u);
+    if (key < FE_KEY_PASS && (c == ST_FAIL || c == ST_ERROR)) {
+      const uint64_t e = (uint64_t)Q.first[(size_t)list * n_res + r] + (key >> 3);
+      if (e < T.lists[4u * list + 1u]) w = erec[(size_t)p * T.max_el + e];
+    }
+    fe_rec[(size_t)p * n_res + r] = w;
+  }
+}
+
 namespace kv {
-hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream) {
+hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream,
+                          const FePatTables* Q, const DevPS* P, const DevBatch* B, uint2* erec, uint2* fe_rec) {
   if (n_res == 0 || T.n_sets == 0) return hipSuccess;
   const hipError_t e = hipMemsetAsync(fe_acc, 0xFF, (size_t)T.n_sets * n_res * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
   const uint32_t gy = T.n_sets < KV_PRE_YMAX ? T.n_sets : KV_PRE_YMAX;
-  if (T.max_el)
+  const uint32_t n_pats = Q ? Q->n_pats : 0u, py = n_pats < KV_PRE_YMAX ? n_pats : KV_PRE_YMAX;
+  if (T.max_el && T.n_sets > n_pats)
     hipLaunchKernelGGL(kv_foreach_elem_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, gy), dim3(KV_WG), 0, stream, T, n_res,
                        fe_acc);
+  if (T.max_el && n_pats)
+    hipLaunchKernelGGL(kv_foreach_pat_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, py), dim3(KV_WG), 0, stream, T, *Q, P, B,
+                       n_res, fe_acc, erec);
   hipLaunchKernelGGL(kv_foreach_fin_kernel, dim3((n_res + KV_WG - 1) / KV_WG, gy), dim3(KV_WG), 0, stream, T, n_res,
                      (const uint32_t*)fe_acc, fe_st);
+  if (n_pats)
+    hipLaunchKernelGGL(kv_foreach_rec_kernel, dim3((n_res + KV_WG - 1) / KV_WG, py), dim3(KV_WG), 0, stream, T, *Q, n_res,
+                       (const uint32_t*)fe_acc, (const uint2*)erec, fe_rec);
   return hipGetLastError();
 }
 }  // namespace kv

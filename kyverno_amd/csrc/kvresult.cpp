@@ -363,6 +363,23 @@ Pair pair_of(const kv_result* cr, uint32_t rule, uint64_t res, bool records) {
 
 bool is_record(uint8_t st) { return st == ST_FAIL || st == ST_ERROR || st == ST_SKIP; }
 
+// A pair of a device foreach rule with a pattern entry (KV_COMPILE_FOREACH_PATTERN) whose status
+// its deciding element gave: the fetched reduction key and that element's record. False for every
+// other pair (another rule, no fetched rows, a status the rule's own preconditions or match
+// decided, PASS / SKIP).
+bool pattern_pair(const Pair& q, uint32_t* key, ErrRec8* rec) {
+  const uint32_t fs = q.ps().rhost[q.rule].foreach_set;
+  if (!fs || !q.part || !q.ps().fsets[fs - 1].pattern || q.part->fe_key.empty()) return false;
+  const uint8_t st = q.status();
+  if (st != ST_FAIL && st != ST_ERROR) return false;
+  const size_t at = (size_t)q.ps().fsets[fs - 1].pat * q.part->n + q.local;
+  const uint32_t k = q.part->fe_key[at];
+  if (k >= FE_KEY_PASS || (k & 7u) != st) return false;
+  *key = k;
+  *rec = q.part->fe_rec[at];
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -510,6 +527,12 @@ int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, u
     if (!set || !q.part) return 0;  // (not a device foreach rule: not reported)
     const uint8_t st = q.status();
     if (st != ST_FAIL && st != ST_ERROR) return 0;  // (PASS, SKIP: no deciding element)
+    if (q.ps().fsets[set - 1].pattern) {  // a pattern entry: the key fetched with the statuses
+      uint32_t key;
+      ErrRec8 rec;
+      if (pattern_pair(q, &key, &rec)) *index = key >> 3;
+      return 0;
+    }
     uint32_t e = 0xFFFFFFFFu;
     if (foreach_fold_host(q.kb->fe_host(q.ps()), set - 1, q.n_local(), q.local, &e) == st) *index = e;
     return 0;
@@ -525,6 +548,16 @@ int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, c
     if (!fs || !q.part) return 0;
     const uint8_t st = q.status();
     if (st != ST_ERROR && st != ST_SKIP) return 0;
+    if (ps.fsets[fs - 1].pattern) {
+      // a pattern entry has no host fold: an ERROR is its element's pattern error
+      // (kv_result_foreach_error_message); a SKIP is "rule skipped" unless the rule's own
+      // preconditions decided it, and the fetched key tells: they leave the fold's key untouched
+      if (st != ST_SKIP || q.part->fe_key.empty()) return 0;
+      const RuleRec& rr = ps.rules[rule];
+      if (rr.pre && pre_status_host(q.kb->pre_host(ps), rr.pre - 1, q.n_local(), q.local) == ST_SKIP) return 0;
+      if (q.part->fe_key[(size_t)ps.fsets[fs - 1].pat * q.part->n + q.local] != FE_KEY_NONE) return 0;
+      return put_message("rule skipped", buf, cap);
+    }
     const FeHost& h = q.kb->fe_host(ps);
     uint32_t e = 0xFFFFFFFFu;
     // the pair recomputed from the batch's tables: a SKIP of the rule's own preconditions has
@@ -539,6 +572,37 @@ int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, c
     if (err.empty()) return 0;
     return put_message("validation failed in foreach rule for failed to substitute variables in deny conditions: " + err,
                        buf, cap);
+  });
+}
+
+int kv_result_foreach_path(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
+  return guarded(KV_E_INVALID, nullptr, [&]() -> int {
+    const Pair q = pair_of(r, rule, res, false);
+    if (q.code) return q.code;
+    uint32_t key;
+    ErrRec8 rec;
+    if (!pattern_pair(q, &key, &rec) || (key & 7u) != ST_FAIL) return KV_E_INVALID;
+    // (the set's pattern nodes start at its own root: the path is relative to the element)
+    return put_message(render_path(q.ps(), q.r->batch_of(*q.part), kv_result::decode(rec)), buf, cap);
+  });
+}
+
+int kv_result_foreach_error_message(const kv_result* r, uint32_t rule, uint64_t res, const char* element_json, size_t len,
+                                    char* buf, size_t cap) {
+  if (!element_json) return KV_E_INVALID;
+  return guarded(KV_E_PARSE, nullptr, [&]() -> int {
+    const Pair q = pair_of(r, rule, res, false);
+    if (q.code) return q.code;
+    uint32_t key;
+    ErrRec8 rec;
+    if (!pattern_pair(q, &key, &rec)) return KV_E_INVALID;
+    // the element comes out of the JSON context: every number of it is float64 ('%v' 8.08e+06,
+    // %T float64)
+    JDoc doc;
+    parse_json(element_json, len, NUM_FLOAT, &doc);
+    const std::string m = error_message(q.ps(), q.r->batch_of(*q.part), kv_result::decode(rec), doc);
+    if (m.empty()) return KV_E_INVALID;
+    return put_message(m, buf, cap);
   });
 }
 
@@ -587,10 +651,19 @@ int kv_rule_foreach_set(const kv_policyset* ps, uint32_t rule, uint32_t* set) {
   return 0;
 }
 
+int kv_rule_foreach_pattern(const kv_policyset* ps, uint32_t rule, uint32_t* on) {
+  if (!ps || !on) return KV_E_INVALID;
+  if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
+  const uint32_t fs = ps->ps.rhost[rule].foreach_set;
+  *on = fs && ps->ps.fsets[fs - 1].pattern ? 1u : 0u;
+  return 0;
+}
+
 int kv_batch_foreach_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint8_t* status, uint32_t* elem,
                           uint64_t n) {
   if (!ps || !b || !status) return KV_E_INVALID;
   if (set >= ps->ps.fsets.size() || n != b->b.res.size()) return KV_E_RANGE;
+  if (ps->ps.fsets[set].pattern) return KV_E_INVALID;  // (a pattern set has no host evaluator)
   return guarded(KV_E_INVALID, nullptr, [&]() -> int {
     FeHost h;
     build_foreach(ps->ps, b->b, &h);

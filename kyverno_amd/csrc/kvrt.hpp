@@ -171,6 +171,11 @@ struct ResultPart {
   HostArray<uint8_t> sflag, spack;
   std::vector<uint64_t> sbase;
   uint64_t nwg = 0;
+  // Pattern sets of foreach rules (KV_COMPILE_FOREACH_PATTERN; fetched with the statuses), in
+  // store order: [pattern set][n] the reduction key (kvforeach.h: the deciding element and its
+  // code) and the deciding element's 8-byte record
+  HostArray<uint32_t> fe_key;
+  HostArray<ErrRec8> fe_rec;
   // statuses [lo, lo + n) of rule `rule` from the transfer form into dst[0, n)
   void unpack_row(uint32_t rule, uint8_t* dst) const;
   uint64_t n_rec() const { return base.empty() ? 0 : base.back(); }

@@ -340,6 +340,14 @@ bool list_query_in_scope(const std::string& q) {
   return parse_query(q, &steps);
 }
 
+bool list_query_steps(const std::string& q, std::vector<ListStep>* out) {
+  std::vector<QStep> steps;
+  if (!parse_query(q, &steps)) return false;
+  out->clear();
+  for (const QStep& s : steps) out->push_back(ListStep{s.index, s.key, s.idx});
+  return true;
+}
+
 namespace {
 bool has_null(const JDoc& d, uint32_t node) {
   const JNode& n = d.at(node);

@@ -191,6 +191,38 @@ def c2_foreach_policies() -> list[dict]:
     return pols
 
 
+# The eight blocks of C2_FOREACH_SETS restated as patterns on the element (a deny block holds where
+# the pattern fails): string globs, `|` / `&` alternatives, a condition anchor; the block that
+# mixes both roots keeps its element half.
+C2_FOREACH_PATTERNS = [
+    {"image": "!*:latest"},
+    {"name": "c0"},
+    {"name": "!c2 & !c3", "image": "!docker.io/*"},
+    {"name": "c0 | c1"},
+    {"(name)": "!c1", "image": "!*e*"},
+    {"imagePullPolicy": "Always"},
+    {"name": "!c3 & ?*"},
+    {"name": "!c1"},
+]
+
+
+def c2_foreach_pattern_policies() -> list[dict]:
+    """The pattern twin of ``c2_foreach_policies``: the same 100 single-entry ``validate.foreach``
+    rules over ``request.object.spec.containers`` with each deny block restated as a ``pattern`` on
+    ``image`` / ``name`` / ``imagePullPolicy`` (rule i: pattern i mod 8), to be compiled with
+    ``PolicySet(..., foreach=True, foreach_pattern=True)``: the workload of the pattern sets'
+    measurement (DESIGN.md §3 *Foreach*)."""
+    import copy
+
+    pols = c2_policies()
+    for i, r in enumerate(pols[0]["spec"]["rules"]):
+        r["validate"] = {"message": r["validate"].get("message", ""),
+                         "foreach": [{"list": "request.object.spec.containers",
+                                      "pattern": copy.deepcopy(C2_FOREACH_PATTERNS[i % len(C2_FOREACH_PATTERNS)])}]}
+    pols[0]["metadata"]["name"] = "c2-pod-rules-foreach-pattern"
+    return pols
+
+
 C3_KIND_MIX = 2  # kv_synth stream of C3: Pods/Deployments/Services 60/25/15 over 1 000 namespaces
 C3_NAMESPACES = 1000
 

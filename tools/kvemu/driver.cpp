@@ -28,6 +28,8 @@
 #include "../../kyverno_amd/csrc/kvinternal.hpp"
 #include "../../kyverno_amd/csrc/kvjit.hpp"
 #include "../../kyverno_amd/csrc/kvcond.h"
+#include "../../kyverno_amd/csrc/kvblocks.h"
+#include "../../kyverno_amd/csrc/kvforeach.h"
 
 using namespace kv;
 using namespace kvh;
@@ -46,6 +48,9 @@ std::vector<uint32_t> kvemu_pcol(const DevBatch* B, const std::vector<ColDesc>& 
                                  std::vector<uint32_t>* erow);
 typedef void (*ptab_fn)(const DevPS*, const Val*, const uint8_t*, uint32_t, uint32_t*);
 extern "C" void kvemu_mfac(const DevPS* P, const DevBatch* B, uint32_t* mtup);
+// the pattern sets' rows of the foreach plane (fepat.cpp: kvwalk.h as a one-lane wave)
+extern "C" void kvemu_foreach_pat(const FeTables* T, const FePatTables* Q, const DevPS* P, const DevBatch* B,
+                                  uint32_t n_res, uint8_t* fe_st);
 typedef void (*chunk_fn)(const DevPS*, const DevBatch*, const Node*, const Val*, const uint8_t*, DevOut, uint32_t);
 
 static std::string slurp(const char* p) {
@@ -96,7 +101,8 @@ int main(int argc, char** argv) {
     const std::string pol = slurp(argv[1]), res = slurp(argv[2]);
     std::string ctx = strcmp(argv[3], "-") ? slurp(argv[3]) : std::string();
     PolicySet ps;
-    // KVEMU_COMPILE_FLAGS: kv_compile's flags (2: KV_COMPILE_DENY, 4: KV_COMPILE_FOREACH), as the binary's source was generated
+    // KVEMU_COMPILE_FLAGS: kv_compile's flags (2: KV_COMPILE_DENY, 4: KV_COMPILE_FOREACH, 8:
+    // KV_COMPILE_FOREACH_PATTERN), as the binary's source was generated
     compile_policies(pol.data(), pol.size(), &ps, getenv("KVEMU_COMPILE_FLAGS") ? (uint32_t)atoi(getenv("KVEMU_COMPILE_FLAGS")) : 0u);
     Batch whole;
     ingest_resources(ps, res.data(), res.size(), nullptr, &whole);
@@ -244,8 +250,13 @@ int main(int argc, char** argv) {
       for (size_t s = 0; s < n_dn; s++)
         for (uint32_t r = 0; r < B.n_res; r++) deny_st[s * B.n_res + r] = deny_status_host(dn, (uint32_t)s, B.n_res, r);
       for (size_t s = 0; s < n_fe; s++)
-        for (uint32_t r = 0; r < B.n_res; r++)
+        for (uint32_t r = 0; r < B.n_res && !ps.fsets[s].pattern; r++)
           deny_st[(n_dn + s) * B.n_res + r] = foreach_fold_host(fe, (uint32_t)s, B.n_res, r, nullptr);
+      if (!ps.fpats.empty()) {  // (as launch_foreach: the pattern sets' elements through the pattern walk)
+        const FeTables ft = fe.view();
+        const FePatTables qt = fe.pat_view();
+        kvemu_foreach_pat(&ft, &qt, &P, &B, B.n_res, deny_st.data() + n_dn * B.n_res);
+      }
       B.deny_st = deny_st.data();
     }
     // path columns of the image (as dev_batch: built once per batch)
