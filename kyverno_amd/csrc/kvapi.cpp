@@ -205,8 +205,9 @@ DevPolicySet& dev_ps(kv_policyset* s, int device) {
 
 // Path columns of the batch for the policy set's specialized kernels (kvcol.h, kvdevtypes.h):
 // the rows of family 0, one per wave group (wave groups padded to whole workgroups, so every lane
-// of the rule kernels' grid has its cells), then each family's element rows; built once per
-// batch and device from the node rows (d->view_dev must hold the batch view).
+// of the rule kernels' grid has its cells), then each family's element rows (a nested family's:
+// one run of rows per row of its parent); built once per batch and device from the node rows
+// (d->view_dev must hold the batch view).
 void build_pcol(const JitImage& J, const Batch& b, DevBatchRes* d, int device) {
   const auto t0 = std::chrono::steady_clock::now();
   const uint32_t nf = (uint32_t)J.fam_ncols.size(), j0 = J.fam_ncols.at(0);
@@ -218,8 +219,11 @@ void build_pcol(const JitImage& J, const Batch& b, DevBatchRes* d, int device) {
   HIPCHK(hipMemset(d->perow.p, 0, d->perow.n));
   std::vector<ColFam> fams(nf);
   uint32_t n_wide = 0, n_narrow = 0;
+  bool nested = false;
   for (uint32_t f = 0; f < nf; f++) {
     fams[f].arr_col = J.fam_arr[f];
+    fams[f].parent = J.fam_parent.at(f);
+    nested = nested || fams[f].parent != 0;
     fams[f].ncols = J.fam_ncols[f];
     fams[f].nw = J.fam_nw.at(f);
     fams[f].nb = J.fam_nb.at(f);
@@ -236,7 +240,8 @@ void build_pcol(const JitImage& J, const Batch& b, DevBatchRes* d, int device) {
   const ColDesc* cd = (const ColDesc*)d->pcold.p;
   std::vector<uint32_t> erow;
   if (nf > 1) {
-    HIPCHK(launch_pcol_rows(Bd, cd, (const ColFam*)d->pfam.p, nf, groups, nullptr));
+    // (the rows of every family, nested ones included, come back in this one copy)
+    HIPCHK(launch_pcol_rows(Bd, cd, (const ColFam*)d->pfam.p, nf, nested, groups, nullptr));
     erow.resize((size_t)(nf - 1) * (groups + 1));
     HIPCHK(hipMemcpy(erow.data(), d->perow.p, erow.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
@@ -255,9 +260,10 @@ void build_pcol(const JitImage& J, const Batch& b, DevBatchRes* d, int device) {
   uint32_t* pool = (uint32_t*)d->pcol.p;
   // element rows past a lane's own elements stay zero
   if (words > root_words) HIPCHK(hipMemset(pool + root_words, 0, (words - root_words) * sizeof(uint32_t)));
-  HIPCHK(launch_pcol_build(Bd, cd, (const ColFam*)d->pfam.p, 0, j0, groups, false, pool, nullptr));
-  HIPCHK(launch_pcol_build(Bd, cd, (const ColFam*)d->pfam.p, j0, (uint32_t)J.cols.size() - j0, groups, true, pool,
-                           nullptr));
+  HIPCHK(launch_pcol_build(Bd, cd, (const ColFam*)d->pfam.p, 0, j0, groups, 0u, pool, nullptr));
+  for (uint32_t level = 1; level <= (nested ? 2u : 1u); level++)
+    HIPCHK(launch_pcol_build(Bd, cd, (const ColFam*)d->pfam.p, j0, (uint32_t)J.cols.size() - j0, groups, level, pool,
+                             nullptr));
   HIPCHK(hipStreamSynchronize(nullptr));
   d->view.pcol = pool;
   d->pcol_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

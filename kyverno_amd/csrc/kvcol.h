@@ -85,11 +85,40 @@ KV_FN Node col_get(const uint32_t* __restrict__ pool, uint64_t row, const ColFam
   return Node{w[0], w[1], pool[row + (size_t)(3u * F.nw + d.bpos) * KV_LANES + lane], w[2]};
 }
 
-// element rows lane r needs in family f (its array's element count; 0 without an array)
+// lane r's cell of the root-path array that family F (not a nested one) belongs to, from the
+// built rows of family 0: a wide cell with its b, c = the word offset of the lane's element rows
+KV_FN Node col_root_arr(const uint32_t* __restrict__ pool, const ColDesc* cols, const ColFam* fams, const ColFam& F,
+                        uint32_t r) {
+  return col_get(pool, (uint64_t)(r >> 6) * col_row_words(fams[0]), fams[0], cols[F.arr_col], r & (KV_LANES - 1));
+}
+KV_FN bool col_is_arr(const Node& a) { return a.kt != 0u && node_type(a.kt) == NT_ARR; }
+
+// element rows lane r needs in family f, not a nested one (its array's element count; 0 without
+// an array)
 KV_FN uint32_t col_rows(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t f, uint32_t r) {
   if (r >= B.n_res) return 0u;
   uint32_t idx;
   const Node n = col_walk(B.nodes, ni(B.res[r].root), cols[fams[f].arr_col], &idx);
+  return idx != ABSENT && node_type(n.kt) == NT_ARR ? n.b : 0u;
+}
+
+// Rows of a nested family f, from the node rows: col_nested_parent is lane r's array of f's
+// parent family (its node; all zero without one), col_rows_nested the rows the lane needs below
+// element i of that array (the nested array's element count; 0 without that element or without
+// an array in it). The rows of parent row (wave group, i) are the most any of the group's lanes
+// needs.
+KV_FN Node col_nested_parent(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t f, uint32_t r) {
+  const Node z{0u, 0u, 0u, 0u};
+  if (r >= B.n_res) return z;
+  uint32_t idx;
+  const Node a = col_walk(B.nodes, ni(B.res[r].root), cols[fams[fams[f].parent].arr_col], &idx);
+  return idx != ABSENT && node_type(a.kt) == NT_ARR ? a : z;
+}
+KV_FN uint32_t col_rows_nested(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t f, const Node& a,
+                               uint32_t i) {
+  if (i >= a.b) return 0u;
+  uint32_t idx;
+  const Node n = col_walk(B.nodes, ni(a.a + i), cols[fams[f].arr_col], &idx);
   return idx != ABSENT && node_type(n.kt) == NT_ARR ? n.b : 0u;
 }
 
@@ -111,18 +140,55 @@ KV_FN void col_build_root(const DevBatch& B, const ColDesc* cols, const ColFam* 
   col_put(pool, (uint64_t)(r >> 6) * col_row_words(fams[0]), fams[0], d, r & (KV_LANES - 1), cell, idx);
 }
 
-// cells of element column `c` (family f > 0) for every element of lane r's family array (whose
-// cell, a wide one with its b, must be built)
-KV_FN void col_build_elem(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t c, uint32_t r,
-                          uint32_t* __restrict__ pool) {
+// cell of element column `c` (of a family of a root-path array, whose cell must be built) for
+// element i of lane r's array, if it has one; arr_c: for a column that holds a nested family's
+// array, the word offset of the nested rows of this parent row (col_nested_off). Returns the
+// element count of an array at the cell (0: none): the rows this lane needs in that nested family.
+KV_FN uint32_t col_build_elem_at(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t c, uint32_t r, uint32_t i,
+                             uint32_t arr_c, uint32_t* __restrict__ pool) {
   const ColDesc& d = cols[c];
   const ColFam& F = fams[d.fam];
+  const Node a = col_root_arr(pool, cols, fams, F, r);
+  if (!col_is_arr(a) || i >= a.b) return 0u;
+  uint32_t idx;
+  const Node n = col_walk(B.nodes, ni(a.a + i), d, &idx);
+  col_put(pool, (uint64_t)a.c + (uint64_t)i * col_row_words(F), F, d, r & (KV_LANES - 1), col_cell(n, idx, arr_c), idx);
+  return idx != ABSENT && node_type(n.kt) == NT_ARR ? n.b : 0u;
+}
+// elements lane r has in the array of the family of element column c (built, as above)
+KV_FN uint32_t col_elems(const ColDesc* cols, const ColFam* fams, uint32_t c, uint32_t r, const uint32_t* __restrict__ pool) {
+  const Node a = col_root_arr(pool, cols, fams, fams[cols[c].fam], r);
+  return col_is_arr(a) ? a.b : 0u;
+}
+// word offset of the rows of nested family N that follow `run` rows of wave group g
+KV_FN uint32_t col_nested_off(const ColFam& N, uint32_t g, uint32_t run) {
+  return (uint32_t)(col_fam_off(N) + (uint64_t)(N.erow[g] + run) * col_row_words(N));
+}
+
+// cells of element column `c` (as col_build_elem_at; not a nested family's array) for every
+// element of lane r's family array
+KV_FN void col_build_elem(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t c, uint32_t r,
+                          uint32_t* __restrict__ pool) {
+  for (uint32_t i = 0, n = col_elems(cols, fams, c, r, pool); i < n; i++) col_build_elem_at(B, cols, fams, c, r, i, 0u, pool);
+}
+
+// cells of column `c` of a nested family for every element of every nested array of lane r (the
+// parent family's cells of the nested array, wide ones with their b, must be built)
+KV_FN void col_build_nested(const DevBatch& B, const ColDesc* cols, const ColFam* fams, uint32_t c, uint32_t r,
+                            uint32_t* __restrict__ pool) {
+  const ColDesc& d = cols[c];
+  const ColFam& F = fams[d.fam];
+  const ColFam& P = fams[F.parent];
   const uint32_t lane = r & (KV_LANES - 1);
-  const Node a = col_get(pool, (uint64_t)(r >> 6) * col_row_words(fams[0]), fams[0], cols[F.arr_col], lane);
-  if (node_type(a.kt) != NT_ARR || a.kt == 0u) return;
+  const Node a = col_root_arr(pool, cols, fams, P, r);
+  if (!col_is_arr(a)) return;
   for (uint32_t i = 0; i < a.b; i++) {
-    uint32_t idx;
-    const Node n = col_walk(B.nodes, ni(a.a + i), d, &idx);
-    col_put(pool, (uint64_t)a.c + (uint64_t)i * col_row_words(F), F, d, lane, col_cell(n, idx, 0u), idx);
+    const Node e = col_get(pool, (uint64_t)a.c + (uint64_t)i * col_row_words(P), P, cols[F.arr_col], lane);
+    if (!col_is_arr(e)) continue;
+    for (uint32_t k = 0; k < e.b; k++) {
+      uint32_t idx;
+      const Node n = col_walk(B.nodes, ni(e.a + k), d, &idx);
+      col_put(pool, (uint64_t)e.c + (uint64_t)k * col_row_words(F), F, d, lane, col_cell(n, idx, 0u), idx);
+    }
   }
 }

@@ -100,12 +100,14 @@ hipError_t launch_expand_rows(const uint64_t* tcells, const uint64_t* rmask, con
 
 // Path columns of a batch (kvcol.h, kvdevtypes.h ColDesc / ColFam; n_groups: 64-lane wave
 // groups, a multiple of 4). rows: for every family f > 0 the element rows of each wave group
-// (the most any of its lanes needs) into fams[f].erow, then their exclusive prefix (the
-// family's total at erow[n_groups]). build: the cells of columns [c0, c0 + n) of every lane
-// into the pool (family-0 columns first; element columns read their family arrays' cells).
-hipError_t launch_pcol_rows(const DevBatch* B, const ColDesc* cols, const ColFam* fams, uint32_t n_fam,
+// (the families of root-path arrays, then, with `nested`, the nested families from their
+// parents' counts) into fams[f].erow, then their exclusive prefix (the family's total at
+// erow[n_groups]). build: the cells of those of the columns [c0, c0 + n) that belong to `level`
+// for every lane into the pool, the levels in order: 0 family-0 columns, 1 element columns of
+// the families of root-path arrays, 2 columns of the nested families.
+hipError_t launch_pcol_rows(const DevBatch* B, const ColDesc* cols, const ColFam* fams, uint32_t n_fam, bool nested,
                             uint32_t n_groups, hipStream_t stream);
 hipError_t launch_pcol_build(const DevBatch* B, const ColDesc* cols, const ColFam* fams, uint32_t c0, uint32_t n,
-                             uint32_t n_groups, bool elem, uint32_t* pool, hipStream_t stream);
+                             uint32_t n_groups, uint32_t level, uint32_t* pool, hipStream_t stream);
 
 }  // namespace kv

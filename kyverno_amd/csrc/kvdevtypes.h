@@ -163,6 +163,12 @@ struct DevBatch {
 // node's c otherwise (absent: all zero), and its b in a plane of its own when a consumer reads
 // it. A row of a family with nw wide columns, nb of them with a b plane, and nn narrow ones:
 //   [wide (kt, a, c) x nw x 64 lanes][b x nb x 64][narrow x nn x 64]     (32-bit words)
+// A family may be *nested*: its array is a column of another element family (its parent, itself
+// a family of a root-path array), and it holds one row per element of that array, the rows of
+// one parent row (one wave group's element j) together: as many as the longest such array among
+// the row's 64 lanes. The parent's array cell carries their word offset in `c`, the same for
+// every lane of the row, so the nested cells load coalesced as the element cells do. Two levels
+// only: a nested family has no nested family of its own.
 // Built once per batch and device (kvcol.h, kv_pcol_* in kvkernel.hip).
 constexpr uint32_t KV_COL_MAXD = 12;            // steps of a column path
 constexpr uint32_t KV_COL_SCAN = 0x80000000u;   // step: key id of a keep-all map (else a slot)
@@ -173,18 +179,20 @@ struct ColDesc {
   uint32_t fam;      // 0: a root path, f > 0: a path relative to the elements of family f
   uint32_t j;        // column within its family (order of first use)
   uint32_t nsteps;   // path length
-  uint32_t arr_fam;  // family columns 0: the family whose array this column holds (0: none)
+  uint32_t arr_fam;  // the family whose array this column holds (0: none)
   uint32_t fmt;      // ColFmt
   uint32_t pos;      // position among the family's wide (or narrow) columns
   uint32_t bpos;     // KV_COLF_WIDEB: position in the b plane
   uint32_t steps[KV_COL_MAXD];
 };
-// per family: its array's column in family 0 (family 0: unused), its columns by format; set per
-// batch: the first word of its element rows in the pool, and (device pointer) the exclusive
-// prefix of element rows per wave group (n_groups + 1 entries: the last one is the family's row
-// count)
+// per family: its array's column (an index into the plan's columns: a column of family 0, or of
+// the parent family of a nested one; family 0: unused), its parent family (0: the array is a
+// root path), its columns by format; set per batch: the first word of its element rows in the
+// pool, and (device pointer) the exclusive prefix of element rows per wave group (n_groups + 1
+// entries: the last one is the family's row count)
 struct ColFam {
   uint32_t arr_col, ncols;
+  uint32_t parent;
   uint32_t nw, nb, nn;
   uint32_t off_lo, off_hi;
   uint32_t* erow;

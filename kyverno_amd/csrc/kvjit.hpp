@@ -33,6 +33,10 @@ struct JitKernelPlan {
   // it for the kernels that meet their register rules with it at the plan they settle on in
   // first-use order (kvjitbuild.cpp jit_group_regions)
   bool grouped = false;
+  // its per-rule and nested array loops over path columns (kvjitgen.cpp ColLoop) instead of walking
+  // the node rows: a hoist region more per loop. Asked for and kept as `grouped` is, and given up
+  // before it (jit_group_regions)
+  bool colloops = false;
 };
 
 struct JitImage {
@@ -61,9 +65,10 @@ struct JitImage {
   std::vector<uint32_t> gs_desc, gs_mem;
   uint32_t gs_members = 0;
   // path columns the kernels read (kvdevtypes.h ColDesc, built per batch by kvcol.h): every
-  // column; per family its array's column in family 0 and its column count
+  // column; per family its array's column (an index into cols: of family 0, or of the parent
+  // family of a nested one), its parent family (0: none) and its column count
   std::vector<kv::ColDesc> cols;
-  std::vector<uint32_t> fam_arr, fam_ncols;
+  std::vector<uint32_t> fam_arr, fam_parent, fam_ncols;
   // per family its wide columns, those of them with a b plane, and its narrow columns (cell
   // formats: kvdevtypes.h ColFmt; KVGPU_JIT_NARROW=0 at generation: every column wide)
   std::vector<uint32_t> fam_nw, fam_nb, fam_nn;

@@ -322,7 +322,9 @@ bool jit_plan_spills(JitImage* img, const std::vector<RegVerdict>& verdicts) {
     changed = true;
     JitKernelPlan np = kp;
     const size_t big = (size_t)(std::max_element(np.blocks.begin(), np.blocks.end()) - np.blocks.begin());  // (the first)
-    if (kp.grouped) {  // (the plan comes first: the three-part layout goes before a block or a wave does)
+    if (kp.colloops) {  // (the plan comes first: the column loops go, then the three-part layout, before a block or a wave does)
+      np.colloops = false;
+    } else if (kp.grouped) {
       np.grouped = false;
     } else if (v.calls && v.fits) {  // (its scratch is the call frame: it drops its bound instead of splitting blocks)
       np.waves = 0;
@@ -467,10 +469,10 @@ bool jit_load_plan(const std::string& key, JitImage* img) {
   std::vector<JitKernelPlan> plan;
   std::istringstream in(std::string(text.begin(), text.end()));
   for (std::string line; std::getline(in, line);) {
-    if (line.rfind("kernel ", 0) != 0) continue;  // kernel <first> <count> <waves> <grouped> <block sizes...>
+    if (line.rfind("kernel ", 0) != 0) continue;  // kernel <first> <count> <waves> <grouped> <colloops> <block sizes...>
     std::istringstream ls(line.substr(7));
     JitKernelPlan kp{0, 0, 0, {}};
-    ls >> kp.first >> kp.count >> kp.waves >> kp.grouped;
+    ls >> kp.first >> kp.count >> kp.waves >> kp.grouped >> kp.colloops;
     uint32_t sum = 0;
     for (uint32_t b; ls >> b; sum += b) kp.blocks.push_back(b);
     if (sum != kp.count || kp.blocks.empty()) return false;
@@ -487,7 +489,7 @@ void jit_save_plan(const std::string& key, const JitImage& img) {
   std::string t;
   for (const JitKernelPlan& kp : img.plan) {
     t += "kernel " + std::to_string(kp.first) + " " + std::to_string(kp.count) + " " + std::to_string(kp.waves) + " " +
-         (kp.grouped ? "1" : "0");
+         (kp.grouped ? "1" : "0") + " " + (kp.colloops ? "1" : "0");
     for (uint32_t b : kp.blocks) t += " " + std::to_string(b);
     t += "\n";
   }
@@ -504,26 +506,34 @@ void jit_save_plan(const std::string& key, const JitImage& img) {
 }
 
 // The layout of every kernel's hoist regions, over the settled plan: all of them in three parts
-// (JitKernelPlan::grouped), compiled once; a kernel that no longer meets its register rules that
-// way (the loads grouped at the top of a region are in flight together) goes back to first-use
-// order, in which it settled, instead of giving up blocks or waves for the layout.
+// (JitKernelPlan::grouped) and every per-rule array loop over path columns (JitKernelPlan::
+// colloops: a hoist region more per loop), compiled once; a kernel that no longer meets its
+// register rules that way (the loads grouped at the top of a region are in flight together)
+// steps down, instead of giving up blocks or waves: three parts with its loops walking the node
+// rows, then first-use order with column loops, then first-use order with the walk, in which
+// it settled.
 static void jit_group_regions(const PolicySet& ps, uint32_t chunk, JitImage* img) {
-  for (JitKernelPlan& kp : img->plan) kp.grouped = true;
-  jit_generate(ps, chunk, img);
-  jit_compile(img);
-  bool back = false;
-  for (size_t k = 0; k < img->plan.size(); k++) {
-    RegVerdict v;
-    if (!reg_verdict(*img, program_of(*img, img->chunks[k].name), img->plan[k].waves, &v))
-      throw std::runtime_error("kvjit: no kernel descriptor for " + img->chunks[k].name);
-    if (!v.ships()) {
-      img->plan[k].grouped = false;
-      back = true;
+  static const bool kSteps[4][2] = {{true, true}, {true, false}, {false, true}, {false, false}};  // (grouped, colloops)
+  std::vector<int> step(img->plan.size(), 0);
+  for (int round = 0; round < 4; round++) {
+    for (size_t k = 0; k < img->plan.size(); k++) {
+      img->plan[k].grouped = kSteps[step[k]][0];
+      img->plan[k].colloops = kSteps[step[k]][1];
     }
+    jit_generate(ps, chunk, img);
+    jit_compile(img);  // (the kernels that did not change: from the cache)
+    bool back = false;
+    for (size_t k = 0; k < img->plan.size(); k++) {
+      RegVerdict v;
+      if (!reg_verdict(*img, program_of(*img, img->chunks[k].name), img->plan[k].waves, &v))
+        throw std::runtime_error("kvjit: no kernel descriptor for " + img->chunks[k].name);
+      if (!v.ships() && step[k] < 3) {
+        step[k]++;
+        back = true;
+      }
+    }
+    if (!back) return;
   }
-  if (!back) return;
-  jit_generate(ps, chunk, img);
-  jit_compile(img);  // (the kernels that went back: from the cache, or compiled again)
 }
 
 void jit_build(const PolicySet& ps, JitImage* img) {
@@ -537,7 +547,7 @@ void jit_build(const PolicySet& ps, JitImage* img) {
     // layout is the first thing to go; a new one is made in first-use order, then given its layouts)
     const bool stored = jit_load_plan(pkey, img);
     if (!stored) {
-      for (JitKernelPlan& kp : img->plan) kp.grouped = false;
+      for (JitKernelPlan& kp : img->plan) kp.grouped = kp.colloops = false;
       jit_refine_blocks(ps, chunk, img);  // block sizes from probe compiles
     }
     jit_generate(ps, chunk, img);

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <list>
 #include <map>
 #include <set>
 #include <sstream>
@@ -64,18 +65,21 @@ constexpr uint32_t kGslotMembers = 22u;
 // The generator's tuning environment, read once per jit_generate. Every one of these is part of
 // the program text and so of the cache keys (code objects and plan):
 //   KVGPU_JIT_NARROW=0   every path column wide (A/B runs; col_plan)
+//   KVGPU_JIT_COLLOOPS=0 per-rule and nested array loops walk the node rows (A/B runs; emit_region)
 //   KVGPU_JIT_STAMPS     the rule kernels stamp their segment boundaries (group_kernel, kJitStamps)
 //   KVGPU_JIT_WAVES      first launch bound in waves per SIMD (default: at most 8, 0: none)
 //   KVGPU_JIT_BLOCK_W    weight budget of the first block sizes (initial_blocks; default 160 / 240)
 //   KVGPU_JIT_DIAG=A,B   diagnostics-only kernels (#define KV_DIAG_A ... ahead of the prelude; wrong results)
 struct GenOpts {
-  bool narrow, stamps, has_waves;
+  bool narrow, colloops, stamps, has_waves;
   int waves;
   uint32_t block_w;  // 0: the defaults
   std::string diag;  // the #define lines
   GenOpts() {
     const char* e = getenv("KVGPU_JIT_NARROW");
     narrow = !(e && e[0] == '0');
+    e = getenv("KVGPU_JIT_COLLOOPS");
+    colloops = !(e && e[0] == '0');
     stamps = getenv("KVGPU_JIT_STAMPS") != nullptr;
     e = getenv("KVGPU_JIT_WAVES");
     has_waves = e != nullptr;
@@ -90,7 +94,8 @@ struct GenOpts {
 
 struct Gen {
   struct Fam {
-    std::string arr;                          // family array expr (family 0: "")
+    std::string arr;                          // family array expr (family 0: ""; nested: "<parent's>[]<relative>")
+    uint32_t parent = 0, arr_j = 0;           // the family and column that hold its array
     std::map<std::string, uint32_t> idx;      // relative expr -> column
     std::vector<std::vector<uint32_t>> steps; // per column: its path steps
     std::vector<uint32_t> use;                // per column: what the kernels read of it (ColUse)
@@ -153,6 +158,7 @@ struct Gen {
     uint32_t gs0 = 0, gsn = 0;  // site-record groups: the kernel's first (of the image) and its count
     std::string decls;          // declarations its blocks need ahead of the kernel (member tables)
     bool grouped = false;       // hoist regions in three parts (JitKernelPlan::grouped)
+    bool colloops = false;      // per-rule array loops over path columns (JitKernelPlan::colloops)
   };
 
   explicit Gen(const PolicySet& p) : ps(p), rec_slot(p.rules.size(), 0) {
@@ -174,7 +180,8 @@ struct Gen {
   // (kvdevtypes.h, built per batch by kvcol.h) instead of walking the node rows from the root
   // or the loop element: one independent coalesced load per lookup instead of a chain of
   // dependent ones. Family 0 holds root paths; family f > 0 the paths relative to the elements
-  // of one array path (a column of family 0). Columns are numbered in order of first use; the
+  // of one array path (a column of family 0), or of one array path relative to the elements of
+  // such a family (a nested family: kvdevtypes.h). Columns are numbered in order of first use; the
   // kernels read column j of family f through macros (KVC_LD_<f>_<j> and its kin, col_plan)
   // defined at the head of every kernel program once the whole image is generated and the
   // cell format of every column is known.
@@ -221,18 +228,26 @@ struct Gen {
     F.use.push_back(0u);
     return j;
   }
-  // family of the elements of array expr `arr` (a root path); its column 0 is the element itself
-  uint32_t family(const std::string& arr) {
+  // family of the elements of the array at `rel` in family `parent` (0: a root path; f > 0: a
+  // path relative to the elements of f, itself a family of a root path: two levels only); its
+  // column 0 is the element itself
+  uint32_t family(uint32_t parent, const std::string& rel) {
+    if (parent && fams.at(parent).parent) return kNoCol;
+    const std::string arr = parent ? fams[parent].arr + "[]" + rel : rel;
     auto it = fam_of.find(arr);
     if (it != fam_of.end()) return it->second;
-    if (col_of(0, arr) == kNoCol) return kNoCol;
+    const uint32_t j = col_of(parent, rel);
+    if (j == kNoCol) return kNoCol;
     const uint32_t f = (uint32_t)fams.size();
     fams.emplace_back();
     fams.back().arr = arr;
+    fams.back().parent = parent;
+    fams.back().arr_j = j;
     col_of(f, "");
     fam_of.emplace(arr, f);
     return f;
   }
+  uint32_t family(const std::string& arr) { return family(0, arr); }
   // the plan (JitImage::cols / fam_*) and the macro block of the kernel programs: per family
   // the words of a row (KVC_W<f>), per column its load from the row at word `b` (KVC_LD), the
   // node index of a map cell (KVC_IX) and the table word of a leaf on it: whole, array case
@@ -241,6 +256,7 @@ struct Gen {
   void col_plan(JitImage* out, std::string* defs) const {
     out->cols.clear();
     out->fam_arr.clear();
+    out->fam_parent.clear();
     out->fam_ncols.clear();
     out->fam_nw.clear();
     out->fam_nb.clear();
@@ -251,9 +267,14 @@ struct Gen {
     d << "#define KVC_LO_ROW(n, w) kv_leaf_word(P, N, n, w)\n"
       << "#define KVC_LW_ROW(n, w) kv_leaf_gather(P, n, w)\n"
       << "#define KVC_LA_ROW(n, w) kv_leaf_fix(P.ptab, P.n_vals, N, (n).a, (n).b, false, w)\n";
+    std::vector<uint32_t> col0(fams.size(), 0u);  // first column of each family in out->cols
+    for (uint32_t f = 1; f < fams.size(); f++) col0[f] = col0[f - 1] + (uint32_t)fams[f - 1].steps.size();
+    std::set<std::pair<uint32_t, uint32_t>> arrs;  // the family arrays: (family, column)
+    for (uint32_t f = 1; f < fams.size(); f++) arrs.insert({fams[f].parent, fams[f].arr_j});
     for (uint32_t f = 0; f < fams.size(); f++) {
       const Fam& F = fams[f];
-      out->fam_arr.push_back(f ? fams[0].idx.at(F.arr) : 0u);  // (family 0 columns come first)
+      out->fam_arr.push_back(f ? col0[F.parent] + F.arr_j : 0u);
+      out->fam_parent.push_back(F.parent);
       out->fam_ncols.push_back((uint32_t)F.steps.size());
       std::vector<uint32_t> use(F.steps.size(), 0u);
       for (const auto& kv : F.idx) {
@@ -261,7 +282,7 @@ struct Gen {
         uint32_t u = F.use[kv.second];
         auto it = use_seed.find(key);
         if (it != use_seed.end()) u |= it->second;
-        if (f == 0 && fam_of.count(kv.first)) u |= CU_WIDE | CU_B;  // a family array: a, b, c
+        if (arrs.count({f, kv.second})) u |= CU_WIDE | CU_B;  // a family array: a, b, c
         use[kv.second] = u;
         out->col_use[key] = u;
       }
@@ -1035,11 +1056,25 @@ struct Gen {
     // of its exprs (an element family) and the word offset of its lane's row in the pool
     int fam = -1;
     std::string troot, cell0;
+    // an empty asm statement with the words `xs` as inputs: their loads are issued, together, ahead of it
+    static std::string joined(const std::vector<std::string>& xs) {
+      std::string s;
+      for (size_t i = 0; i < xs.size(); i += 8) {  // (a few inputs per statement)
+        s += "#ifndef KVEMU\n  asm volatile(\"\" ::";
+        for (size_t k = i; k < xs.size() && k < i + 8; k++) s += (k > i ? ", \"v\"(" : " \"v\"(") + xs[k] + ")";
+        s += ");\n#endif\n";
+      }
+      return s;
+    }
     // What was hoisted since the last flush. grouped: in three parts, the cell loads, the gathers
     // of the leaf words (kv_leaf_gather: no branch, so they issue behind the cell loads' one wait),
     // and the fix-up of the words whose cell is an array (kv_leaf_fix), under one wave-uniform
     // test. Otherwise in first-use order, each word whole (kv_leaf_word: its array case inline).
-    std::string flush(bool grouped) {
+    // join (three parts only; a column loop's region, flushed once): the words `join` and the
+    // region's cell words, then its gathered words, are `joined` behind their part, so every load
+    // of a part is issued ahead of the first branch that reads one of them (left alone the
+    // compiler sinks a cell's load below the test of the cell before it).
+    std::string flush(bool grouped, const std::vector<std::string>* join = nullptr) {
       std::string s;
       if (!grouped) {
         for (; oflushed < order.size(); oflushed++) {
@@ -1056,6 +1091,12 @@ struct Gen {
       }
       oflushed = order.size();
       for (; cflushed < cells.size(); cflushed++) s += cells[cflushed];
+      if (join) {
+        std::vector<std::string> xs = *join;
+        for (const auto& kv : vars)
+          if (kv.second.fam >= 0) xs.push_back(kv.second.node + ".kt");
+        s += joined(xs);
+      }
       if (wflushed == words.size()) return s;
       std::vector<std::string> nodes;  // the words' nodes, each once
       std::string fix;
@@ -1067,6 +1108,11 @@ struct Gen {
         if (std::find(nodes.begin(), nodes.end(), x.hv.node) == nodes.end()) nodes.push_back(x.hv.node);
         fix += "    if (node_type(" + x.hv.node + ".kt) == NT_ARR) " + x.var + " = " +
                (col ? col_macro("LA", (uint32_t)x.hv.fam, x.hv.j) : std::string("KVC_LA_ROW")) + args;
+      }
+      if (join) {
+        std::vector<std::string> xs;
+        for (size_t i = wflushed; i < words.size(); i++) xs.push_back(words[i].var);
+        s += joined(xs);
       }
       wflushed = words.size();
       s += "  if (__ballot(";
@@ -1206,8 +1252,31 @@ struct Gen {
     }
   };
 
-  void emit_region(Block& B, RGen& g, const Region& R, std::ostream& w) {
+  // A per-rule loop (an existence anchor, a loop nested in a loop element) over an array that is
+  // a path column: its elements are the rows of the array's family (a nested family when the
+  // array lies in a loop element), and the lookups and leaves below an element are a hoist region
+  // of their own at the head of the loop body, so the body is emitted once its END is reached:
+  //   { uint32_t <row offset>; <BEGIN> <body label>:; <element cell> <region> <body> <END> }
+  // The braces keep the region's declarations out of the scope of every jump past the loop.
+  struct ColLoop {
+    uint32_t body_pc = 0, end_pc = 0, fam = 0;
+    std::string troot;
+    HoistTable T;
+    std::ostringstream body;
+    std::ostream* outer = nullptr;
+  };
+
+  void emit_region(Block& B, RGen& g, const Region& R, std::ostream& w0) {
     const std::string& s = g.s;
+    std::list<ColLoop> cloops;  // the open ones, innermost last
+    std::ostream* wcur = &w0;
+    auto cloop_of = [&](const std::string& ex) -> ColLoop* {
+      for (auto it = cloops.rbegin(); it != cloops.rend(); ++it) {
+        const size_t n = it->troot.size();
+        if (ex.compare(0, n, it->troot) == 0 && (ex.size() == n || ex[n] == '/')) return &*it;
+      }
+      return nullptr;
+    };
     auto C = [&](uint32_t d) { return "c" + std::to_string(d) + s; };
     auto L = [&](uint32_t pc) { return "R" + std::to_string(g.ri) + "_L" + std::to_string(pc); };
     // err: the jump carries a pending error (a raise, or an error passed on by a scope end)
@@ -1268,7 +1337,7 @@ struct Gen {
     auto known = [&](uint32_t d) {
       if (d >= g.expr.size() || g.expr[d].empty()) return false;
       const std::string& ex = g.expr[d];
-      return ex[0] == 'R' || (R.T && ex.compare(0, R.troot.size(), R.troot) == 0);
+      return ex[0] == 'R' || (R.T && ex.compare(0, R.troot.size(), R.troot) == 0) || cloop_of(ex);
     };
     // the cursor c<d> read as a node index: the columns it may come from hold one (wide)
     auto IDX = [&](uint32_t d) {
@@ -1288,6 +1357,7 @@ struct Gen {
       const std::string& ex = g.expr[d];
       if (ex[0] == 'R') return &B.global;
       if (R.T && ex.compare(0, R.troot.size(), R.troot) == 0) return R.T;
+      if (ColLoop* cl = cloop_of(ex)) return &cl->T;
       return nullptr;
     };
     // "the node at depth d is absent or its type <cmp>": a hoisted node carries its absence as
@@ -1328,13 +1398,29 @@ struct Gen {
              s + "); " + jump(body) + " }\n";
     };
 
+    // the column loop whose END at `pc` was just emitted: its element cell, its hoist region and
+    // its body, into the stream the loop began in
+    auto close_cloop = [&](uint32_t pc, const std::string& lv) {
+      if (cloops.empty() || cloops.back().end_pc != pc) return;
+      ColLoop& cl = cloops.back();
+      const std::string& p = cl.T.prefix;
+      const std::vector<std::string> join{p + "n.kt"};
+      *cl.outer << L(cl.body_pc) << ":;\n  const uint32_t " << p << "e = " << p << "c + li" << lv << s << " * KVC_W" << cl.fam
+                << ";\n  const Node " << p << "n = " << col_macro("LD", cl.fam, 0) << "(" << p << "e);\n"
+                << cl.T.flush(B.kern.grouped, &join) << cl.body.str() << "  }\n";
+      wcur = cl.outer;
+      cloops.pop_back();
+    };
+
     for (uint32_t pc = R.rb; pc < R.re; pc++) {
       const Inst& in = ps.prog[pc];
       const uint32_t op = in.op & 0xFF, d = (in.op >> 8) & 0xFF, aux = (in.op >> 16) & 0xFF;
       const std::string cd = C(d), cn = C(d + 1);
       const uint32_t lv = aux & 3;
       const std::string L_lv = std::to_string(lv);
-      w << L(pc) << ":;\n";
+      std::ostream& w = *wcur;
+      // (the body label of a column loop goes ahead of its hoist region, below)
+      if (cloops.empty() || cloops.back().body_pc != pc) w << L(pc) << ":;\n";
       switch (op) {
         case OP_MAPCHK:
           w << "  if (" << absent_or(d, "!= NT_MAP") << ") " << raise(E_TYPE_MAP, in.a, in.c) << "\n";
@@ -1438,6 +1524,41 @@ struct Gen {
           [[fallthrough]];  // nested loop, per rule
         case OP_EXIST_BEGIN:
           if (G && op == OP_EXIST_BEGIN) throw std::runtime_error("kvjit: EXIST in a rule group");
+          {
+            // the array is a path column (a root path, or a path in an element of a root-path
+            // array's family): its elements from the rows of its family
+            uint32_t f = kNoCol;
+            HoistTable* AT = opt.colloops && B.kern.colloops && known(d) ? table_for(d) : nullptr;
+            if (AT && AT->fam >= 0 && g.hv[d].fam == AT->fam && g.hv[d].j != kNoCol)
+              f = family((uint32_t)AT->fam, AT->fam == 0 ? g.expr[d] : g.expr[d].substr(AT->troot.size()));
+            if (f != kNoCol) {
+              const std::string an = NODE(d, CU_WIDE | CU_B);
+              set_unknown(d + 1);
+              cloops.emplace_back();
+              ColLoop& cl = cloops.back();
+              cl.body_pc = pc + 1;
+              cl.end_pc = in.a;
+              cl.fam = f;
+              cl.troot = "P" + std::to_string(pc);
+              cl.T.prefix = "p" + std::to_string(pc) + "_";
+              cl.T.fam = (int)f;
+              cl.T.troot = cl.troot;
+              cl.T.cell0 = cl.T.prefix + "e";
+              cl.outer = wcur;
+              g.expr[d + 1] = cl.troot;
+              g.hv[d + 1] = HVar{cn, cl.T.prefix + "n", (int)f, 0u};
+              // (an array's cell carries the word offset of its element rows in c; the loop runs
+              // on an array only, whatever the checks ahead of it)
+              w << "  { uint32_t " << cl.T.prefix << "c;\n  { const Node an_ = " << an << "; lf" << L_lv << s << " = an_.a; ll" << L_lv
+                << s << " = node_type(an_.kt) == NT_ARR ? an_.b : 0u; li" << L_lv << s << " = 0u; " << cl.T.prefix
+                << "c = an_.c;\n    if (ll" << L_lv << s << " == 0u) ";
+              if (op == OP_LOOP_BEGIN) w << jump(in.a + 1);
+              else w << raise(E_EXIST_FAIL, in.b, in.c);
+              w << "\n    " << cn << " = ni(an_.a); }\n";
+              wcur = &cl.body;
+              break;
+            }
+          }
           set_unknown(d + 1);
           w << "  { const Node an_ = " << NODE(d, CU_WIDE | CU_B) << "; lf" << L_lv << s << " = an_.a; ll" << L_lv << s << " = an_.b; li"
             << L_lv << s << " = 0u;\n    if (an_.b == 0u) ";
@@ -1451,12 +1572,14 @@ struct Gen {
               << jump(in.c, true) << " }\n";
           w << next_elem(L_lv, cn, in.a + 1);
           set_unknown(d + 1);
+          close_cloop(pc, L_lv);
           break;
         case OP_EXIST_END:
           if (G) throw std::runtime_error("kvjit: EXIST in a rule group");
           w << "  if (!" << kindof << ") " << jump(pc + 1) << "\n  " << ek << " = 0u;\n"
             << next_elem(L_lv, cn, in.a + 1) << "  " << raise(E_EXIST_FAIL, in.b, in.c) << "\n";
           set_unknown(d + 1);
+          close_cloop(pc, L_lv);
           break;
         case OP_ALT_BEGIN:
           if (G) throw std::runtime_error("kvjit: anyPattern in a rule group");
@@ -1484,6 +1607,7 @@ struct Gen {
           break;
       }
     }
+    if (!cloops.empty()) throw std::runtime_error("kvjit: a loop of rule " + std::to_string(g.ri) + " does not end in its region");
   }
 
   RGen analyze(uint32_t ri) {
@@ -2204,7 +2328,7 @@ struct Gen {
   // The kernel `name` of the blocks `chs` (each one's rules) at a bound of `waves` per SIMD
   // (0: none); returns its rules in LDS-row order (blocks reorder rule-group members).
   std::vector<uint32_t> group_kernel(const std::string& name, const std::vector<std::vector<uint32_t>>& chs, int waves,
-                                     bool grouped) {
+                                     bool grouped, bool colloops) {
     std::vector<std::string> blocks;
     std::vector<std::pair<uint32_t, uint32_t>> rows;  // LDS rows [first, first + count) of each block
     std::vector<uint32_t> rules;
@@ -2216,6 +2340,7 @@ struct Gen {
     kern.mt_kbase = (uint32_t)(mt_bits.size() / 32u);
     kern.gs0 = (uint32_t)(gs_desc.size() / 4u);
     kern.grouped = grouped;
+    kern.colloops = colloops;
     for (const auto& c : chs) {
       std::vector<uint32_t> ord;
       rows.push_back({(uint32_t)rules.size(), (uint32_t)c.size()});
@@ -2541,7 +2666,7 @@ std::vector<JitKernelPlan> first_plan(Gen& g, const std::vector<uint32_t>& sorte
     // workgroups of 4 waves: waves per SIMD = workgroups per CU the LDS admits
     const int lds_waves = Gen::lds_waves(e - a);
     const int rule_waves = (int)std::max<uint32_t>(1u, (160u * 1024u) / std::max<uint32_t>(1u, (e - a) * 256u));
-    plan.push_back({a, e - a, g.opt.has_waves ? g.opt.waves : std::min({8, lds_waves, rule_waves}), bl, true});
+    plan.push_back({a, e - a, g.opt.has_waves ? g.opt.waves : std::min({8, lds_waves, rule_waves}), bl, true, true});
   }
   return plan;
 }
@@ -2628,7 +2753,7 @@ void jit_generate(const PolicySet& ps, uint32_t chunk_rules, JitImage* out) {
     }
     if (at != kp.count) throw std::runtime_error("kvjit: kernel plan blocks do not cover its rules");
     // the kernel's rules in LDS-row order (blocks reorder rule-group members)
-    kc.rules = g.group_kernel(kc.name, bl, kp.waves, kp.grouped);
+    kc.rules = g.group_kernel(kc.name, bl, kp.waves, kp.grouped, kp.colloops);
     out->chunks.push_back(kc);
   }
   out->mtup_words = (uint32_t)(g.mt_bits.size() / 32u);

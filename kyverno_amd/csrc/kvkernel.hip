@@ -945,14 +945,29 @@ hipError_t launch_expand_rows(const uint64_t* tcells, const uint64_t* rmask, con
 }
 
 // ------------------------------------------------------------------ path columns (kvcol.h)
-// element rows of family f = 1 + blockIdx.y per wave group: the most any lane of the group needs
-__global__ __launch_bounds__(KV_WG) void kv_pcol_rows_kernel(const DevBatch* __restrict__ Bp,
-                                                             const ColDesc* __restrict__ cols,
-                                                             const ColFam* __restrict__ fams) {
-  const uint32_t r = blockIdx.x * KV_WG + threadIdx.x, f = 1u + blockIdx.y;
-  uint32_t v = col_rows(*Bp, cols, fams, f, r);
+__device__ __forceinline__ uint32_t kv_wave_max(uint32_t v) {
 #pragma unroll
   for (int m = 1; m < (int)KV_LANES; m <<= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m, (int)KV_LANES));
+  return v;
+}
+
+// element rows of family f = 1 + blockIdx.y per wave group (one wave per group). nested == 0,
+// the families of root-path arrays: the most any lane of the group needs. nested == 1, the
+// nested families, once their parents' counts are there (and before the scan): per parent row
+// the most any lane needs, summed over the group's parent rows.
+__global__ __launch_bounds__(KV_WG) void kv_pcol_rows_kernel(const DevBatch* __restrict__ Bp,
+                                                             const ColDesc* __restrict__ cols,
+                                                             const ColFam* __restrict__ fams, uint32_t nested) {
+  const uint32_t r = blockIdx.x * KV_WG + threadIdx.x, f = 1u + blockIdx.y;
+  if ((fams[f].parent != 0u) != (nested != 0u)) return;
+  uint32_t v = 0u;
+  if (!nested) {
+    v = kv_wave_max(col_rows(*Bp, cols, fams, f, r));
+  } else {
+    const uint32_t n = fams[fams[f].parent].erow[r >> 6];
+    const Node a = col_nested_parent(*Bp, cols, fams, f, r);
+    for (uint32_t i = 0; i < n; i++) v += kv_wave_max(col_rows_nested(*Bp, cols, fams, f, a, i));
+  }
   if ((threadIdx.x & (KV_LANES - 1)) == 0) fams[f].erow[r >> 6] = v;
 }
 
@@ -981,33 +996,54 @@ __global__ __launch_bounds__(1024) void kv_pcol_scan_kernel(const ColFam* __rest
   if (threadIdx.x == 1023u) e[n_groups] = s_sum[1023];
 }
 
-// cells of columns [c0, c0 + gridDim.y) for every lane (family-0 columns, or element columns
-// after them: their family arrays' cells must be built)
+// cells of columns [c0, c0 + gridDim.y) for every lane, those of one level per launch and the
+// levels in order: 0 the family-0 columns, 1 the element columns of the families of root-path
+// arrays (their arrays' cells must be built), 2 the columns of the nested families (their
+// arrays' cells, element cells of their parents, must be built). An element column that holds a
+// nested family's array is built by whole waves: its cell of parent row (group, i) carries the
+// offset of that row's nested rows, which follow those of the group's parent rows before it.
 __global__ __launch_bounds__(KV_WG) void kv_pcol_build_kernel(const DevBatch* __restrict__ Bp,
                                                               const ColDesc* __restrict__ cols,
                                                               const ColFam* __restrict__ fams, uint32_t c0,
-                                                              uint32_t elem, uint32_t* __restrict__ pool) {
+                                                              uint32_t level, uint32_t* __restrict__ pool) {
   const uint32_t r = blockIdx.x * KV_WG + threadIdx.x, c = c0 + blockIdx.y;
-  if (elem) col_build_elem(*Bp, cols, fams, c, r, pool);
-  else col_build_root(*Bp, cols, fams, c, r, pool);
+  const ColDesc& d = cols[c];
+  if (level == 0u) {
+    col_build_root(*Bp, cols, fams, c, r, pool);
+    return;
+  }
+  if ((fams[d.fam].parent != 0u) != (level == 2u)) return;
+  if (level == 2u) {
+    col_build_nested(*Bp, cols, fams, c, r, pool);
+  } else if (!d.arr_fam) {
+    col_build_elem(*Bp, cols, fams, c, r, pool);
+  } else {
+    const ColFam& nf = fams[d.arr_fam];
+    const uint32_t n = kv_wave_max(col_elems(cols, fams, c, r, pool));
+    for (uint32_t i = 0, run = 0; i < n; i++) {
+      run += kv_wave_max(col_build_elem_at(*Bp, cols, fams, c, r, i, col_nested_off(nf, r >> 6, run), pool));
+    }
+  }
 }
 
-hipError_t launch_pcol_rows(const DevBatch* B, const ColDesc* cols, const ColFam* fams, uint32_t n_fam,
+hipError_t launch_pcol_rows(const DevBatch* B, const ColDesc* cols, const ColFam* fams, uint32_t n_fam, bool nested,
                             uint32_t n_groups, hipStream_t stream) {
   if (n_fam < 2 || n_groups == 0) return hipSuccess;
-  hipLaunchKernelGGL(kv_pcol_rows_kernel, dim3(n_groups * KV_LANES / KV_WG, n_fam - 1), dim3(KV_WG), 0, stream, B, cols,
-                     fams);
-  if (hipError_t e = hipGetLastError()) return e;
+  for (uint32_t lv = 0; lv < (nested ? 2u : 1u); lv++) {  // parents first
+    hipLaunchKernelGGL(kv_pcol_rows_kernel, dim3(n_groups * KV_LANES / KV_WG, n_fam - 1), dim3(KV_WG), 0, stream, B, cols,
+                       fams, lv);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
   hipLaunchKernelGGL(kv_pcol_scan_kernel, dim3(n_fam - 1), dim3(1024), 0, stream, fams, n_groups);
   return hipGetLastError();
 }
 
 hipError_t launch_pcol_build(const DevBatch* B, const ColDesc* cols, const ColFam* fams, uint32_t c0, uint32_t n,
-                             uint32_t n_groups, bool elem, uint32_t* pool, hipStream_t stream) {
+                             uint32_t n_groups, uint32_t level, uint32_t* pool, hipStream_t stream) {
   if (n == 0 || n_groups == 0) return hipSuccess;
   if (n > 65535u) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kv_pcol_build_kernel, dim3(n_groups * KV_LANES / KV_WG, n), dim3(KV_WG), 0, stream, B, cols, fams,
-                     c0, elem ? 1u : 0u, pool);
+                     c0, level, pool);
   return hipGetLastError();
 }
 

@@ -18,6 +18,11 @@ mask. A hoist region (kvjitgen.cpp HoistTable::flush) has no branch before its f
 body, so the head holds the region's cell loads and word gathers: one round for the cells in
 the head, and one for the words where the first rule reads one.
 
+Single-load waits (`one`): the waits before which exactly one load was issued since the wait
+before them. A chain of them is a walk of the node rows, each load waiting for the one before
+it (a cursor's type, its map's slot, the child); the lookups of a hoist region share their
+waits instead. Per kernel (column `one`) and per loop.
+
     python tools/jit_isa.py [c2|c3|c4|c5] [--env K=V ...]
 """
 import collections
@@ -61,17 +66,18 @@ def is_wait(o, rest):
 
 
 def loop_report(dis):
-    """[(instructions, (loads, waits, rounds), the same of the head)] of the outermost large loops"""
+    """[(instructions, (loads, waits, rounds, single-load waits), the same of the head)] of the outermost
+    large loops"""
 
     def lwr(xs):
-        ld = wt = rd = 0
-        fresh = False  # a load was issued since the last wait
+        ld = wt = rd = one = 0
+        fresh = 0  # loads issued since the last wait
         for _, o, rest, _ in xs:
             if is_load(o):
-                ld, fresh = ld + 1, True
+                ld, fresh = ld + 1, fresh + 1
             elif is_wait(o, rest):
-                wt, rd, fresh = wt + 1, rd + fresh, False
-        return ld, wt, rd
+                wt, rd, one, fresh = wt + 1, rd + (fresh > 0), one + (fresh == 1), 0
+        return ld, wt, rd, one
 
     ins = [(int(a, 16), o, rest, int(t, 16) if t else None) for o, rest, a, t in INST.findall(dis)]
     if not ins:
@@ -102,7 +108,7 @@ def loop_report(dis):
 
 tot = collections.Counter()
 print(f"{'kernel':24s} {'vgpr':>4s} {'sgpr':>4s} {'spill':>5s} {'priv':>4s} {'KB':>6s} {'salu':>6s} {'exec':>6s} "
-      f"{'valu':>6s} {'lane':>5s} {'vmem':>5s} {'lds':>5s} {'ld':>5s} {'wait':>5s}")
+      f"{'valu':>6s} {'lane':>5s} {'vmem':>5s} {'lds':>5s} {'ld':>5s} {'wait':>5s} {'one':>5s}")
 for f in sorted(glob.glob(os.path.join(d, "k.*.co"))):
     label = f.split("k.", 1)[1][:-3]
     name = label.split(".m")[0]  # (output-mode variants: <name>.m<full>)
@@ -118,9 +124,15 @@ for f in sorted(glob.glob(os.path.join(d, "k.*.co"))):
     ops = re.findall(r"^\s+([sv]_[a-z0-9_]+|global_[a-z0-9_]+|ds_[a-z0-9_]+|buffer_[a-z0-9_]+|flat_[a-z0-9_]+)([^/\n]*)",
                      dis, re.M)
     c = collections.Counter()
+    fresh = 0  # loads issued since the last wait
     for o, rest in ops:
         c["ld"] += is_load(o)
         c["wait"] += is_wait(o, rest)
+        if is_load(o):
+            fresh += 1
+        elif is_wait(o, rest):
+            c["one"] += fresh == 1
+            fresh = 0
         if o in CTRL or (o.startswith("s_") and "exec" in o + rest):
             c["exec"] += 1
         elif o.startswith("s_"):
@@ -137,8 +149,8 @@ for f in sorted(glob.glob(os.path.join(d, "k.*.co"))):
     tot.update(c)
     print(f"{label[:24]:24s} {meta('vgpr_count'):4d} {meta('sgpr_count'):4d} {meta('sgpr_spill_count'):5d} "
           f"{meta('private_segment_fixed_size'):4d} {size / 1024:6.0f} {c['salu']:6d} {c['exec']:6d} {c['valu']:6d} "
-          f"{c['lane']:5d} {c['vmem']:5d} {c['lds']:5d} {c['ld']:5d} {c['wait']:5d}")
+          f"{c['lane']:5d} {c['vmem']:5d} {c['lds']:5d} {c['ld']:5d} {c['wait']:5d} {c['one']:5d}")
     for k, (n, b, h) in enumerate(loop_report(dis)):
-        print(f"  loop {k}: {n:5d} instructions, {b[0]:3d} loads {b[1]:3d} waits {b[2]:3d} rounds; "
+        print(f"  loop {k}: {n:5d} instructions, {b[0]:3d} loads {b[1]:3d} waits {b[2]:3d} rounds {b[3]:3d} single; "
               f"head: {h[0]:2d} loads {h[1]:2d} waits {h[2]:2d} rounds")
 print("total", dict(tot))

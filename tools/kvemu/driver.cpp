@@ -43,7 +43,7 @@ extern "C" void kvemu_mtab(const DevPS* P, const DevBatch* B, uint32_t words, ui
                            uint32_t* an, uint32_t* sl);
 
 std::vector<uint32_t> kvemu_pcol(const DevBatch* B, const std::vector<ColDesc>& cols, const std::vector<uint32_t>& fam_arr,
-                                 const std::vector<uint32_t>& fam_ncols, const std::vector<uint32_t>& fam_nw,
+                                 const std::vector<uint32_t>& fam_parent, const std::vector<uint32_t>& fam_ncols, const std::vector<uint32_t>& fam_nw,
                                  const std::vector<uint32_t>& fam_nb, const std::vector<uint32_t>& fam_nn,
                                  std::vector<uint32_t>* erow);
 typedef void (*ptab_fn)(const DevPS*, const Val*, const uint8_t*, uint32_t, uint32_t*);
@@ -264,7 +264,7 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> pcol;  // rows by cell format (kvcol.h col_put)
     if (!img.cols.empty() && B.n_res) {
       if (NV + KV_PTAB_PSEUDO >= (1ull << KV_COL_PAYLOAD)) throw std::runtime_error("kvemu: more than 2^28 distinct values");
-      pcol = kvemu_pcol(&B, img.cols, img.fam_arr, img.fam_ncols, img.fam_nw, img.fam_nb, img.fam_nn, &pcol_erow);
+      pcol = kvemu_pcol(&B, img.cols, img.fam_arr, img.fam_parent, img.fam_ncols, img.fam_nw, img.fam_nb, img.fam_nn, &pcol_erow);
       B.pcol = pcol.data();
     }
     // match tables (as kv_session: one allocation, three [word][entity] tables)
