@@ -1055,19 +1055,50 @@ __device__ __forceinline__ void kv_count_seg(const uint32_t* w, uint64_t m, uint
   }
 }
 
-// End of the rule kernel for this wave: its statuses of the nr rules (kernel rules
-// rules[0..nr)) go to the status matrix (KV_OFULL(O) & 1); lane q counts the wave's segment of row q
+// End of the rule kernel for this wave: its statuses of the NR rules (kernel rules
+// rules[0..NR)) go to the status matrix (KV_OFULL(O) & 1); lane q counts the wave's segment of row q
 // (every lane, and with per-scope counts, KV_OFULL(O) & 8, the lanes of the workgroup's scope wsc;
 // lanes of other scopes go straight to O.scounts) and leaves the 16 counts in that segment
 // (counts[KV_HIST], scope counts[KV_HIST]); after a workgroup barrier one thread per (rule,
 // count) sums the four waves' segments into O.counts / O.scounts with a global atomic. The
 // store is ordered by kind and namespace, so a workgroup mostly holds one scope. `sc` is this
 // lane's scope.
-__device__ __forceinline__ void kv_end_flush(const DevOut& O, uint32_t* s_stw, uint32_t nr, const uint32_t* rules,
+// Rule ids: `rules` is the kernel's constant table and the row a thread handles varies per lane,
+// so rules[q] would be a vector load, and the wait for it would also drain every store and atomic
+// issued before it. Instead the workgroup reads the table once, ahead of the entry barrier: a
+// wave's record counter bytes (KV_KROWS of them, its own, dead after its last block) take the
+// ids of KV_KROWS / 4 rows, the four waves' together the kernel's table, s_id[q] = rules[q].
+// After the barrier the ids come from LDS and nothing loads from memory, so no store or atomic
+// of the flush is waited for: they stream behind the LDS work. (Held in registers instead, a
+// thread's 8 ids spilled over the count phase.)
+template <uint32_t NR>
+__device__ __forceinline__ void kv_end_flush(const DevOut& O, uint32_t* s_stw, const uint32_t* rules,
                                              uint32_t n_res, uint32_t r, bool valid, uint32_t sc, uint32_t wsc,
                                              uint32_t n_rules) {
+  constexpr uint32_t LPR = KV_RSTRIDE / 16u;  // lanes per row of the copy loop, 16 B each
+  constexpr uint32_t IPW = KV_KROWS / 4u;     // ids a wave's counter bytes hold
+  static_assert(NR >= 1u && NR <= KV_KROWS, "rows of one rule kernel");
+  static_assert(KV_RSTRIDE % 16u == 0u && (uint32_t)KV_RWG % LPR == 0u && 64u % LPR == 0u, "a wave store writes whole rows");
+  static_assert(LPR == 2u * (uint32_t)KV_HIST, "the copy loop and the sum loop walk the same rows");
+  static_assert(KV_ROW0 == KV_RWAVES * KV_KROWS && KV_RWAVES * IPW >= KV_KROWS && IPW <= 64u,
+                "the waves' counter bytes hold an id per row, each wave writing its own");
   const uint8_t* s_b = (const uint8_t*)s_stw + KV_ROW0;
-  __syncthreads();  // (the waves read each other's rows)
+#ifndef KVEMU
+  const uint32_t* s_id = s_stw;
+  {
+    uint32_t t = (threadIdx.x >> 6) * IPW + (threadIdx.x & 63u);
+    asm volatile("" : "+v"(t));  // (the read issues here, not above the blocks with its id live over them)
+    // every lane reads, and the id is named on the wave's straight path: the one wait of the flush
+    // on vector memory stands here, ahead of the barrier, for this read and for whatever load of
+    // the blocks a lane left in flight (a wait for one of those further down, where its register is
+    // written again, would drain the flush's stores); the lane's scope arrives here too
+    uint32_t ri = kv_gld(rules, t < NR ? t : NR - 1u);
+    asm volatile("" : "+v"(ri));
+    if (KV_OFULL(O) & 8u) asm volatile("" : "+v"(sc));
+    if ((threadIdx.x & 63u) < IPW && t < NR) s_stw[t] = ri;
+  }
+#endif
+  __syncthreads();  // (the waves read each other's rows and ids)
 #ifndef KVEMU
   const uint32_t wg0 = r - threadIdx.x;
 #ifdef KV_DIAG_NOCOPY
@@ -1080,20 +1111,20 @@ __device__ __forceinline__ void kv_end_flush(const DevOut& O, uint32_t* s_stw, u
     // byte per lane and row, round 4); a partial workgroup, or rows not 16 B aligned: a byte per
     // lane. A row segment of the workgroup that is NOMATCH throughout (72 % of C3's statuses) is
     // not written: its flag says so (O.sflag) and the fetch fills it
-    constexpr uint32_t LPR = KV_RSTRIDE / 16u;
     const uint32_t l = threadIdx.x & 63u, c16 = (threadIdx.x % LPR) * 16u;
     const size_t nwg = (n_res + (uint32_t)KV_RWG - 1u) / (uint32_t)KV_RWG;
-    for (uint32_t q = threadIdx.x / LPR; q < nr; q += (uint32_t)KV_RWG / LPR) {
+    for (uint32_t q = threadIdx.x / LPR; q < NR; q += (uint32_t)KV_RWG / LPR) {
       const uint4 v = *(const uint4*)(s_b + q * KV_RSTRIDE + c16);
+      const uint32_t ri = s_id[q];
       if (O.sflag) {
         constexpr uint32_t NM4 = 0x01010101u * (uint32_t)ST_NOMATCH;
         const bool nm = v.x == NM4 && v.y == NM4 && v.z == NM4 && v.w == NM4;
         // the row's LPR lanes
         const bool any = ((__ballot(!nm) >> (l & (64u - LPR))) & ((1ull << LPR) - 1ull)) != 0ull;
-        if ((l % LPR) == 0u) O.sflag[(size_t)rules[q] * nwg + wg0 / (uint32_t)KV_RWG] = any ? 1u : 0u;
+        if ((l % LPR) == 0u) O.sflag[(size_t)ri * nwg + wg0 / (uint32_t)KV_RWG] = any ? 1u : 0u;
         if (!any) continue;
       }
-      *(uint4*)(O.status + (size_t)rules[q] * n_res + wg0 + c16) = v;
+      *(uint4*)(O.status + (size_t)ri * n_res + wg0 + c16) = v;
     }
     // (a wave copies the other waves' segments, which they overwrite with counts below; the
     // condition is uniform over the workgroup)
@@ -1101,10 +1132,11 @@ __device__ __forceinline__ void kv_end_flush(const DevOut& O, uint32_t* s_stw, u
   } else
 #endif
   if ((KV_OFULL(O) & 1u) && valid) {
+    // (q is uniform here: the ids come through scalar loads)
 #pragma unroll 4
-    for (uint32_t q = 0; q < nr; q++) O.status[(size_t)rules[q] * n_res + r] = s_b[q * KV_RSTRIDE + threadIdx.x];
+    for (uint32_t q = 0; q < NR; q++) O.status[(size_t)rules[q] * n_res + r] = s_b[q * KV_RSTRIDE + threadIdx.x];
     if (O.sflag && (r & ((uint32_t)KV_RWG - 1u)) == 0u)  // (the workgroup's first lane: rows written)
-      for (uint32_t q = 0; q < nr; q++) O.sflag[(size_t)rules[q] * ((n_res + (uint32_t)KV_RWG - 1u) / (uint32_t)KV_RWG) + r / (uint32_t)KV_RWG] = 1u;
+      for (uint32_t q = 0; q < NR; q++) O.sflag[(size_t)rules[q] * ((n_res + (uint32_t)KV_RWG - 1u) / (uint32_t)KV_RWG) + r / (uint32_t)KV_RWG] = 1u;
   }
 #ifdef KV_DIAG_NOCOUNT
   return;
@@ -1123,16 +1155,17 @@ __device__ __forceinline__ void kv_end_flush(const DevOut& O, uint32_t* s_stw, u
         mw = m;
         continue;
       }
-      for (uint32_t q = l; q < nr; q += 64u) {
+      for (uint32_t q = l; q < NR; q += 64u) {
         uint32_t c[KV_HIST];
         kv_count_seg((const uint32_t*)(s_b + q * KV_RSTRIDE + w * 64u), m, c);
+        const uint32_t ri = s_id[q];
         for (uint32_t k = 0; k < (uint32_t)KV_HIST; k++)
-          if (c[k] && k != 7u) atomicAdd(&O.scounts[((size_t)s * n_rules + rules[q]) * KV_HIST + k], (unsigned long long)c[k]);
+          if (c[k] && k != 7u) atomicAdd(&O.scounts[((size_t)s * n_rules + ri) * KV_HIST + k], (unsigned long long)c[k]);
       }
     }
   }
   kv_wsync();
-  for (uint32_t q = l; q < nr; q += 64u) {
+  for (uint32_t q = l; q < NR; q += 64u) {
     uint32_t* seg = (uint32_t*)(s_b + q * KV_RSTRIDE + w * 64u);
     uint32_t c[KV_HIST], cs[KV_HIST];
     kv_count_seg(seg, ~0ull, c);
@@ -1145,10 +1178,11 @@ __device__ __forceinline__ void kv_end_flush(const DevOut& O, uint32_t* s_stw, u
     }
   }
   __syncthreads();
-  for (uint32_t t = threadIdx.x; t < nr * 2u * KV_HIST; t += (uint32_t)KV_RWG) {
+  for (uint32_t t = threadIdx.x; t < NR * 2u * KV_HIST; t += (uint32_t)KV_RWG) {
     const uint32_t q = t / (2u * KV_HIST), k = t % (2u * KV_HIST);
     uint32_t v = 0u;
     for (uint32_t x = 0; x < KV_RWAVES; x++) v += ((const uint32_t*)(s_b + q * KV_RSTRIDE + x * 64u))[k];
+    const uint32_t ri = s_id[q];
 #ifdef KV_DIAG_NOATOM
     asm volatile("" ::"v"(v));
     continue;
@@ -1156,9 +1190,9 @@ __device__ __forceinline__ void kv_end_flush(const DevOut& O, uint32_t* s_stw, u
     if (!v) continue;
     if (k < (uint32_t)KV_HIST) {
       // (with per-scope counts the per-rule totals are their sum, kv_scope_totals_kernel)
-      if (!(KV_OFULL(O) & 8u)) atomicAdd(&O.counts[(size_t)rules[q] * KV_HIST + k], (unsigned long long)v);
+      if (!(KV_OFULL(O) & 8u)) atomicAdd(&O.counts[(size_t)ri * KV_HIST + k], (unsigned long long)v);
     } else if ((KV_OFULL(O) & 8u) && wsc != 0xFFFFFFFFu)
-      atomicAdd(&O.scounts[((size_t)wsc * n_rules + rules[q]) * KV_HIST + (k - KV_HIST)], (unsigned long long)v);
+      atomicAdd(&O.scounts[((size_t)wsc * n_rules + ri) * KV_HIST + (k - KV_HIST)], (unsigned long long)v);
   }
 #else
   (void)sc; (void)wsc; (void)n_rules;  // (counts are not emulated)

@@ -229,11 +229,11 @@ struct GSiteDesc {
 };
 
 constexpr int KV_WG = 256;
-// Workgroup of the specialized rule kernels: one wave. A workgroup's LDS (its status rows) is
-// released when its last wave ends, so with four waves per workgroup a wave that finished its
-// blocks early held its slot until the slowest wave of the four reached the end-of-kernel flush
-// (C2: 14 % of wave lifetime at that barrier, KVGPU_JIT_STAMPS); one-wave workgroups hand their
-// LDS and registers to the next workgroup as soon as they end.
+// Workgroup of the specialized rule kernels: four waves, 256 resources. A workgroup's statuses
+// of a rule are one 256-byte row of its LDS, which the end-of-kernel flush (kvdevfn.h
+// kv_end_flush) copies in 16 B pieces and counts across the waves, and one segment of the status
+// matrix (DevOut::sflag, KV_WG). The waves meet at the flush's entry barrier: a wave that ends its
+// blocks early holds its slot until the slowest of the four arrives.
 constexpr int KV_RWG = 256;
 constexpr uint32_t KV_RWAVES = (uint32_t)KV_RWG / 64u;
 // LDS of a specialized rule kernel: the waves' record counters (a byte per (wave, row), wave

@@ -2431,7 +2431,7 @@ struct Gen {
       o << "#ifndef KVEMU\n  if ((KV_OFULL(O) & 2u) && !(KV_OFULL(O) & 4u) && (threadIdx.x & 63u) < " << u32(kern.gsn)
         << " && r - (threadIdx.x & 63u) < n_res)\n    O.gcnt[(size_t)(" << u32(kern.gs0)
         << " + (threadIdx.x & 63u)) * ((n_res + 63u) >> 6) + (r >> 6)] = s_gc_[(threadIdx.x & 63u) * KV_RWAVES + (threadIdx.x >> 6)];\n#endif\n";
-    o << "  kv_end_flush(O, s_stw, " << nr << "u, " << name << "_rules, n_res, r, valid, "
+    o << "  kv_end_flush<" << nr << "u>(O, s_stw, " << name << "_rules, n_res, r, valid, "
          "(KV_OFULL(O) & 8u) && valid ? O.scope[r] : 0xFFFFFFFFu, (KV_OFULL(O) & 8u) && wg0_ < n_res ? O.scope[wg0_] : 0xFFFFFFFFu, "
          "P.n_rules);\n";
     stamp(std::min<size_t>(blocks.size() + 1, kJitStamps - 1));

@@ -23,6 +23,18 @@ before them. A chain of them is a walk of the node rows, each load waiting for t
 it (a cursor's type, its map's slot, the child); the lookups of a hoist region share their
 waits instead. Per kernel (column `one`) and per loop.
 
+End flush (`flush`): one line per kernel for the code from the entry barrier of kv_end_flush
+(kvdevfn.h) to s_endpgm: its instructions, vector-memory loads, `s_waitcnt`s with a vmcnt field,
+stores and atomics. Stores and atomics count in vmcnt with the loads, so a load's wait in this
+region also drains every store and atomic before it; the flush reads its rule ids ahead of the
+entry barrier and should show no load and no wait here. The entry barrier is found from the
+end, since the prefill has a barrier of its own near the kernel start: the flush has three
+barriers where the kernel copies statuses (entry, after the copy, after the count phase), so
+the entry barrier is the third from the end; a variant that writes no status matrix (.m8) has
+no copy loop and no middle barrier, and the kernel then has three barriers in all: there the
+entry barrier is the second from the end. (At run time the byte path of a partial workgroup
+skips the middle barrier too; statically it is there.)
+
     python tools/jit_isa.py [c2|c3|c4|c5] [--env K=V ...]
 """
 import collections
@@ -106,6 +118,22 @@ def loop_report(dis):
     return out
 
 
+def flush_report(dis):
+    """(instructions, loads, vmcnt waits, stores, atomics) from the end flush's entry barrier to s_endpgm;
+    None if the kernel has no such region"""
+    ins = INST.findall(dis)
+    ends = [i for i, x in enumerate(ins) if x[0] == "s_endpgm"]
+    if not ends:
+        return None
+    bars = [i for i, x in enumerate(ins[:ends[0]]) if x[0] == "s_barrier"]
+    if len(bars) < 3:
+        return None
+    reg = ins[bars[-3] if len(bars) >= 4 else bars[-2]:ends[0] + 1]
+    return (len(reg), sum(is_load(o) for o, *_ in reg), sum(is_wait(o, rest) for o, rest, *_ in reg),
+            sum(o.startswith(("global_store", "flat_store", "buffer_store")) for o, *_ in reg),
+            sum(o.startswith(("global_atomic", "flat_atomic", "buffer_atomic")) for o, *_ in reg))
+
+
 tot = collections.Counter()
 print(f"{'kernel':24s} {'vgpr':>4s} {'sgpr':>4s} {'spill':>5s} {'priv':>4s} {'KB':>6s} {'salu':>6s} {'exec':>6s} "
       f"{'valu':>6s} {'lane':>5s} {'vmem':>5s} {'lds':>5s} {'ld':>5s} {'wait':>5s} {'one':>5s}")
@@ -153,4 +181,7 @@ for f in sorted(glob.glob(os.path.join(d, "k.*.co"))):
     for k, (n, b, h) in enumerate(loop_report(dis)):
         print(f"  loop {k}: {n:5d} instructions, {b[0]:3d} loads {b[1]:3d} waits {b[2]:3d} rounds {b[3]:3d} single; "
               f"head: {h[0]:2d} loads {h[1]:2d} waits {h[2]:2d} rounds")
+    fr = flush_report(dis)
+    if fr:
+        print(f"  flush: {fr[0]:5d} instructions, {fr[1]:3d} loads {fr[2]:3d} waits {fr[3]:3d} stores {fr[4]:3d} atomics")
 print("total", dict(tot))
