@@ -77,7 +77,20 @@ enum {
    * an element holding an int64-typed number where that typing could change the verdict (a
    * string pattern compared on the number's text form, |n| >= 2^53) is CPU, as is an error
    * record that does not fit 8 bytes. */
-  KV_COMPILE_FOREACH_PATTERN = 8
+  KV_COMPILE_FOREACH_PATTERN = 8,
+  /* also evaluate validate.foreach rules of 2 to 16 entries on the device (opt-in; needs
+   * KV_COMPILE_FOREACH, else kv_compile returns KV_E_INVALID; composes with
+   * KV_COMPILE_FOREACH_PATTERN; without it such a rule is KV_ROUTE_CPU, reason "foreach"). Every
+   * entry must be what a single entry may be under the other two flags; deny and pattern entries
+   * may mix. The entries run in order with one applyCount: the first FAIL / ERROR / CPU element
+   * of the first entry that has one decides (kv_result_foreach_entry, kv_result_foreach_element),
+   * else PASS when an element of any entry passed, else SKIP "rule skipped"; an entry whose list
+   * is outside the device scope makes the pair CPU unless an earlier entry decided. As in the
+   * reference, the last element of entry k stays merged into the context when entry k + 1 starts:
+   * the {{element...}} variables of a later entry's preconditions, deny conditions and message read
+   * the element merged over the last elements of the lists before it (maps merge key by key,
+   * anything else replaces); an entry's pattern sees the raw element. */
+  KV_COMPILE_FOREACH_ENTRIES = 16
 };
 
 /* kv_validate modes (bit set). KV_MODE_SCOPES adds per-scope counts
@@ -153,6 +166,38 @@ int kv_rule_foreach_set(const kv_policyset* ps, uint32_t rule, uint32_t* set);
 /* *on = 1 when rule `rule` is a device foreach rule whose entry carries a pattern
  * (KV_COMPILE_FOREACH_PATTERN), else 0 */
 int kv_rule_foreach_pattern(const kv_policyset* ps, uint32_t rule, uint32_t* on);
+/* Rules of several entries (KV_COMPILE_FOREACH_ENTRIES). A *chain* is the ordered list of the
+ * foreach sets of a rule's entries, interned by that list. kv_policyset_foreach_chains: their
+ * number. kv_rule_foreach_chain: *chain_plus_1 = 1 + the chain of rule `rule` and *n_entries its
+ * entry count, both 0 for any other rule (kv_rule_foreach_set, kv_rule_foreach_pattern and
+ * kv_rule_deny_set are 0 for a chain rule). kv_chain_entry_set: *set = the foreach set (0-based)
+ * of entry `k` of chain `chain` (0-based); KV_E_RANGE past the end. */
+int kv_policyset_foreach_chains(const kv_policyset* ps, uint32_t* chains);
+int kv_rule_foreach_chain(const kv_policyset* ps, uint32_t rule, uint32_t* chain_plus_1, uint32_t* n_entries);
+int kv_chain_entry_set(const kv_policyset* ps, uint32_t chain, uint32_t k, uint32_t* set);
+/* The fold of chain `chain` (0-based) over an ingested batch, on the host: the twin of the entry
+ * sets' kernels and kv_foreach_chain_kernel. status[i] of resource i (caller order) as
+ * kv_batch_foreach_fold; entry[i] / elem[i] (each may be null) the deciding entry and the index of
+ * the deciding element in that entry's list, 0xFFFFFFFF without one. Needs no GPU. KV_E_INVALID
+ * when an entry of the chain carries a pattern. */
+int kv_batch_foreach_chain_fold(const kv_policyset* ps, const kv_batch* b, uint32_t chain, uint8_t* status, uint32_t* entry,
+                                uint32_t* elem, uint64_t n);
+/* The text kv_result_foreach_message gives for resource `res` (caller order) of a chain where the
+ * fold decides the pair, from the host fold alone: "validation failed in foreach rule for failed to
+ * substitute variables in deny conditions: ..." for an ERROR (the first string that does not
+ * resolve on the deciding element merged over what the entries before it leaked), "rule skipped"
+ * for a SKIP; returns its length, 0 for any other status. Needs no GPU. KV_E_INVALID when an entry
+ * of the chain carries a pattern. */
+int kv_batch_foreach_chain_message(const kv_policyset* ps, const kv_batch* b, uint32_t chain, uint64_t res, char* buf,
+                                   size_t cap);
+/* (diagnostics) The per-batch foreach tables as the device receives them (sets, lists, element
+ * rows, list states, pattern and chain tables, the gate's and the deny blocks' entries, outcome
+ * ids and planes), each as a 64-bit count followed by its 32-bit words, in one buffer the caller
+ * frees with kv_free_buffer. Needs no GPU. */
+int kv_batch_foreach_tables(const kv_policyset* ps, const kv_batch* b, char** out, size_t* len);
+/* *on = 1 when foreach set `set` (0-based) is a pattern set (its entry carries a pattern: no host
+ * fold), else 0 */
+int kv_foreach_set_pattern(const kv_policyset* ps, uint32_t set, uint32_t* on);
 /* The foreach fold of foreach set `set` (0-based) over an ingested batch, on the host: the twin
  * of kv_foreach_elem_kernel and kv_foreach_fin_kernel. status[i] of resource i (caller order) is
  * KV_STATUS_PASS / _FAIL / _ERROR / _SKIP / _CPU before match / exclude and the rule's
@@ -275,6 +320,14 @@ int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char
  * (kv_result_deny_message is 0 for foreach rules). Negative codes as kv_result_subst_error. */
 int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* index);
 int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
+/* Rules of several entries (KV_COMPILE_FOREACH_ENTRIES). A result fetched with statuses carries
+ * a 4-byte key per (chain, resource): the deciding entry, its element and the code.
+ * kv_result_foreach_entry: *entry = the position of the entry that decided a FAIL or ERROR pair
+ * (0 for a rule of one entry), 0xFFFFFFFF for every other pair; kv_result_foreach_element then
+ * gives the index within that entry's list, and kv_result_foreach_message, _path and
+ * _error_message answer through the deciding entry's set (the ERROR text of a deny entry names
+ * the first string that does not resolve on the merged element). */
+int kv_result_foreach_entry(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* entry);
 /* Pattern entries (KV_COMPILE_FOREACH_PATTERN). A result fetched with statuses carries, per
  * pattern set and resource, the reduction key (the deciding element and its code) and the deciding
  * element's 8-byte error record; kv_result_foreach_element reads the key for these rules, and

@@ -96,6 +96,14 @@ def lib():
         L.kv_result_foreach_element.argtypes = [vp, u32, u64, ctypes.POINTER(u32)]
         L.kv_result_foreach_message.argtypes = [vp, u32, u64, ctypes.c_char_p, sz]
         L.kv_rule_foreach_pattern.argtypes = [vp, u32, ctypes.POINTER(u32)]
+        L.kv_policyset_foreach_chains.argtypes = [vp, ctypes.POINTER(u32)]
+        L.kv_rule_foreach_chain.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.kv_chain_entry_set.argtypes = [vp, u32, u32, ctypes.POINTER(u32)]
+        L.kv_batch_foreach_chain_fold.argtypes = [vp, vp, u32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u64]
+        L.kv_result_foreach_entry.argtypes = [vp, u32, u64, ctypes.POINTER(u32)]
+        L.kv_batch_foreach_chain_message.argtypes = [vp, vp, u32, u64, ctypes.c_char_p, sz]
+        L.kv_foreach_set_pattern.argtypes = [vp, u32, ctypes.POINTER(u32)]
+        L.kv_batch_foreach_tables.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         L.kv_result_foreach_path.argtypes = [vp, u32, u64, ctypes.c_char_p, sz]
         L.kv_result_foreach_error_message.argtypes = [vp, u32, u64, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
         L.kv_result_kernel_ms.argtypes = [vp]
@@ -144,6 +152,9 @@ EXPORTED_SYMBOLS = [
     "kv_result_deny_message", "kv_policyset_deny_sets", "kv_rule_deny_set", "kv_batch_deny_fold",
     "kv_policyset_foreach_sets", "kv_rule_foreach_set", "kv_batch_foreach_fold", "kv_result_foreach_element",
     "kv_result_foreach_message", "kv_rule_foreach_pattern", "kv_result_foreach_path", "kv_result_foreach_error_message",
+    "kv_policyset_foreach_chains", "kv_rule_foreach_chain", "kv_chain_entry_set", "kv_batch_foreach_chain_fold",
+    "kv_result_foreach_entry", "kv_batch_foreach_chain_message", "kv_foreach_set_pattern",
+    "kv_batch_foreach_tables",
     "kv_bench", "kv_synth", "kv_synth_range", "kv_free_policyset", "kv_free_batch", "kv_free_result", "kv_free_error",
     "kv_free_buffer", "kv_session_create", "kv_session_run", "kv_session_counts", "kv_free_session",
     "kv_session_scope_counts", "kv_result_scope_counts", "kv_batch_namespaces", "kv_batch_namespace",

@@ -23,6 +23,9 @@ element passed, else ``SKIP`` "rule skipped" (``Result.foreach_message``).
 evaluates entries that carry a ``pattern``: the pattern is matched per element with the element as
 the whole resource (``kv_foreach_pat_kernel``); the deciding element's failing path and pattern
 error are ``Result.foreach_path`` / ``Result.foreach_error_message``.
+``PolicySet(..., foreach=True, foreach_entries=True)`` (``KV_COMPILE_FOREACH_ENTRIES``, opt-in) also
+takes ``validate.foreach`` rules of 2 to 16 such entries (``kv_foreach_chain_kernel`` walks the
+entries' rows in order); ``Result.foreach_entry`` names the deciding entry.
 """
 from __future__ import annotations
 
@@ -40,6 +43,7 @@ STATUS_NAMES = ["pass", "fail", "warn", "error", "skip", "nomatch", "cpu"]
 
 MODE_STATUS, MODE_ERRORS, MODE_COUNTS, MODE_SCOPES = 1, 2, 4, 8
 COMPILE_SPECIALIZE, COMPILE_DENY, COMPILE_FOREACH, COMPILE_FOREACH_PATTERN = 1, 2, 4, 8
+COMPILE_FOREACH_ENTRIES = 16
 ROUTE_GPU, ROUTE_CPU, ROUTE_NORESPONSE, ROUTE_CONSTANT = range(4)
 
 
@@ -78,6 +82,7 @@ class Rule:
     deny: bool = False  # a validate.deny rule evaluated on the device (PolicySet(deny=True))
     foreach: bool = False  # a validate.foreach rule evaluated on the device (PolicySet(foreach=True))
     foreach_pattern: bool = False  # ... whose entry carries a pattern (PolicySet(foreach_pattern=True))
+    foreach_entries: int = 0  # ... of several entries: their number (PolicySet(foreach_entries=True)), else 0
 
 
 class PolicySet:
@@ -101,22 +106,29 @@ class PolicySet:
     ``foreach_pattern=True`` (``KV_COMPILE_FOREACH_PATTERN``, opt-in, needs ``foreach``) also routes
     entries ``{list, preconditions?, pattern}`` to the GPU: the pattern a map without ``{{ }}``
     variables or a ``metadata`` key. Without it such a rule stays CPU-routed, reason ``"foreach"``.
+
+    ``foreach_entries=True`` (``KV_COMPILE_FOREACH_ENTRIES``, opt-in, needs ``foreach``) also routes
+    rules of 2 to 16 entries, each of the forms above, to the GPU. As in the reference, the
+    ``{{element...}}`` variables of a later entry read the element merged over the last elements of
+    the lists before it. Without it such a rule stays CPU-routed, reason ``"foreach"``.
     """
 
     def __init__(self, policies, specialize: bool = False, deny: bool = False, foreach: bool = False,
-                 foreach_pattern: bool = False):
+                 foreach_pattern: bool = False, foreach_entries: bool = False):
         L = lib()
         data = _dumps(policies)
         h = ctypes.c_void_p()
         err = new_err()
         flags = ((COMPILE_SPECIALIZE if specialize else 0) | (COMPILE_DENY if deny else 0)
-                 | (COMPILE_FOREACH if foreach else 0) | (COMPILE_FOREACH_PATTERN if foreach_pattern else 0))
+                 | (COMPILE_FOREACH if foreach else 0) | (COMPILE_FOREACH_PATTERN if foreach_pattern else 0)
+                 | (COMPILE_FOREACH_ENTRIES if foreach_entries else 0))
         check(L.kv_compile(data, len(data), flags, ctypes.byref(h), ctypes.byref(err)), err)
         self._h = h
         self.specialize = specialize
         self.deny = deny
         self.foreach = foreach
         self.foreach_pattern = foreach_pattern
+        self.foreach_entries = foreach_entries
         np_, nr = ctypes.c_uint32(), ctypes.c_uint32()
         L.kv_policyset_info(h, ctypes.byref(np_), ctypes.byref(nr))
         self.n_policies, self.n_rules = np_.value, nr.value
@@ -134,6 +146,11 @@ class PolicySet:
             on = ctypes.c_uint32()
             L.kv_rule_foreach_pattern(h, i, ctypes.byref(on))
             self.rules[-1].foreach_pattern = on.value != 0
+            ch, ne = ctypes.c_uint32(), ctypes.c_uint32()
+            L.kv_rule_foreach_chain(h, i, ctypes.byref(ch), ctypes.byref(ne))
+            if ch.value:  # (kv_rule_info.foreach_set stays 0 for a rule of several entries)
+                self.rules[-1].foreach = True
+                self.rules[-1].foreach_entries = ne.value
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -211,17 +228,89 @@ class PolicySet:
         walked on the device only."""
         info = self.foreach_info
         n_sets = info["sets"]
-        pattern_sets = {info["rule_sets"][r.index] - 1 for r in self.rules if r.foreach_pattern}
         st = np.zeros((n_sets, b.n_res), dtype=np.uint8)
         el = np.full((n_sets, b.n_res), 0xFFFFFFFF, dtype=np.uint32)
         for s in range(n_sets):
-            if s in pattern_sets:
+            on = ctypes.c_uint32()
+            lib().kv_foreach_set_pattern(self._h, s, ctypes.byref(on))
+            if on.value:  # (a pattern set, of a rule of one entry or of several)
                 st[s] = 255
                 continue
             rc = lib().kv_batch_foreach_fold(self._h, b._h, s, st[s].ctypes.data, el[s].ctypes.data, b.n_res)
             if rc != 0:
                 raise RuntimeError(f"kv_batch_foreach_fold: code {rc}")
         return st, el
+
+    @property
+    def foreach_chain_info(self) -> dict:
+        """Foreach rules of several entries (``foreach_entries=True``): the interned chains
+        (``kv_policyset_foreach_chains``), per chain the foreach sets of its entries in order
+        (``kv_chain_entry_set``, 0-based), and per rule 1 + its chain, 0 for any other rule
+        (``kv_rule_foreach_chain``)."""
+        n = ctypes.c_uint32()
+        lib().kv_policyset_foreach_chains(self._h, ctypes.byref(n))
+        rule_chains, entries = [], {}
+        for i in range(self.n_rules):
+            ch, ne = ctypes.c_uint32(), ctypes.c_uint32()
+            lib().kv_rule_foreach_chain(self._h, i, ctypes.byref(ch), ctypes.byref(ne))
+            rule_chains.append(ch.value)
+            if ch.value:
+                entries[ch.value - 1] = ne.value
+        chain_sets = []
+        for c in range(n.value):
+            sets, k = [], 0
+            while True:
+                s = ctypes.c_uint32()
+                if lib().kv_chain_entry_set(self._h, c, k, ctypes.byref(s)) != 0:
+                    break
+                sets.append(s.value)
+                k += 1
+            chain_sets.append(sets)
+        return {"chains": n.value, "chain_sets": chain_sets, "rule_chains": rule_chains}
+
+    def foreach_chain_fold(self, b: "Batch") -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(u8 status, u32 entry, u32 element) [chains][n_res]: the fold of every chain over batch
+        ``b`` on the host (``kv_batch_foreach_chain_fold``, no GPU), the twin of the entry kernels and
+        ``kv_foreach_chain_kernel``; entry / element 0xFFFFFFFF: none decided. The rows of chains
+        with a pattern entry stay unset, status 255."""
+        n = self.foreach_chain_info["chains"]
+        st = np.zeros((n, b.n_res), dtype=np.uint8)
+        en = np.full((n, b.n_res), 0xFFFFFFFF, dtype=np.uint32)
+        el = np.full((n, b.n_res), 0xFFFFFFFF, dtype=np.uint32)
+        for c in range(n):
+            rc = lib().kv_batch_foreach_chain_fold(self._h, b._h, c, st[c].ctypes.data, en[c].ctypes.data,
+                                                   el[c].ctypes.data, b.n_res)
+            if rc == -1:
+                st[c] = 255
+            elif rc != 0:
+                raise RuntimeError(f"kv_batch_foreach_chain_fold: code {rc}")
+        return st, en, el
+
+    def foreach_tables(self, b: "Batch") -> bytes:
+        """The per-batch foreach tables of ``b`` as the device receives them, as bytes
+        (``kv_batch_foreach_tables``; diagnostics, no GPU)."""
+        p, ln = ctypes.c_void_p(), ctypes.c_size_t()
+        rc = lib().kv_batch_foreach_tables(self._h, b._h, ctypes.byref(p), ctypes.byref(ln))
+        if rc != 0:
+            raise RuntimeError(f"kv_batch_foreach_tables: code {rc}")
+        try:
+            return ctypes.string_at(p.value, ln.value)
+        finally:
+            lib().kv_free_buffer(p)
+
+    def foreach_chain_message(self, b: "Batch", chain: int, res: int) -> str | None:
+        """What ``Result.foreach_message`` gives for resource ``res`` of chain ``chain`` where the fold
+        decides the pair, from the host fold (``kv_batch_foreach_chain_message``, no GPU): the ERROR
+        text of a deny entry, "rule skipped" for a SKIP, else None."""
+        cap = 256
+        while True:
+            buf = ctypes.create_string_buffer(cap)
+            n = lib().kv_batch_foreach_chain_message(self._h, b._h, chain, res, buf, cap)
+            if n <= 0:
+                return None
+            if n < cap:
+                return buf.raw[:n].decode("utf-8")
+            cap = n + 1
 
     def policy_rules(self, policy: int) -> list[Rule]:
         return [r for r in self.rules if r.policy == policy]
@@ -380,6 +469,13 @@ class Result:
         rule (``kv_result_foreach_element``), else None."""
         i = ctypes.c_uint32()
         rc = lib().kv_result_foreach_element(self._h, rule, res, ctypes.byref(i))
+        return i.value if rc == 0 and i.value != 0xFFFFFFFF else None
+
+    def foreach_entry(self, rule: int, res: int) -> int | None:
+        """The position among the rule's entries of the one that decided a FAIL / ERROR pair of a
+        device foreach rule (``kv_result_foreach_entry``; 0 for a rule of one entry), else None."""
+        i = ctypes.c_uint32()
+        rc = lib().kv_result_foreach_entry(self._h, rule, res, ctypes.byref(i))
         return i.value if rc == 0 and i.value != 0xFFFFFFFF else None
 
     def foreach_message(self, rule: int, res: int) -> str | None:

@@ -27,10 +27,12 @@ whose conditions are of those forms on the device, with the messages of ``valida
 ``--device-foreach`` (``evaluate(foreach=True)``, ``KV_COMPILE_FOREACH``) does the same for single-entry
 ``validate.foreach`` rules with a ``deny`` block, with the messages of ``validateForEach``;
 ``--device-foreach-pattern`` (``evaluate(foreach_pattern=True)``, ``KV_COMPILE_FOREACH_PATTERN``; implies
-``--device-foreach``) also for entries that carry a ``pattern``.
+``--device-foreach``) also for entries that carry a ``pattern``; ``--device-foreach-entries``
+(``evaluate(foreach_entries=True)``, ``KV_COMPILE_FOREACH_ENTRIES``; implies ``--device-foreach``) also for
+rules of several entries.
 
     python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N] [--device-deny] [--device-foreach]
-        [--device-foreach-pattern]
+        [--device-foreach-pattern] [--device-foreach-entries]
     python -m kyverno_amd test test/cli/test/simple
 """
 from __future__ import annotations
@@ -113,6 +115,7 @@ class Evaluation:
     deny: dict = field(default_factory=dict)    # (rule, res) -> message of an ERROR of a deny rule's substitution
     foreach: dict = field(default_factory=dict)  # (rule, res) -> message of an ERROR / SKIP of a foreach rule
     foreach_elem: dict = field(default_factory=dict)  # (rule, res) -> index of the deciding element (FAIL)
+    foreach_entry: dict = field(default_factory=dict)  # (rule, res) -> the deciding entry (rules of several entries)
     foreach_path: dict = field(default_factory=dict)  # (rule, res) -> failing path in the deciding element (pattern entries)
     foreach_err: dict = field(default_factory=dict)   # (rule, res) -> pattern error of the deciding element (pattern entries, ERROR)
     anypattern: dict = field(default_factory=dict)  # (rule, res) -> [(status, path)] per pattern
@@ -124,7 +127,8 @@ class Evaluation:
 
 def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messages: bool = True,
              namespace_labels: dict | None = None, specialize: bool = False, gpus: int = 1,
-             deny: bool = False, foreach: bool = False, foreach_pattern: bool = False) -> Evaluation:
+             deny: bool = False, foreach: bool = False, foreach_pattern: bool = False,
+             foreach_entries: bool = False) -> Evaluation:
     """All (rule, resource) pairs on the GPU (``kv_compile`` → ``kv_ingest`` → ``kv_validate``).
     ``specialize`` selects the per-policy-set specialized kernels (worth their hiprtc compile on
     large batches) over the bytecode interpreter; both write the same statuses and error records.
@@ -132,11 +136,14 @@ def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messa
     ``deny`` evaluates ``validate.deny`` rules of the device forms on the GPU (``KV_COMPILE_DENY``)
     instead of routing them to the reference engine; ``foreach`` does the same for
     ``validate.foreach`` rules (``KV_COMPILE_FOREACH``), ``foreach_pattern`` (which implies
-    ``foreach``) also for entries that carry a ``pattern`` (``KV_COMPILE_FOREACH_PATTERN``)."""
+    ``foreach``) also for entries that carry a ``pattern`` (``KV_COMPILE_FOREACH_PATTERN``),
+    ``foreach_entries`` (which implies ``foreach`` too) also for rules of several entries
+    (``KV_COMPILE_FOREACH_ENTRIES``)."""
     from . import batch
 
-    ps = batch.PolicySet(policies, specialize=specialize, deny=deny, foreach=foreach or foreach_pattern,
-                         foreach_pattern=foreach_pattern)
+    ps = batch.PolicySet(policies, specialize=specialize, deny=deny,
+                         foreach=foreach or foreach_pattern or foreach_entries,
+                         foreach_pattern=foreach_pattern, foreach_entries=foreach_entries)
     b = batch.Batch(ps, resources, namespace_labels)
     mask = ((1 << gpus) - 1) << device if gpus > 1 else None
     r = batch.validate(ps, b, device=device, device_mask=mask)
@@ -145,7 +152,9 @@ def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messa
         for ri, res in zip(*np.nonzero(r.status == FAIL)):
             if ps.rules[ri].foreach:  # (no failing path either: the deciding element instead)
                 ev.foreach_elem[(int(ri), int(res))] = r.foreach_element(int(ri), int(res))
-                if getattr(ps.rules[ri], "foreach_pattern", False):  # (a pattern entry: the path inside that element)
+                if getattr(ps.rules[ri], "foreach_entries", 0):  # (several entries: which one decided)
+                    ev.foreach_entry[(int(ri), int(res))] = r.foreach_entry(int(ri), int(res))
+                if _pattern_entry(ev, ps.rules[ri], int(res)):  # (a pattern entry: the path inside that element)
                     ev.foreach_path[(int(ri), int(res))] = r.foreach_path(int(ri), int(res))
             elif not ps.rules[ri].any_pattern and not ps.rules[ri].deny:  # (a deny FAIL has no failing path)
                 ev.paths[(int(ri), int(res))] = r.path(int(ri), int(res))
@@ -173,7 +182,9 @@ def collect_errors(ev: Evaluation, ps, r, resources: list) -> None:
             if m is not None:
                 ev.precond[key] = m
                 continue
-        if getattr(ps.rules[ri], "foreach_pattern", False) and r.status[ri, res] == ERROR:
+        if getattr(ps.rules[ri], "foreach_entries", 0) and r.status[ri, res] == ERROR:
+            ev.foreach_entry[key] = r.foreach_entry(*key)
+        if r.status[ri, res] == ERROR and _pattern_entry(ev, ps.rules[ri], key[1]):
             # a pattern entry: the pattern error of the deciding element, formatted from that element
             ev.foreach_elem[key] = r.foreach_element(*key)
             el = _foreach_element(ev, ps.rules[ri], key[1])
@@ -254,16 +265,80 @@ def _message(ev: Evaluation, rule, res: int, element: dict | None = None) -> str
         return rule.message
 
 
-def _foreach_element(ev: Evaluation, rule, res: int):
-    """The deciding element of a FAIL pair of a device foreach rule: the rule's list evaluated on
-    the resource (a map is a one-element list), at the index the device reported."""
-    idx = ev.foreach_elem.get((rule.index, res))
+def _foreach_entries(ev: Evaluation, rule) -> list:
+    """The entries of a foreach rule, as written."""
     src = ev.policies[rule.policy]
     rdoc = next(x for x in src["spec"]["rules"] if x.get("name") == rule.name)
-    lst = msgvars.query(rdoc["validate"]["foreach"][0]["list"], {"request": {"object": ev.resources[res]}})
-    if isinstance(lst, dict):
-        lst = [lst]
-    return lst[idx] if idx is not None and isinstance(lst, list) and idx < len(lst) else None
+    return rdoc["validate"]["foreach"]
+
+
+def _deciding_entry(ev: Evaluation, rule, res: int) -> int | None:
+    """The position of the entry that decided the pair: 0 for a rule of one entry, what the device
+    reported for a rule of several (None: no entry decided)."""
+    if not getattr(rule, "foreach_entries", 0):
+        return 0
+    return ev.foreach_entry.get((rule.index, res))
+
+
+def _pattern_entry(ev: Evaluation, rule, res: int) -> bool:
+    """The pair of a device foreach rule was decided by an entry that carries a pattern."""
+    if getattr(rule, "foreach_pattern", False):
+        return True
+    if not getattr(rule, "foreach_entries", 0):
+        return False
+    k = _deciding_entry(ev, rule, res)
+    return k is not None and "pattern" in _foreach_entries(ev, rule)[k]
+
+
+def _entry_list(entry: dict, resource) -> list | None:
+    """evaluateList of one entry: None where the query fails, a map is a one-element list."""
+    try:
+        lst = msgvars.query(entry["list"], {"request": {"object": resource}})
+    except msgvars.MessageVariableNotFound:
+        return None
+    return [lst] if isinstance(lst, dict) else lst
+
+
+def merge_maps(base, over):
+    """The JSON merge of two documents without nulls (jsonpatch.MergeMergePatches, as AddJSON uses
+    it): two maps merge key by key, anything else replaces what was there."""
+    if not (isinstance(base, dict) and isinstance(over, dict)):
+        return over
+    out = dict(base)
+    for k, v in over.items():
+        out[k] = merge_maps(out[k], v) if k in out else v
+    return out
+
+
+def foreach_leak_base(entries: list, resource, k: int):
+    """What the reference's context holds as ``element`` when entry ``k`` of a foreach rule starts
+    (validateForEach: the checkpoint of an entry is taken with the last element of the entry before
+    it still merged in): the last elements of the lists of entries 0 .. k-1, merged in order; an
+    entry whose list query fails or gives no element adds nothing. None: nothing leaked."""
+    base = None
+    for e in entries[:k]:
+        lst = _entry_list(e, resource)
+        if isinstance(lst, list) and lst and isinstance(lst[-1], dict):
+            base = lst[-1] if base is None else merge_maps(base, lst[-1])
+    return base
+
+
+def _foreach_element(ev: Evaluation, rule, res: int, merged: bool = False):
+    """The deciding element of a FAIL pair of a device foreach rule: the deciding entry's list
+    evaluated on the resource (a map is a one-element list), at the index the device reported.
+    ``merged``: as the variables of that entry see it, over what the entries before it leaked."""
+    idx = ev.foreach_elem.get((rule.index, res))
+    k = _deciding_entry(ev, rule, res)
+    if k is None:
+        return None
+    entries = _foreach_entries(ev, rule)
+    lst = _entry_list(entries[k], ev.resources[res])
+    el = lst[idx] if idx is not None and isinstance(lst, list) and idx < len(lst) else None
+    if merged and el is not None and k:
+        base = foreach_leak_base(entries, ev.resources[res], k)
+        if base is not None:
+            el = merge_maps(base, el)
+    return el
 
 
 def rule_message(ev: Evaluation, rule, res: int) -> str:
@@ -278,7 +353,7 @@ def rule_message(ev: Evaluation, rule, res: int) -> str:
     if getattr(rule, "foreach", False):  # validateForEach (validation.go:204-283)
         if st == PASS:
             return "rule passed"
-        if getattr(rule, "foreach_pattern", False) and st in (FAIL, ERROR):
+        if st in (FAIL, ERROR) and _pattern_entry(ev, rule, res):
             # the element's validatePatterns message: buildErrorMessage in the element's context
             # (validation.go:421-445,510-534)
             head = "validation failed in foreach rule for "
@@ -287,14 +362,15 @@ def rule_message(ev: Evaluation, rule, res: int) -> str:
                     f"execution error: {ev.foreach_err.get((rule.index, res), '')}")
             if not rule.message:
                 return head + f"validation error: rule {rule.name} {tail}"
-            msg = _message(ev, rule, res, _foreach_element(ev, rule, res))
+            msg = _message(ev, rule, res, _foreach_element(ev, rule, res, merged=True))
             return head + f"validation error: {_with_dot(msg)} Rule {rule.name} {tail}"
         if st == FAIL:  # the element's validateDeny message, in the element's context
             head = "validation failed in foreach rule for "
             if not rule.message:
                 return head + f"validation error: rule {rule.name} failed"
             try:
-                return head + msgvars.substitute_message(rule.message, ev.resources[res], _foreach_element(ev, rule, res))
+                return head + msgvars.substitute_message(rule.message, ev.resources[res],
+                                                         _foreach_element(ev, rule, res, merged=True))
             except (msgvars.MessageVariableNotFound, msgvars.UnsupportedMessageVariable):
                 return head + rule.message
         return ev.foreach.get((rule.index, res), "")  # ERROR, SKIP "rule skipped"
@@ -421,18 +497,19 @@ def policy_has_validate(policy: dict) -> bool:
 
 def apply(policy_paths: list[str], resource_paths: list[str], policy_report: bool = False, device: int = 0,
           out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
-          foreach: bool = False, foreach_pattern: bool = False) -> tuple[ResultCounts, list]:
+          foreach: bool = False, foreach_pattern: bool = False, foreach_entries: bool = False) -> tuple[ResultCounts, list]:
     """applyCommandHelper (apply_command.go:147-310) for resource files. Returns counts and the
     policyreport infos. ``evaluation_fn(policies, resources) -> Evaluation`` replaces the device
     evaluation (tests of the host logic)."""
     policies = load_policies(policy_paths)
     resources = load_resources(resource_paths)
-    return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny, foreach, foreach_pattern)
+    return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny, foreach, foreach_pattern,
+                      foreach_entries)
 
 
 def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool = False, device: int = 0,
                out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
-          foreach: bool = False, foreach_pattern: bool = False) -> tuple[ResultCounts, list]:
+          foreach: bool = False, foreach_pattern: bool = False, foreach_entries: bool = False) -> tuple[ResultCounts, list]:
     mutated = autogen.mutate_policies(policies)
     if len(mutated) > 0 and len(resources) > 0:
         msg_p = "1 policy" if len(mutated) <= 1 else f"{len(policies)} policies"
@@ -445,7 +522,8 @@ def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool 
     infos = []
     if active and resources:
         ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus, deny=deny, foreach=foreach,
-                                                          foreach_pattern=foreach_pattern)))(active, resources)
+                                                          foreach_pattern=foreach_pattern,
+                                                          foreach_entries=foreach_entries)))(active, resources)
         for pi, pol in enumerate(active):
             if not policy_has_validate(pol):
                 continue
@@ -556,6 +634,9 @@ def main(argv: list[str] | None = None) -> int:
     a.add_argument("--device-foreach-pattern", action="store_true",
                    help="also evaluate validate.foreach entries that carry a pattern on the GPU "
                         "(KV_COMPILE_FOREACH_PATTERN; implies --device-foreach)")
+    a.add_argument("--device-foreach-entries", action="store_true",
+                   help="also evaluate validate.foreach rules of several entries on the GPU "
+                        "(KV_COMPILE_FOREACH_ENTRIES; implies --device-foreach)")
     t = sub.add_parser("test", help="run tests from a directory holding test.yaml")
     t.add_argument("dir")
     t.add_argument("--device", type=int, default=0)
@@ -563,8 +644,8 @@ def main(argv: list[str] | None = None) -> int:
     if args.cmd == "apply":
         try:
             rc, _ = apply(args.policies, args.resource, args.policy_report, args.device, gpus=args.gpus, deny=args.device_deny,
-                          foreach=args.device_foreach or args.device_foreach_pattern,
-                          foreach_pattern=args.device_foreach_pattern)
+                          foreach=args.device_foreach or args.device_foreach_pattern or args.device_foreach_entries,
+                          foreach_pattern=args.device_foreach_pattern, foreach_entries=args.device_foreach_entries)
         except msgvars.MessageVariableError as e:
             # the Go CLI dies in buildErrorMessage (msgRaw.(string), validation.go:519-524): a
             # panic, exit status 2

@@ -70,6 +70,8 @@ struct DevBatchRes {
   // (rows of the deny sets) and the foreach kernels (rows after them) wrote; HIP-event times
   // pattern sets (KV_COMPILE_FOREACH_PATTERN): their three tables and fe_rec[pattern set][res]
   DevBuf pre[5], dn[7], feg[2], fed[7], fe[5], fep[3], feacc, ferec, prest, dnst;
+  // rules of several entries (KV_COMPILE_FOREACH_ENTRIES): the chain tables and fe_ckey[chain][res]
+  DevBuf fec[2], feckey;
   double pre_ms = 0, deny_ms = 0, fe_ms = 0;
   DevBatch view{};
 };
@@ -400,7 +402,8 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
   FePatTables qt{};
   DevBuf erec;  // the pattern sets' per-element records: needed until the fold's kernels are done
   const uint32_t n_sets = (uint32_t)ps.csets.size(), n_dsets = (uint32_t)ps.dsets.size(),
-                 n_fsets = (uint32_t)ps.fsets.size(), n_pats = (uint32_t)ps.fpats.size();
+                 n_fsets = (uint32_t)ps.fsets.size(), n_pats = (uint32_t)ps.fpats.size(),
+                 n_chains = (uint32_t)ps.fe_chains.size();
   if (n_sets && !b.res.empty()) {
     build_pre(ps, b, &pre);
     pt = up_blocks(d->pre, pre, false);
@@ -430,9 +433,15 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
       erec.alloc(std::max<size_t>((size_t)n_pats * fh.max_el * sizeof(ErrRec8), 16), device);
       d->ferec.alloc((size_t)n_pats * b.res.size() * sizeof(ErrRec8), device);
     }
+    if (n_chains) {
+      const uint32_t* cp[2];
+      up(d->fec, {&fh.chains, &fh.chain_ents}, cp);
+      ft.chains = cp[0]; ft.chain_ents = cp[1];
+      d->feckey.alloc((size_t)n_chains * b.res.size() * sizeof(uint32_t), device);
+    }
   }
   if ((n_dsets || n_fsets) && !b.res.empty()) {
-    d->dnst.alloc((size_t)(n_dsets + n_fsets) * b.res.size(), device);
+    d->dnst.alloc((size_t)(n_dsets + n_fsets + n_chains) * b.res.size(), device);
     v.deny_st = (const uint8_t*)d->dnst.p;
   }
   d->view_dev.upload_raw(&d->view, sizeof(DevBatch), device);
@@ -443,7 +452,8 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     timed_launch(&d->fe_ms, [&]() {
       return launch_foreach(ft, v.n_res, (uint32_t*)d->feacc.p, (uint8_t*)d->dnst.p + (size_t)n_dsets * v.n_res, us,
                             n_pats ? &qt : nullptr, pdev, (const DevBatch*)d->view_dev.p, (uint2*)erec.p,
-                            (uint2*)d->ferec.p);
+                            (uint2*)d->ferec.p, (uint8_t*)d->dnst.p + (size_t)(n_dsets + n_fsets) * v.n_res,
+                            (uint32_t*)d->feckey.p);
     });
   HIPCHK(hipStreamSynchronize(us));
   for (const Timed& t : timed) {
@@ -1178,6 +1188,13 @@ struct DevSession {
                             hipMemcpyDeviceToHost, stream));
       lap("foreach_rows_d2h");
     }
+    // rules of several entries: the chain key per (chain, resource) (kvforeach.h kv_fe_chain)
+    if (want_st && !ps->ps.fe_chains.empty() && batch_ref && batch_ref->feckey.p) {
+      part->fe_ckey.alloc(ps->ps.fe_chains.size() * nres);
+      HIPCHK(hipMemcpyAsync(part->fe_ckey.data(), batch_ref->feckey.p, ps->ps.fe_chains.size() * nres * sizeof(uint32_t),
+                            hipMemcpyDeviceToHost, stream));
+      lap("foreach_chain_d2h");
+    }
     if (packed) {  // the statuses' transfer form (kv_status_pack_kernel above; the re-run leaves it)
       HIPCHK(hipMemcpyAsync(part->sflag.data(), O.sflag, part->sflag.size(), hipMemcpyDeviceToHost, stream));
       if (spack_bytes) HIPCHK(hipMemcpyAsync(part->spack.data(), s_pack.p, spack_bytes, hipMemcpyDeviceToHost, stream));
@@ -1528,9 +1545,12 @@ int kv_compile(const char* policies_json, size_t len, uint32_t flags, kv_policys
   if (!policies_json || !out) return fail(err, KV_E_INVALID, "null argument");
   if ((flags & KV_COMPILE_FOREACH_PATTERN) && !(flags & KV_COMPILE_FOREACH))
     return fail(err, KV_E_INVALID, "KV_COMPILE_FOREACH_PATTERN needs KV_COMPILE_FOREACH");
+  if ((flags & KV_COMPILE_FOREACH_ENTRIES) && !(flags & KV_COMPILE_FOREACH))
+    return fail(err, KV_E_INVALID, "KV_COMPILE_FOREACH_ENTRIES needs KV_COMPILE_FOREACH");
   return guarded(KV_E_PARSE, err, [&]() -> int {
     auto s = std::make_unique<kv_policyset>();
-    compile_policies(policies_json, len, &s->ps, flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN));
+    compile_policies(policies_json, len, &s->ps,
+                     flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN | KV_COMPILE_FOREACH_ENTRIES));
     if (flags & KV_COMPILE_SPECIALIZE) {
       s->jit = std::make_unique<JitImage>();
       jit_build(s->ps, s->jit.get());  // (kvjitbuild.cpp: generate, plan, compile, variants)

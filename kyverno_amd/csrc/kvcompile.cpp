@@ -1578,8 +1578,12 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
         const FePatternCompiler* fe_patp =
             (flags & 8u /* KV_COMPILE_FOREACH_PATTERN */) && !has_magic(rh.name) ? &fe_pat : nullptr;
         rr.route = 0;
+        // several entries (KV_COMPILE_FOREACH_ENTRIES): the rule compiles to a chain of foreach sets
+        uint32_t fe_chain = 0;
+        uint32_t* fe_chainp = (flags & 16u /* KV_COMPILE_FOREACH_ENTRIES */) ? &fe_chain : nullptr;
         if (!has_validate) { rr.route = 2; rh.route_reason = "no validate"; }
-        else if (feP && (!feD || (rh.foreach_set = compile_foreach(*ps, d, (uint32_t)fen, fe_patp)) == 0)) {
+        else if (feP && (!feD || ((rh.foreach_set = compile_foreach(*ps, d, (uint32_t)fen, fe_patp, fe_chainp)) == 0 &&
+                                  (rh.foreach_chain = fe_chain) == 0))) {
           rr.route = 1;
           rh.route_reason = "foreach";
         }
@@ -1587,7 +1591,7 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
           if (preP && (pre_set = compile_preconditions(*ps, d, (uint32_t)pre)) == 0) {
             rr.route = 1;
             rh.route_reason = "preconditions";
-            rh.foreach_set = 0;
+            rh.foreach_set = rh.foreach_chain = 0;
           }
         }
         else if (ctxP) { rr.route = 1; rh.route_reason = "context"; }
@@ -1674,6 +1678,10 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
   // foreach rules read their status from the rows of the deny plane after the deny sets'
   for (size_t i = 0; i < ps->rules.size(); i++)
     if (ps->rhost[i].foreach_set) ps->rules[i].deny = (uint32_t)ps->dsets.size() + ps->rhost[i].foreach_set;
+  // ... and the rules of several entries from the rows after the foreach sets', one per chain
+  for (size_t i = 0; i < ps->rules.size(); i++)
+    if (ps->rhost[i].foreach_chain)
+      ps->rules[i].deny = (uint32_t)(ps->dsets.size() + ps->fsets.size()) + ps->rhost[i].foreach_chain;
   // The one-element rule of evaluateList (utils.go:445-472): a list query that a field step ends
   // in a single map makes that map the one element, and the map stands at the field's own trie
   // node, not at its element node. The two nodes get the same keys, all the way down, so both map

@@ -617,11 +617,26 @@ void pattern_text(const PV& p, std::string* o) {
 }
 }  // namespace
 
-uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern) {
-  // validate.foreach: a list of exactly one entry {list, preconditions?, deny | pattern} (with
-  // several, keys of entry k-1's last element leak into entry k's `element`: kvcond.h)
-  if (d.at(node).t != J_ARR || d.at(node).count != 1) return 0;
-  const uint32_t en = d.at(node).first;
+namespace {
+// a string below `node` that may hold an `element` variable (a superset: what makes an entry's
+// strings depend on the entries before it)
+bool may_read_element(const JDoc& d, uint32_t node) {
+  const JNode& n = d.at(node);
+  if (n.t == J_STR) {
+    const std::string_view s = d.sval(n);
+    return s.find("{{") != std::string_view::npos && s.find("element") != std::string_view::npos;
+  }
+  if (n.t == J_MAP || n.t == J_ARR)
+    for (uint32_t c = n.first; c < n.first + n.count; c++)
+      if (may_read_element(d, c)) return true;
+  return false;
+}
+
+// One entry {list, preconditions?, deny | pattern} of validate.foreach, its element strings in
+// the leak context `before` (the lists of the entries in front of it; empty for the first): 1 +
+// its foreach set, 0 outside the scope (nothing is left behind)
+uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const FePatternCompiler* pattern,
+                               const std::vector<uint32_t>& before) {
   if (d.at(en).t != J_MAP) return 0;
   int64_t ln = -1, pn = -1, dn = -1, tn = -1;
   for (uint32_t c = d.at(en).first; c < d.at(en).first + d.at(en).count; c++) {
@@ -645,8 +660,17 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePa
   if (cn < 0) return 0;
   // checkpoint: an entry outside the scope leaves nothing behind
   const size_t l0 = ps.flists.size(), k0 = ps.elem.keys.size(), c0 = ps.elem.conds.size();
+  const size_t x0 = ps.fctx.size();
+  auto drop_contexts = [&]() {  // (those this entry interned, the empty one included)
+    for (; ps.fctx.size() > x0; ps.fctx.pop_back()) {
+      std::string key;
+      for (uint32_t l : ps.fctx.back()) key += std::to_string(l) + ",";
+      ps.fctx_id.erase(key);
+    }
+  };
   auto rollback = [&]() {
     ps.elem.truncate(k0, c0);
+    drop_contexts();
     if (ps.flists.size() > l0) {
       ps.flist_id.erase(ps.flists.back());
       ps.flists.pop_back();
@@ -662,16 +686,32 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePa
   }
   FeSet s;
   s.list = li->second;
+  // the leak context: that of the first entry unless a string of this one may read `element`
+  if (!before.empty() && ((pn >= 0 && may_read_element(d, (uint32_t)pn)) || (dn >= 0 && may_read_element(d, (uint32_t)dn)))) {
+    if (ps.fctx.empty()) {
+      ps.fctx.emplace_back();
+      ps.fctx_id.emplace(std::string(), 0u);
+    }
+    std::string key;
+    for (uint32_t l : before) key += std::to_string(l) + ",";
+    auto ci = ps.fctx_id.find(key);
+    if (ci == ps.fctx_id.end()) {
+      ci = ps.fctx_id.emplace(key, (uint32_t)ps.fctx.size()).first;
+      ps.fctx.push_back(before);
+    }
+    s.ctx = ci->second;
+  }
+  const std::string at = s.ctx ? "@" + std::to_string(s.ctx) : std::string();
   CondSpace sp{ps.elem, nullptr};
   sp.element = true;
   if (pn >= 0) {
     bool always = false;
-    sp.tag = "p" + std::to_string(s.list) + ":";
+    sp.tag = "p" + std::to_string(s.list) + at + ":";
     if (!compile_block(sp, d, (uint32_t)pn, &s.pre, &always)) return rollback();
     s.has_pre = !always;
     if (always) s.pre = CondSet();
   }
-  sp.tag = "d" + std::to_string(s.list) + ":";
+  sp.tag = "d" + std::to_string(s.list) + at + ":";
   std::string did;
   if (tn >= 0) {
     did = "P";
@@ -679,7 +719,13 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePa
   } else if (!compile_deny_block(sp, d, (uint32_t)cn, &s.deny, &did)) {
     return rollback();
   }
-  const std::string id = std::to_string(s.list) + "|" + (s.has_pre ? set_key(s.pre) : std::string("none")) + "|" + did;
+  // (a set that kept no string of its context reads nothing the entries before it left: the first entry's set)
+  if (s.ctx && !s.has_pre && s.deny.strs.empty()) {
+    s.ctx = 0;
+    if (ps.elem.keys.size() == k0) drop_contexts();  // (no string names the context either)
+  }
+  const std::string id = std::to_string(s.list) + (s.ctx ? "@" + std::to_string(s.ctx) : std::string()) + "|" +
+                         (s.has_pre ? set_key(s.pre) : std::string("none")) + "|" + did;
   auto it = ps.fset_id.find(id);
   // a pattern entry met for the first time: its program, rooted at the list's element
   if (tn >= 0 && it == ps.fset_id.end()) {
@@ -694,7 +740,9 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePa
     FeKey k;
     k.list = s.list;
     k.precond = t[0] == 'p';
-    k.text = t.substr(t.find(':') + 1);
+    const size_t colon = t.find(':'), ctx_at = t.find('@');
+    if (ctx_at < colon) k.ctx = (uint32_t)std::stoul(t.substr(ctx_at + 1, colon - ctx_at - 1));
+    k.text = t.substr(colon + 1);
     k.col = (uint32_t)ps.flist_keys[s.list].size();
     ps.flist_keys[s.list].push_back((uint32_t)i);
     ps.fkeys.push_back(std::move(k));
@@ -704,6 +752,86 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePa
     ps.fsets.push_back(std::move(s));
   }
   return it->second + 1;
+}
+
+// the sizes every table a foreach rule compiles into had before it, and the way back
+struct FeCheckpoint {
+  PolicySet& ps;
+  size_t prog, fix, pnodes, lists, keys, conds, fkeys, sets, pats, ctxs, paths;
+  size_t preds, alts, conjs, atoms, gsegs, gwords, strs;  // (what the programs' leaf predicates interned)
+  std::vector<size_t> list_keys;
+  std::vector<bool> path_set;
+  explicit FeCheckpoint(PolicySet& p)
+      : ps(p), prog(p.prog.size()), fix(p.slot_fix.size()), pnodes(p.pnodes.size()), lists(p.flists.size()),
+        keys(p.elem.keys.size()), conds(p.elem.conds.size()), fkeys(p.fkeys.size()), sets(p.fsets.size()),
+        pats(p.fpats.size()), ctxs(p.fctx.size()), paths(p.fchains.size()), preds(p.preds.size()), alts(p.alts.size()),
+        conjs(p.conjs.size()), atoms(p.atoms.size()), gsegs(p.gsegs.size()), gwords(p.gwords.size()), strs(p.strs.size()) {
+    for (const auto& k : p.flist_keys) list_keys.push_back(k.size());
+    for (const FeChain& c : p.fchains) path_set.push_back(!c.steps.empty());
+  }
+  template <class M>
+  static void drop_from(M& ids, size_t n0) {
+    for (auto it = ids.begin(); it != ids.end();) it = it->second >= n0 ? ids.erase(it) : std::next(it);
+  }
+  void rollback() {
+    ps.prog.resize(prog);
+    ps.slot_fix.resize(fix);
+    ps.pnodes.resize(pnodes);
+    ps.preds.resize(preds);
+    drop_from(ps.pred_cache, preds);
+    ps.alts.resize(alts);
+    ps.conjs.resize(conjs);
+    ps.atoms.resize(atoms);
+    ps.gsegs.resize(gsegs);
+    ps.gwords.resize(gwords);
+    ps.strs.resize(strs);
+    ps.elem.truncate(keys, conds);
+    ps.fkeys.resize(fkeys);
+    ps.flists.resize(lists);
+    ps.flist_keys.resize(lists);
+    for (size_t l = 0; l < lists; l++) ps.flist_keys[l].resize(list_keys[l]);
+    drop_from(ps.flist_id, lists);
+    ps.fsets.resize(sets);
+    drop_from(ps.fset_id, sets);
+    ps.fpats.resize(pats);
+    ps.fctx.resize(ctxs);
+    drop_from(ps.fctx_id, ctxs);
+    ps.fchains.resize(paths);
+    for (size_t l = 0; l < paths; l++)
+      if (!path_set[l]) ps.fchains[l] = FeChain();
+  }
+};
+}  // namespace
+
+uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern, uint32_t* chain) {
+  // validate.foreach: a list of one entry, or (chain: KV_COMPILE_FOREACH_ENTRIES) of 2 to 16, each
+  // what a single entry may be. With several, keys of entry k-1's last element leak into entry
+  // k's `element` (kvcond.h): entry k's strings are compiled in the context of the lists before it
+  if (chain) *chain = 0;
+  if (d.at(node).t != J_ARR) return 0;
+  const uint32_t count = d.at(node).count, first = d.at(node).first;
+  if (count == 1) return compile_foreach_entry(ps, d, first, pattern, {});
+  if (!chain || count < 2 || count > FE_MAX_ENTRIES) return 0;
+  FeCheckpoint ck(ps);
+  std::vector<uint32_t> sets, before;
+  std::string id;
+  for (uint32_t en = first; en < first + count; en++) {
+    const uint32_t s = compile_foreach_entry(ps, d, en, pattern, before);
+    if (!s) {
+      ck.rollback();
+      return 0;
+    }
+    sets.push_back(s - 1);
+    before.push_back(ps.fsets[s - 1].list);
+    id += std::to_string(s - 1) + ",";
+  }
+  auto it = ps.fe_chain_id.find(id);
+  if (it == ps.fe_chain_id.end()) {
+    it = ps.fe_chain_id.emplace(id, (uint32_t)ps.fe_chains.size()).first;
+    ps.fe_chains.push_back(std::move(sets));
+  }
+  *chain = it->second + 1;
+  return 0;
 }
 
 // ------------------------------------------------------------------ per batch
@@ -922,6 +1050,11 @@ void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out) {
   }
   pack_sets(ps.elem.conds, gate, key_col, &h.gate);
   pack_sets(ps.elem.conds, deny, key_col, &h.deny);
+  // the rules of several entries: per chain its entries' sets
+  for (const std::vector<uint32_t>& c : ps.fe_chains) {
+    h.chains.insert(h.chains.end(), {(uint32_t)h.chain_ents.size(), (uint32_t)c.size()});
+    h.chain_ents.insert(h.chain_ents.end(), c.begin(), c.end());
+  }
   // the pattern sets: their program and the path to their list's elements
   for (uint32_t fs : ps.fpats) {
     const FeSet& s = ps.fsets[fs];
@@ -942,6 +1075,8 @@ FeTables FeHost::view() const {
   t.n_sets = (uint32_t)(sets.size() / 4);
   t.n_lists = (uint32_t)(lists.size() / 4);
   t.max_el = max_el;
+  t.chains = chains.data(); t.chain_ents = chain_ents.data();
+  t.n_chains = (uint32_t)(chains.size() / 2);
   return t;
 }
 
@@ -962,6 +1097,36 @@ uint8_t foreach_fold_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_
     key = std::min(key, kv_fe_key(kv_foreach_elem(t, set, e), h.el_ord[el0 + e]));
   if (elem) *elem = key < FE_KEY_PASS ? key >> 3 : 0xFFFFFFFFu;
   return (uint8_t)kv_fe_final(h.lstate[(size_t)list * n_res + r], key);
+}
+
+uint8_t foreach_chain_fold_host(const FeHost& h, uint32_t chain, uint64_t n_res, uint64_t r, uint32_t* entry, uint32_t* elem,
+                                FeChainScratch* scratch) {
+  // the entry sets' rows of this resource (what kv_foreach_fin_kernel's input holds) up to the
+  // entry that ends the walk, then the lane body of kv_foreach_chain_kernel over them
+  FeChainScratch own;
+  FeChainScratch& sc = scratch ? *scratch : own;
+  const uint32_t e0 = h.chains[2 * chain], n_ent = h.chains[2 * chain + 1];
+  if (sc.acc.empty()) {  // (one resource: the rows have a stride of 1)
+    sc.acc.assign(h.sets.size() / 4, FE_KEY_NONE);
+    sc.ls.resize(h.lists.size() / 4);
+  }
+  for (size_t l = 0; l < sc.ls.size(); l++) sc.ls[l] = h.lstate[l * n_res + r];
+  for (uint32_t k = 0; k < n_ent; k++) {
+    const uint32_t s = h.chain_ents[e0 + k];
+    if (sc.ls[h.sets[4 * s]] == FE_LIST_OOS) break;  // (the walk stops here: nothing behind is read)
+    uint32_t e = 0xFFFFFFFFu;
+    const uint8_t st = foreach_fold_host(h, s, n_res, r, &e);
+    sc.acc[s] = st == ST_PASS ? FE_KEY_PASS : st == ST_SKIP ? FE_KEY_NONE : (e << 3 | st);
+    if (sc.acc[s] < FE_KEY_PASS) break;
+  }
+  FeTables t = h.view();  // (pointers only)
+  t.lstate = sc.ls.data();
+  uint32_t key = FE_KEY_NONE;
+  const uint8_t st = (uint8_t)kv_fe_chain(t, chain, 1, 0, sc.acc.data(), &key);
+  for (uint32_t k = 0; k < n_ent; k++) sc.acc[h.chain_ents[e0 + k]] = FE_KEY_NONE;
+  if (entry) *entry = key < FE_KEY_PASS ? key >> 19 : 0xFFFFFFFFu;
+  if (elem) *elem = key < FE_KEY_PASS && (key & 7u) != ST_CPU ? (key >> 3) & 0xFFFFu : 0xFFFFFFFFu;
+  return st;
 }
 
 std::string foreach_error_host(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t set, uint64_t r,

@@ -106,7 +106,8 @@ std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, u
 // first result that is neither PASS nor SKIP ends the rule; without one the rule is PASS when an
 // element passed, else SKIP "rule skipped". Scope: one entry {list, preconditions?, deny} per
 // rule (with several entries, keys of the previous entry's last element leak into `element`
-// through the merge patch), preconditions a map (the old list form is dropped by the reference),
+// through the merge patch: KV_COMPILE_FOREACH_ENTRIES, compile_foreach below, restates that),
+// preconditions a map (the old list form is dropped by the reference),
 // variables `{{element<chain>}}` / `{{request.object<chain>}}`. DESIGN.md §3 *Foreach*.
 //  * compile (compile_foreach): lists, element-scoped strings (per list and resolver mode; a
 //    string with request.object variables only is an element-scoped string too: one key space,
@@ -139,7 +140,15 @@ std::string deny_error_host(const PolicySet& ps, const Batch& b, uint32_t set, u
 // pattern node for list `list` (index `list_index`) into s->prog / s->root_pnode and records the
 // list's path (PolicySet::fchains); false: outside the scope (no instruction or set is left behind; kvcompile.cpp).
 using FePatternCompiler = std::function<bool(uint32_t pattern_node, const std::string& list, uint32_t list_index, FeSet* s)>;
-uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern = nullptr);
+// `chain` (KV_COMPILE_FOREACH_ENTRIES; null: a rule of several entries stays outside the scope): a
+// list of 2 to 16 entries, each what a single entry may be, compiles to a *chain*, the ordered
+// list of its entries' foreach sets (PolicySet::fe_chains); the return value is then 0 and
+// *chain = 1 + the interned chain. The reference's context keeps the last element of entry k
+// merged in when entry k + 1 starts (DESIGN.md §3 *Several entries*), so the element strings of an
+// entry behind the first are interned per *leak context*, the lists of the entries before it
+// (PolicySet::fctx), and resolve at ingest against the element over those lists' last elements.
+uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern = nullptr,
+                         uint32_t* chain = nullptr);
 
 struct FeHost {
   // row s of gate / deny: the entry preconditions / the deny block of foreach set s. deny holds the
@@ -149,6 +158,7 @@ struct FeHost {
   std::vector<uint32_t> first;  // [list][res]: the resource's first element in the list's block (the host
                                 // accessors; on the device only kv_foreach_rec_kernel reads it)
   std::vector<uint32_t> pats, chain;  // kvforeach.h FePatTables: the pattern sets and their lists' paths
+  std::vector<uint32_t> chains, chain_ents;  // kvforeach.h FeTables: the rules of several entries
   uint32_t max_el = 0;
   kv::FeTables view() const;
   kv::FePatTables pat_view() const;
@@ -158,6 +168,15 @@ void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out);
 // ST_SKIP or ST_CPU; *elem the deciding element's index in its list, 0xFFFFFFFF without one.
 // Throws for a pattern set (its elements are walked on the device only)
 uint8_t foreach_fold_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_t r, uint32_t* elem);
+// one (chain, store resource) on the host, as kv_foreach_chain_kernel over the rows
+// foreach_fold_host gives: the status, *entry the deciding entry (0xFFFFFFFF without one) and *elem
+// its deciding element. Throws where an entry is a pattern set
+// (`scratch`: kept by a caller that folds many resources, so nothing is allocated per resource)
+struct FeChainScratch {
+  std::vector<uint32_t> acc, ls;
+};
+uint8_t foreach_chain_fold_host(const FeHost& h, uint32_t chain, uint64_t n_res, uint64_t r, uint32_t* entry, uint32_t* elem,
+                                FeChainScratch* scratch = nullptr);
 // the error of the first unresolved deny string of element `elem` of store resource r, in the
 // order of deny_error_host
 std::string foreach_error_host(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t set, uint64_t r,

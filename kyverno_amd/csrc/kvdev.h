@@ -28,12 +28,15 @@ hipError_t launch_cond(bool strict, const CondBlocks& T, uint32_t n_res, uint32_
 // through kv_foreach_pat_kernel (kvwalk.h: the pattern walk over the policy set's and the batch's
 // device views P and B, whose node rows must be in place on `stream`), the 8-byte records of
 // their FAIL / ERROR elements into the transient erec[pattern set][T.max_el], the deciding
-// element's into fe_rec[pattern set][res].
+// element's into fe_rec[pattern set][res]. With chains (T.n_chains, KV_COMPILE_FOREACH_ENTRIES):
+// kv_foreach_chain_kernel then folds each chain's entry rows into chain_st[chain][res] (the rows of
+// the deny plane after the foreach sets') and the chain keys fe_ckey[chain][res].
 struct FeTables;
 struct FePatTables;
 hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream,
                           const FePatTables* Q = nullptr, const DevPS* P = nullptr, const DevBatch* B = nullptr,
-                          uint2* erec = nullptr, uint2* fe_rec = nullptr);
+                          uint2* erec = nullptr, uint2* fe_rec = nullptr, uint8_t* chain_st = nullptr,
+                          uint32_t* fe_ckey = nullptr);
 
 // Match tables of a pass (DevPS::mt_*): `words` = mt_ns_words + mt_ann_words +
 // mt_sel_words rows, max_entities = max(n_nsm, n_asets, n_lsets).

@@ -1,6 +1,6 @@
 // validate.foreach on the device (kvcond.h): the list states, the per-element verdict and the
-// reduction keys, shared by kv_foreach_elem_kernel / kv_foreach_pat_kernel / kv_foreach_fin_kernel
-// (kvkernel.hip) and the host fold (kvcond.cpp foreach_fold_host). Plain code over the tables of
+// reduction keys, shared by kv_foreach_elem_kernel / kv_foreach_pat_kernel / kv_foreach_fin_kernel /
+// kv_foreach_chain_kernel (kvkernel.hip) and the host fold (kvcond.cpp foreach_fold_host). Plain code over the tables of
 // kvcond.h FeHost; needs kv_layout.h and kvblocks.h.
 #pragma once
 
@@ -11,6 +11,7 @@ constexpr uint8_t FE_LIST_EMPTY = 0;  // the list query is NotFound: no element
 constexpr uint8_t FE_LIST_OK = 1;     // a list of maps (or one map), no null inside
 constexpr uint8_t FE_LIST_OOS = 2;    // anything else: the pair is ST_CPU
 constexpr uint32_t FE_MAX_ELEMS = 0x10000u;
+constexpr uint32_t FE_MAX_ENTRIES = 16u;  // entries of one rule (KV_COMPILE_FOREACH_ENTRIES)
 
 // Reduction keys of fe_acc[set][res] (atomicMin): the first decisive element of the resource's
 // list, (index in the list << 3 | its ST_ code), below the key of "some element passed", below
@@ -30,6 +31,11 @@ struct FeTables {
   const uint32_t* el_ord;  // per list block: the element's index in its list
   const uint32_t* lstate;  // [list][res]: FE_LIST_*
   uint32_t n_sets, n_lists, max_el;
+  // rules of several entries (KV_COMPILE_FOREACH_ENTRIES): a chain is the ordered list of its
+  // entries' foreach sets
+  const uint32_t* chains;      // 2 words per chain: first entry in chain_ents, entries
+  const uint32_t* chain_ents;  // one foreach set per entry
+  uint32_t n_chains;
 };
 
 // Pattern sets (KV_COMPILE_FOREACH_PATTERN, kvwalk.h): the foreach sets whose entry carries a
@@ -78,6 +84,36 @@ KV_HD inline uint32_t kv_fe_final(uint32_t lstate, uint32_t key) {
   if (key == FE_KEY_NONE) return ST_SKIP;  // no element, or every element skipped: "rule skipped"
   if (key == FE_KEY_PASS) return ST_PASS;  // applyCount > 0: "rule passed"
   return key & 7u;
+}
+
+// One (chain, resource): validateForEach over the entries in order (validation.go:204-262), from
+// the rows the entry sets' reduction left: per entry the state of its list on the resource and
+// its key fe_acc[set][res]. An out-of-scope list ends the walk with ST_CPU; the first entry with a
+// decisive element ends it with that element's code; a passing entry counts (applyCount runs
+// across the entries). Without either: ST_PASS when an entry passed, else ST_SKIP. *ckey: the
+// chain key, (entry << 19 | index in the entry's list << 3 | code) of the deciding pair (an
+// out-of-scope list: index 0), below FE_KEY_PASS, below FE_KEY_NONE. The entry count and the
+// entries' sets are the same for every lane of a launch row: the loop is uniform up to a lane's
+// early exit, and each step costs the lane one word of lstate and one of fe_acc, both coalesced.
+KV_HD inline uint32_t kv_fe_chain(const FeTables& T, uint32_t chain, uint64_t n_res, uint64_t r, const uint32_t* fe_acc,
+                                  uint32_t* ckey) {
+  const uint32_t e0 = T.chains[2u * chain], n_ent = T.chains[2u * chain + 1u];
+  bool passed = false;
+  for (uint32_t k = 0; k < n_ent; k++) {
+    const uint32_t s = T.chain_ents[e0 + k];
+    if (T.lstate[(uint64_t)T.sets[4u * s] * n_res + r] == FE_LIST_OOS) {
+      *ckey = k << 19 | ST_CPU;
+      return ST_CPU;
+    }
+    const uint32_t key = fe_acc[(uint64_t)s * n_res + r];
+    if (key < FE_KEY_PASS) {
+      *ckey = k << 19 | key;
+      return key & 7u;
+    }
+    passed |= key == FE_KEY_PASS;
+  }
+  *ckey = passed ? FE_KEY_PASS : FE_KEY_NONE;
+  return passed ? ST_PASS : ST_SKIP;
 }
 
 }  // namespace kv

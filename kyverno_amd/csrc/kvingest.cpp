@@ -734,6 +734,21 @@ struct Ingest {
     // element every string of the list resolved with `element` as a second root
     const size_t nfl = ps.flists.size();
     if (nfl && b.fout.size() != nfl) b.fout.resize(nfl);
+    // (rules of several entries: the strings of a leak context resolve against the element over the
+    // last elements of the context's lists, those in state ok with an element, the later on top)
+    const bool leak = ps.fctx.size() > 1;
+    if (leak) {
+      fe_last.assign(nfl, -1);
+      for (size_t l = 0; l < nfl; l++) {
+        fe_elems.clear();
+        if (resolve_foreach_list(ps.flists[l], d, &fe_elems) == 1 /* FE_LIST_OK */ && !fe_elems.empty())
+          fe_last[l] = fe_elems.back();
+      }
+      fe_under.assign(ps.fctx.size(), {});
+      for (size_t c = 1; c < ps.fctx.size(); c++)
+        for (uint32_t l : ps.fctx[c])
+          if (fe_last[l] >= 0) fe_under[c].push_back((uint32_t)fe_last[l]);
+    }
     for (size_t l = 0; l < nfl; l++) {
       fe_elems.clear();
       const uint8_t st = resolve_foreach_list(ps.flists[l], d, &fe_elems);
@@ -741,7 +756,9 @@ struct Ingest {
       b.fcount.push_back((uint32_t)fe_elems.size());
       for (uint32_t en : fe_elems)
         for (uint32_t k : ps.flist_keys[l]) {
-          std::string o = resolve_elem_string(ps.fkeys[k].text, d, en, ps.fkeys[k].precond);
+          const FeKey& fk = ps.fkeys[k];
+          std::string o = leak && fk.ctx ? resolve_elem_overlay(fk.text, d, en, fe_under[fk.ctx], fk.precond)
+                                         : resolve_elem_string(fk.text, d, en, fk.precond);
           auto it = b.vout_id.find(o);
           if (it == b.vout_id.end()) {
             it = b.vout_id.emplace(o, (uint32_t)b.vout_tab.size()).first;
@@ -752,6 +769,8 @@ struct Ingest {
     }
   }
   std::vector<uint32_t> fe_elems;
+  std::vector<int64_t> fe_last;                 // per list: the last element's node, -1 without one
+  std::vector<std::vector<uint32_t>> fe_under;  // per leak context: the layers under the element
 
   void take(JDoc& d) {
     if (group.size() < KV_LANES) group.resize(KV_LANES);

@@ -102,6 +102,7 @@ struct DenySet {
 struct FeKey {
   uint32_t list = 0;     // PolicySet::flists index
   uint32_t col = 0;      // its column in the list's element rows (Batch::fout[list])
+  uint32_t ctx = 0;      // its leak context (PolicySet::fctx; 0: the element alone)
   bool precond = false;
   std::string text;
 };
@@ -112,6 +113,7 @@ struct FeKey {
 // pattern node `root_pnode`) and its index among the pattern sets (`pat`, PolicySet::fpats).
 struct FeSet {
   uint32_t list = 0;
+  uint32_t ctx = 0;  // the leak context its element strings resolve in (PolicySet::fctx)
   bool has_pre = false;
   CondSet pre;
   DenySet deny;
@@ -193,6 +195,9 @@ struct RuleHost {
   std::string const_message;            // route 3
   uint32_t foreach_set = 0;             // a device foreach rule: 1 + PolicySet::fsets index (RuleRec::deny =
                                         // dsets.size() + foreach_set: a row of the deny plane)
+  uint32_t foreach_chain = 0;           // a device foreach rule of several entries (KV_COMPILE_FOREACH_ENTRIES):
+                                        // 1 + PolicySet::fe_chains index (RuleRec::deny = dsets.size() +
+                                        // fsets.size() + foreach_chain; foreach_set stays 0)
 };
 
 struct PolicySet {
@@ -268,7 +273,7 @@ struct PolicySet {
   std::unordered_map<std::string, uint32_t> dset_id;
   // validate.foreach on the device (KV_COMPILE_FOREACH, kvcond.cpp compile_foreach): the list
   // queries (text after `request.object`-rooted JMESPath), the element-scoped strings (elem.keys:
-  // the interning text of each, "<p|d><list>:" + text; fkeys: the same strings taken apart), the
+  // the interning text of each, "<p|d><list>[@<leak context>]:" + text; fkeys: the same strings taken apart), the
   // conditions over them and the foreach sets (RuleRec::deny - 1 - dsets.size()); flist_keys: the
   // strings of each list in column order
   std::vector<std::string> flists;
@@ -282,13 +287,21 @@ struct PolicySet {
   // no pattern set reads the list)
   std::vector<uint32_t> fpats;
   std::vector<FeChain> fchains;
+  // rules of several entries (KV_COMPILE_FOREACH_ENTRIES): a *chain* is the ordered list of the
+  // entries' foreach sets, interned by that list (fe_chains). The reference's JSON context keeps
+  // the last element of entry k merged in when entry k + 1 starts, so an entry's `element` strings
+  // depend on the lists before it: a *leak context* is that ordered tuple of list indices (fctx;
+  // context 0 is the empty tuple: the first entry, and every entry without an `element` string)
+  std::vector<std::vector<uint32_t>> fctx, fe_chains;
+  std::unordered_map<std::string, uint32_t> fctx_id, fe_chain_id;
   // columns of a Batch::vout row: the pattern-variable keys, then the condition strings of the
   // preconditions, then those of the deny blocks
   size_t vout_width() const { return vkeys.size() + gate.keys.size() + deny.keys.size(); }
 };
 
 // Compiles a JSON list of (already autogen-expanded) ClusterPolicy/Policy
-// objects (flags: kv_compile's KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN). Throws
+// objects (flags: kv_compile's KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN |
+// KV_COMPILE_FOREACH_ENTRIES). Throws
 // std::runtime_error on malformed input.
 void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flags = 0);
 
@@ -490,6 +503,11 @@ bool list_query_steps(const std::string& q, std::vector<ListStep>* out);
 uint8_t resolve_foreach_list(const std::string& list, const JDoc& d, std::vector<uint32_t>* elems);
 // resolve_var_string with `element` = node `elem` of d as a second variable root
 std::string resolve_elem_string(const std::string& tmpl, const JDoc& d, uint32_t elem, bool precond);
+// the same with `element` = `elem` merged over the maps `under` (the later one on top): what a
+// later entry of a foreach rule sees (kvcond.h). No merged document is built: a step descends in
+// every layer that holds the key as a map
+std::string resolve_elem_overlay(const std::string& tmpl, const JDoc& d, uint32_t elem, const std::vector<uint32_t>& under,
+                                 bool precond);
 PV outcome_value(const std::string& o);
 uint32_t compile_leaf_pred(PolicySet& tbl, const PV& value);  // kvcompile.cpp
 std::string pattern_go_v(const PV& p);                         // Go %v of a scalar pattern value

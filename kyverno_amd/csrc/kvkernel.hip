@@ -315,9 +315,29 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_rec_kernel(FeTabl
   }
 }
 
+// kv_foreach_chain_kernel (KV_COMPILE_FOREACH_ENTRIES): one lane per resource, grid.y = chains,
+// after kv_foreach_fin_kernel on the same stream. A lane walks its chain's entries in order
+// (kv_fe_chain: one coalesced word of lstate and one of fe_acc per entry; the chain's words are
+// the same for the whole workgroup) and writes the status byte to the chain's row of the deny
+// plane and the chain key to fe_ckey[chain][res]. Plain stores, no atomics, no LDS, no wave
+// operation: a lane past the last resource has nothing to wait for and leaves.
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_chain_kernel(FeTables T, uint32_t n_res,
+                                                                             const uint32_t* __restrict__ fe_acc,
+                                                                             uint8_t* __restrict__ chain_st,
+                                                                             uint32_t* __restrict__ fe_ckey) {
+  const uint64_t r = (uint64_t)blockIdx.x * KV_WG + threadIdx.x;
+  if (r >= n_res) return;
+  for (uint32_t c = blockIdx.y; c < T.n_chains; c += gridDim.y) {
+    uint32_t key;
+    chain_st[(size_t)c * n_res + r] = (uint8_t)kv_fe_chain(T, c, n_res, r, fe_acc, &key);
+    fe_ckey[(size_t)c * n_res + r] = key;
+  }
+}
+
 namespace kv {
 hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream,
-                          const FePatTables* Q, const DevPS* P, const DevBatch* B, uint2* erec, uint2* fe_rec) {
+                          const FePatTables* Q, const DevPS* P, const DevBatch* B, uint2* erec, uint2* fe_rec,
+                          uint8_t* chain_st, uint32_t* fe_ckey) {
   if (n_res == 0 || T.n_sets == 0) return hipSuccess;
   const hipError_t e = hipMemsetAsync(fe_acc, 0xFF, (size_t)T.n_sets * n_res * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
@@ -334,6 +354,10 @@ hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, u
   if (n_pats)
     hipLaunchKernelGGL(kv_foreach_rec_kernel, dim3((n_res + KV_WG - 1) / KV_WG, py), dim3(KV_WG), 0, stream, T, *Q, n_res,
                        (const uint32_t*)fe_acc, (const uint2*)erec, fe_rec);
+  if (T.n_chains && chain_st && fe_ckey)
+    hipLaunchKernelGGL(kv_foreach_chain_kernel,
+                       dim3((n_res + KV_WG - 1) / KV_WG, T.n_chains < KV_PRE_YMAX ? T.n_chains : KV_PRE_YMAX), dim3(KV_WG), 0,
+                       stream, T, n_res, (const uint32_t*)fe_acc, chain_st, fe_ckey);
   return hipGetLastError();
 }
 }  // namespace kv

@@ -4,6 +4,7 @@
 // harness (tools/kvemu) builds this file under ASan/UBSan.
 #include <emmintrin.h>
 
+#include <algorithm>
 #include <cassert>
 #include <cstring>
 #include <unordered_map>
@@ -367,14 +368,49 @@ bool is_record(uint8_t st) { return st == ST_FAIL || st == ST_ERROR || st == ST_
 // its deciding element gave: the fetched reduction key and that element's record. False for every
 // other pair (another rule, no fetched rows, a status the rule's own preconditions or match
 // decided, PASS / SKIP).
+// The fetched chain key of a pair of a rule of several entries (KV_COMPILE_FOREACH_ENTRIES;
+// kvforeach.h kv_fe_chain). False for every other rule and without fetched rows.
+bool chain_key(const Pair& q, uint32_t* key) {
+  const uint32_t ch = q.ps().rhost[q.rule].foreach_chain;
+  if (!ch || !q.part || q.part->fe_ckey.empty()) return false;
+  *key = q.part->fe_ckey[(size_t)(ch - 1) * q.part->n + q.local];
+  return true;
+}
+
+// The entry that decided a FAIL / ERROR pair of a device foreach rule: its foreach set, its
+// position among the rule's entries (0 for a rule of one entry) and, for a rule of several
+// entries, the deciding element (else 0xFFFFFFFF: the callers find it per set kind). False where
+// the fold did not decide the pair.
+bool deciding_entry(const Pair& q, uint8_t st, uint32_t* set, uint32_t* entry, uint32_t* elem) {
+  const RuleHost& rh = q.ps().rhost[q.rule];
+  *elem = 0xFFFFFFFFu;
+  if (rh.foreach_set) {
+    *set = rh.foreach_set - 1;
+    *entry = 0;
+    return q.part != nullptr;
+  }
+  uint32_t k;
+  if (!chain_key(q, &k) || k >= FE_KEY_PASS || (k & 7u) != st) return false;
+  const std::vector<uint32_t>& c = q.ps().fe_chains[rh.foreach_chain - 1];
+  if ((k >> 19) >= c.size()) return false;
+  *entry = k >> 19;
+  *set = c[*entry];
+  *elem = (k >> 3) & 0xFFFFu;
+  return true;
+}
+
 bool pattern_pair(const Pair& q, uint32_t* key, ErrRec8* rec) {
-  const uint32_t fs = q.ps().rhost[q.rule].foreach_set;
-  if (!fs || !q.part || !q.ps().fsets[fs - 1].pattern || q.part->fe_key.empty()) return false;
+  if (!q.part || q.part->fe_key.empty()) return false;
+  const RuleHost& rh = q.ps().rhost[q.rule];
+  if (!rh.foreach_set && !rh.foreach_chain) return false;
   const uint8_t st = q.status();
   if (st != ST_FAIL && st != ST_ERROR) return false;
-  const size_t at = (size_t)q.ps().fsets[fs - 1].pat * q.part->n + q.local;
+  uint32_t set, entry, elem;
+  if (!deciding_entry(q, st, &set, &entry, &elem) || !q.ps().fsets[set].pattern) return false;
+  const size_t at = (size_t)q.ps().fsets[set].pat * q.part->n + q.local;
   const uint32_t k = q.part->fe_key[at];
   if (k >= FE_KEY_PASS || (k & 7u) != st) return false;
+  if (rh.foreach_chain && (k >> 3) != elem) return false;
   *key = k;
   *rec = q.part->fe_rec[at];
   return true;
@@ -507,7 +543,8 @@ int kv_result_deny_message(const kv_result* r, uint32_t rule, uint64_t res, char
     const Pair q = pair_of(r, rule, res, false);
     if (q.code) return q.code;
     const RuleRec& rr = q.ps().rules[rule];
-    if (!rr.deny || q.ps().rhost[rule].foreach_set || !q.part || q.status() != ST_ERROR) return 0;
+    if (!rr.deny || q.ps().rhost[rule].foreach_set || q.ps().rhost[rule].foreach_chain || !q.part || q.status() != ST_ERROR)
+      return 0;
     // the error recomputed from the batch's outcome rows: the first unresolved string of the block
     const std::string e = deny_error_host(q.ps(), q.kb->b, rr.deny - 1, q.local);
     if (e.empty()) return 0;
@@ -524,6 +561,12 @@ int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, u
     if (q.code) return q.code;
     *index = 0xFFFFFFFFu;
     const uint32_t set = q.ps().rhost[rule].foreach_set;
+    if (q.ps().rhost[rule].foreach_chain) {  // several entries: the chain key fetched with the statuses
+      const uint8_t cst = q.status();
+      uint32_t s, entry, e;
+      if ((cst == ST_FAIL || cst == ST_ERROR) && deciding_entry(q, cst, &s, &entry, &e)) *index = e;
+      return 0;
+    }
     if (!set || !q.part) return 0;  // (not a device foreach rule: not reported)
     const uint8_t st = q.status();
     if (st != ST_FAIL && st != ST_ERROR) return 0;  // (PASS, SKIP: no deciding element)
@@ -539,12 +582,52 @@ int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, u
   });
 }
 
+int kv_result_foreach_entry(const kv_result* r, uint32_t rule, uint64_t res, uint32_t* entry) {
+  if (!entry) return KV_E_INVALID;
+  return guarded(KV_E_INVALID, nullptr, [&]() -> int {
+    const Pair q = pair_of(r, rule, res, false);
+    if (q.code) return q.code;
+    *entry = 0xFFFFFFFFu;
+    const RuleHost& rh = q.ps().rhost[rule];
+    if (rh.foreach_set) {  // one entry: entry 0 where an element decided
+      uint32_t e = 0xFFFFFFFFu;
+      const int rc = kv_result_foreach_element(r, rule, res, &e);
+      if (rc == 0 && e != 0xFFFFFFFFu) *entry = 0;
+      return rc;
+    }
+    if (!rh.foreach_chain) return 0;
+    const uint8_t st = q.status();
+    uint32_t s, k, e;
+    if ((st == ST_FAIL || st == ST_ERROR) && deciding_entry(q, st, &s, &k, &e)) *entry = k;
+    return 0;
+  });
+}
+
 int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
   return guarded(KV_E_INVALID, nullptr, [&]() -> int {
     const Pair q = pair_of(r, rule, res, false);
     if (q.code) return q.code;
     const PolicySet& ps = q.ps();
     const uint32_t fs = ps.rhost[rule].foreach_set;
+    if (ps.rhost[rule].foreach_chain) {
+      // several entries: the chain key tells what the fold decided. An ERROR is the deciding deny
+      // entry's first unresolved string, resolved under its leak context; a pattern entry's is its
+      // element's pattern error (kv_result_foreach_error_message)
+      const uint8_t cst = q.status();
+      uint32_t key;
+      if ((cst != ST_ERROR && cst != ST_SKIP) || !chain_key(q, &key)) return 0;
+      if (cst == ST_SKIP) {
+        const RuleRec& rr = ps.rules[rule];
+        if (rr.pre && pre_status_host(q.kb->pre_host(ps), rr.pre - 1, q.n_local(), q.local) == ST_SKIP) return 0;
+        return key == FE_KEY_NONE ? put_message("rule skipped", buf, cap) : 0;
+      }
+      uint32_t s, entry, e;
+      if (!deciding_entry(q, cst, &s, &entry, &e) || ps.fsets[s].pattern) return 0;
+      const std::string err = foreach_error_host(ps, q.kb->b, q.kb->fe_host(ps), s, q.local, e);
+      if (err.empty()) return 0;
+      return put_message("validation failed in foreach rule for failed to substitute variables in deny conditions: " + err,
+                         buf, cap);
+    }
     if (!fs || !q.part) return 0;
     const uint8_t st = q.status();
     if (st != ST_ERROR && st != ST_SKIP) return 0;
@@ -629,7 +712,7 @@ int kv_batch_deny_fold(const kv_policyset* ps, const kv_batch* b, uint32_t set, 
 int kv_rule_deny_set(const kv_policyset* ps, uint32_t rule, uint32_t* set) {
   if (!ps || !set) return KV_E_INVALID;
   if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
-  *set = ps->ps.rhost[rule].foreach_set ? 0u : ps->ps.rules[rule].deny;
+  *set = ps->ps.rhost[rule].foreach_set || ps->ps.rhost[rule].foreach_chain ? 0u : ps->ps.rules[rule].deny;
   return 0;
 }
 
@@ -676,6 +759,105 @@ int kv_batch_foreach_fold(const kv_policyset* ps, const kv_batch* b, uint32_t se
     }
     return 0;
   });
+}
+
+int kv_policyset_foreach_chains(const kv_policyset* ps, uint32_t* chains) {
+  if (!ps || !chains) return KV_E_INVALID;
+  *chains = (uint32_t)ps->ps.fe_chains.size();
+  return 0;
+}
+
+int kv_rule_foreach_chain(const kv_policyset* ps, uint32_t rule, uint32_t* chain_plus_1, uint32_t* n_entries) {
+  if (!ps || !chain_plus_1) return KV_E_INVALID;
+  if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
+  const uint32_t ch = ps->ps.rhost[rule].foreach_chain;
+  *chain_plus_1 = ch;
+  if (n_entries) *n_entries = ch ? (uint32_t)ps->ps.fe_chains[ch - 1].size() : 0u;
+  return 0;
+}
+
+int kv_chain_entry_set(const kv_policyset* ps, uint32_t chain, uint32_t k, uint32_t* set) {
+  if (!ps || !set) return KV_E_INVALID;
+  if (chain >= ps->ps.fe_chains.size() || k >= ps->ps.fe_chains[chain].size()) return KV_E_RANGE;
+  *set = ps->ps.fe_chains[chain][k];
+  return 0;
+}
+
+int kv_batch_foreach_chain_fold(const kv_policyset* ps, const kv_batch* b, uint32_t chain, uint8_t* status, uint32_t* entry,
+                                uint32_t* elem, uint64_t n) {
+  if (!ps || !b || !status) return KV_E_INVALID;
+  if (chain >= ps->ps.fe_chains.size() || n != b->b.res.size()) return KV_E_RANGE;
+  for (uint32_t s : ps->ps.fe_chains[chain])
+    if (ps->ps.fsets[s].pattern) return KV_E_INVALID;  // (a pattern set has no host evaluator)
+  return guarded(KV_E_INVALID, nullptr, [&]() -> int {
+    FeHost h;
+    build_foreach(ps->ps, b->b, &h);
+    FeChainScratch scratch;
+    const std::vector<uint32_t>& order = b->b.order;  // store index -> caller index (empty: identity)
+    for (uint64_t s = 0; s < n; s++) {
+      uint32_t k = 0xFFFFFFFFu, e = 0xFFFFFFFFu;
+      const uint64_t i = order.empty() ? s : order[s];
+      status[i] = foreach_chain_fold_host(h, chain, n, s, &k, &e, &scratch);
+      if (entry) entry[i] = k;
+      if (elem) elem[i] = e;
+    }
+    return 0;
+  });
+}
+
+int kv_batch_foreach_chain_message(const kv_policyset* ps, const kv_batch* b, uint32_t chain, uint64_t res, char* buf,
+                                   size_t cap) {
+  if (!ps || !b) return KV_E_INVALID;
+  if (chain >= ps->ps.fe_chains.size() || res >= b->b.res.size()) return KV_E_RANGE;
+  for (uint32_t s : ps->ps.fe_chains[chain])
+    if (ps->ps.fsets[s].pattern) return KV_E_INVALID;
+  return guarded(KV_E_INVALID, nullptr, [&]() -> int {
+    const FeHost& h = const_cast<kv_batch*>(b)->fe_host(ps->ps);
+    const std::vector<uint32_t>& order = b->b.order;  // store index -> caller index (empty: identity)
+    uint64_t s = res;
+    if (!order.empty()) s = (uint64_t)(std::find(order.begin(), order.end(), (uint32_t)res) - order.begin());
+    uint32_t k = 0xFFFFFFFFu, e = 0xFFFFFFFFu;
+    const uint8_t st = foreach_chain_fold_host(h, chain, b->b.res.size(), s, &k, &e);
+    if (st == ST_SKIP) return put_message("rule skipped", buf, cap);  // (validation.go:279-281)
+    if (st != ST_ERROR) return 0;
+    const std::string err = foreach_error_host(ps->ps, b->b, h, ps->ps.fe_chains[chain][k], s, e);
+    if (err.empty()) return 0;
+    return put_message("validation failed in foreach rule for failed to substitute variables in deny conditions: " + err,
+                       buf, cap);
+  });
+}
+
+int kv_batch_foreach_tables(const kv_policyset* ps, const kv_batch* b, char** out, size_t* len) {
+  if (!ps || !b || !out || !len) return KV_E_INVALID;
+  return guarded(KV_E_INVALID, nullptr, [&]() -> int {
+    FeHost h;
+    build_foreach(ps->ps, b->b, &h);
+    std::string o;
+    auto put = [&](const std::vector<uint32_t>& v) {
+      const uint64_t n = v.size();
+      o.append((const char*)&n, 8);
+      o.append((const char*)v.data(), n * 4);
+    };
+    for (const std::vector<uint32_t>* v :
+         {&h.sets, &h.lists, &h.el_res, &h.el_ord, &h.lstate, &h.first, &h.pats, &h.chain, &h.chains, &h.chain_ents,
+          &h.gate.sets, &h.gate.ents, &h.deny.sets, &h.deny.ents, &h.deny.outc, &h.deny.truth, &h.deny.unk, &h.deny.err,
+          &h.deny.oos})
+      put(*v);
+    put({h.deny.words, h.max_el});
+    char* p = (char*)malloc(std::max<size_t>(o.size(), 1));
+    if (!p) return KV_E_NOMEM;
+    memcpy(p, o.data(), o.size());
+    *out = p;
+    *len = o.size();
+    return 0;
+  });
+}
+
+int kv_foreach_set_pattern(const kv_policyset* ps, uint32_t set, uint32_t* on) {
+  if (!ps || !on) return KV_E_INVALID;
+  if (set >= ps->ps.fsets.size()) return KV_E_RANGE;
+  *on = ps->ps.fsets[set].pattern ? 1u : 0u;
+  return 0;
 }
 
 int kv_policyset_cond_sets(const kv_policyset* ps, uint32_t* sets, uint32_t* conditions, uint32_t* strings) {

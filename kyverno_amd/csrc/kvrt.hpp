@@ -176,6 +176,9 @@ struct ResultPart {
   // code) and the deciding element's 8-byte record
   HostArray<uint32_t> fe_key;
   HostArray<ErrRec8> fe_rec;
+  // Rules of several entries (KV_COMPILE_FOREACH_ENTRIES; fetched with the statuses), in store
+  // order: [chain][n] the chain key (kvforeach.h kv_fe_chain: the deciding entry, element and code)
+  HostArray<uint32_t> fe_ckey;
   // statuses [lo, lo + n) of rule `rule` from the transfer form into dst[0, n)
   void unpack_row(uint32_t rule, uint8_t* dst) const;
   uint64_t n_rec() const { return base.empty() ? 0 : base.back(); }

@@ -298,6 +298,77 @@ void json_value(std::string& o, const JDoc& d, int64_t node) {
   }
 }
 
+// The overlay of a later foreach entry (kvcond.h): `layers` are maps of d, the top one first,
+// standing for their JSON merge (two maps merge key by key, anything else replaces what was
+// there). One field step: the layers of the merged value of `key`. It descends in every layer
+// that holds the key as a map and stops at the first one, top first, where the key holds anything
+// else: that value wins when no layer above has the key, and is replaced by the maps above it
+// otherwise. Empty: no layer has the key.
+std::vector<uint32_t> overlay_field(const JDoc& d, const std::vector<uint32_t>& layers, std::string_view key) {
+  std::vector<uint32_t> next;
+  for (uint32_t l : layers) {
+    const JNode& n = d.at(l);
+    int64_t hit = -1;
+    for (uint32_t c = n.first; c < n.first + n.count; c++)
+      if (d.key(d.at(c)) == key) hit = c;  // (the last of duplicate keys)
+    if (hit < 0) continue;
+    if (d.at((uint32_t)hit).t != J_MAP) {
+      if (next.empty()) next.push_back((uint32_t)hit);
+      break;
+    }
+    next.push_back((uint32_t)hit);
+  }
+  return next;
+}
+
+// query_doc over an overlay whose root layers (all maps) are `layers`: 0 found (*out: one node, or
+// several maps to be read as their merge; empty for null), 1 unknown key (*missing)
+int query_overlay(const std::vector<QStep>& steps, const JDoc& d, std::vector<uint32_t> layers, std::vector<uint32_t>* out,
+                  std::string* missing) {
+  for (const QStep& s : steps) {
+    if (layers.empty()) continue;  // null: every further step is null
+    const JNode& n = d.at(layers[0]);
+    if (s.index) {  // (several layers are maps: an index of a non-array is null)
+      if (layers.size() != 1 || n.t != J_ARR) { layers.clear(); continue; }
+      long i = s.idx;
+      if (i < 0) i += (long)n.count;
+      if (i >= 0 && i < (long)n.count) layers.assign(1, n.first + (uint32_t)i);
+      else layers.clear();
+    } else {
+      if (n.t != J_MAP) { layers.clear(); continue; }
+      layers = overlay_field(d, layers, s.key);
+      if (layers.empty()) {
+        *missing = s.key;
+        return 1;
+      }
+    }
+  }
+  if (layers.size() == 1 && d.at(layers[0]).t == J_NULL) layers.clear();
+  *out = std::move(layers);
+  return 0;
+}
+
+// json_value of the merge of the maps `layers` (top first), keys sorted
+void json_value_overlay(std::string& o, const JDoc& d, const std::vector<uint32_t>& layers) {
+  std::vector<std::string_view> keys;
+  for (uint32_t l : layers) {
+    const JNode& n = d.at(l);
+    for (uint32_t c = n.first; c < n.first + n.count; c++) keys.push_back(d.key(d.at(c)));
+  }
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  o += '{';
+  for (size_t k = 0; k < keys.size(); k++) {
+    if (k) o += ',';
+    json_str(o, keys[k]);
+    o += ':';
+    const std::vector<uint32_t> sub = overlay_field(d, layers, keys[k]);
+    if (sub.size() == 1) json_value(o, d, sub[0]);
+    else json_value_overlay(o, d, sub);
+  }
+  o += '}';
+}
+
 }  // namespace
 
 bool var_string(const std::string& s) { return !find_vars(s).empty(); }
@@ -398,7 +469,8 @@ std::string unescape_var_string(const std::string& s) {
 // "F" + 8 raw bytes of a float64, "B0" / "B1", "N" (null), "E" + the error text, "C" (outside
 // the device scope), "M" (a map or array: a structural pattern, outside the scope).
 namespace {
-std::string resolve_impl(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond, int64_t elem);
+std::string resolve_impl(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond, int64_t elem,
+                         const std::vector<uint32_t>* under = nullptr);
 }
 std::string resolve_var_string(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond) {
   return resolve_impl(tmpl, path, d, precond, -1);
@@ -406,9 +478,15 @@ std::string resolve_var_string(const std::string& tmpl, const std::string& path,
 std::string resolve_elem_string(const std::string& tmpl, const JDoc& d, uint32_t elem, bool precond) {
   return resolve_impl(tmpl, "", d, precond, (int64_t)elem);
 }
+std::string resolve_elem_overlay(const std::string& tmpl, const JDoc& d, uint32_t elem, const std::vector<uint32_t>& under,
+                                 bool precond) {
+  return resolve_impl(tmpl, "", d, precond, (int64_t)elem, under.empty() ? nullptr : &under);
+}
 namespace {
-// elem >= 0: a variable whose query starts at `element` resolves against node `elem` of d
-std::string resolve_impl(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond, int64_t elem) {
+// elem >= 0: a variable whose query starts at `element` resolves against node `elem` of d, merged
+// over the maps *under (the last one on top) where there are any
+std::string resolve_impl(const std::string& tmpl, const std::string& path, const JDoc& d, bool precond, int64_t elem,
+                         const std::vector<uint32_t>* under) {
   std::string value = tmpl;
   std::vector<QStep> steps;
   auto vars = find_vars(value);
@@ -429,12 +507,26 @@ std::string resolve_impl(const std::string& tmpl, const std::string& path, const
       int64_t node = -1;
       std::string missing;
       bool unresolved = false;
-      if (query_doc(steps, d, &node, &missing, el ? elem : -1) == 1) {
+      std::vector<uint32_t> merged;  // (an overlay query that ends in several maps: their merge)
+      int found;
+      if (el && under) {
+        std::vector<uint32_t> layers(1, (uint32_t)elem);
+        layers.insert(layers.end(), under->rbegin(), under->rend());
+        found = query_overlay(steps, d, std::move(layers), &merged, &missing);
+        if (found == 0) {
+          node = merged.size() == 1 ? (int64_t)merged[0] : -1;
+          if (merged.size() < 2) merged.clear();
+        }
+      } else {
+        found = query_doc(steps, d, &node, &missing, el ? elem : -1);
+      }
+      if (found == 1) {
         if (!precond) return "EUnknown key \"" + missing + "\" in path";
         unresolved = true;  // newPreconditionsVariableResolver (vars.go:62-74): the value is ""
       }
       if (original == v) {  // the whole string: the value itself
         if (unresolved) return "S";
+        if (!merged.empty()) return "M";
         if (node < 0) return "N";
         const JNode& n = d.at((uint32_t)node);
         switch (n.t) {
@@ -453,6 +545,7 @@ std::string resolve_impl(const std::string& tmpl, const std::string& path, const
       const std::string prefix = initial ? "" : old.substr(0, 1);
       std::string sub;
       if (unresolved) sub.clear();
+      else if (!merged.empty()) json_value_overlay(sub, d, merged);
       else if (node >= 0 && d.at((uint32_t)node).t == J_STR) sub = std::string(d.sval(d.at((uint32_t)node)));
       else json_value(sub, d, node);
       value = replace_first(original, prefix + v, prefix + sub);

@@ -223,6 +223,23 @@ def c2_foreach_pattern_policies() -> list[dict]:
     return pols
 
 
+def c2_foreach_chain_policies() -> list[dict]:
+    """The chain twin of ``c2_foreach_policies``: the same 100 rules with each rule's entry doubled
+    into a ``containers`` entry and an ``initContainers`` entry with the same ``deny`` block (rule i:
+    block i mod 8), to be compiled with ``PolicySet(..., foreach=True, foreach_entries=True)``: the
+    workload of the chain kernel's measurement (DESIGN.md §3 *Several entries*)."""
+    import copy
+
+    pols = c2_policies()
+    for i, r in enumerate(pols[0]["spec"]["rules"]):
+        block = C2_FOREACH_SETS[i % len(C2_FOREACH_SETS)]
+        r["validate"] = {"message": r["validate"].get("message", ""),
+                         "foreach": [{"list": "request.object.spec." + lst, "deny": {"conditions": copy.deepcopy(block)}}
+                                     for lst in ("containers", "initContainers")]}
+    pols[0]["metadata"]["name"] = "c2-pod-rules-foreach-chain"
+    return pols
+
+
 C3_KIND_MIX = 2  # kv_synth stream of C3: Pods/Deployments/Services 60/25/15 over 1 000 namespaces
 C3_NAMESPACES = 1000
 

@@ -102,7 +102,7 @@ int main(int argc, char** argv) {
     std::string ctx = strcmp(argv[3], "-") ? slurp(argv[3]) : std::string();
     PolicySet ps;
     // KVEMU_COMPILE_FLAGS: kv_compile's flags (2: KV_COMPILE_DENY, 4: KV_COMPILE_FOREACH, 8:
-    // KV_COMPILE_FOREACH_PATTERN), as the binary's source was generated
+    // KV_COMPILE_FOREACH_PATTERN, 16: KV_COMPILE_FOREACH_ENTRIES), as the binary's source was generated
     compile_policies(pol.data(), pol.size(), &ps, getenv("KVEMU_COMPILE_FLAGS") ? (uint32_t)atoi(getenv("KVEMU_COMPILE_FLAGS")) : 0u);
     Batch whole;
     ingest_resources(ps, res.data(), res.size(), nullptr, &whole);
@@ -231,11 +231,12 @@ int main(int argc, char** argv) {
     B.dyn_st = dyn.dyn_st.data();
     // condition blocks (as dev_batch): the tables, then every (set, resource) through the host
     // twins of kv_precond_kernel, kv_deny_kernel and the foreach kernels (kvcond.h: the per-lane
-    // functions the kernels run); the deny plane has the deny sets' rows, then the foreach sets'
+    // functions the kernels run); the deny plane has the deny sets' rows, then the foreach sets',
+    // then the chains' (rules of several entries)
     CondHost pre, dn;
     FeHost fe;
     std::vector<uint8_t> pre_st, deny_st;
-    const size_t n_pre = ps.csets.size(), n_dn = ps.dsets.size(), n_fe = ps.fsets.size();
+    const size_t n_pre = ps.csets.size(), n_dn = ps.dsets.size(), n_fe = ps.fsets.size(), n_ch = ps.fe_chains.size();
     if (n_pre && !b.res.empty()) {
       build_pre(ps, b, &pre);
       pre_st.assign(n_pre * B.n_res, 0xEE);
@@ -246,7 +247,7 @@ int main(int argc, char** argv) {
     if ((n_dn || n_fe) && !b.res.empty()) {
       build_deny(ps, b, &dn);
       build_foreach(ps, b, &fe);
-      deny_st.assign((n_dn + n_fe) * B.n_res, 0xEE);
+      deny_st.assign((n_dn + n_fe + n_ch) * B.n_res, 0xEE);
       for (size_t s = 0; s < n_dn; s++)
         for (uint32_t r = 0; r < B.n_res; r++) deny_st[s * B.n_res + r] = deny_status_host(dn, (uint32_t)s, B.n_res, r);
       for (size_t s = 0; s < n_fe; s++)
@@ -256,6 +257,19 @@ int main(int argc, char** argv) {
         const FeTables ft = fe.view();
         const FePatTables qt = fe.pat_view();
         kvemu_foreach_pat(&ft, &qt, &P, &B, B.n_res, deny_st.data() + n_dn * B.n_res);
+      }
+      if (n_ch) {  // (as kv_foreach_chain_kernel, after the set rows: a key per status byte, the element left out)
+        std::vector<uint32_t> acc(n_fe * B.n_res);
+        for (size_t i = 0; i < acc.size(); i++) {
+          const uint8_t st = deny_st[n_dn * B.n_res + i];
+          acc[i] = st == ST_PASS ? FE_KEY_PASS : st == ST_SKIP ? FE_KEY_NONE : st;
+        }
+        const FeTables ft = fe.view();
+        for (size_t c = 0; c < n_ch; c++)
+          for (uint32_t r = 0; r < B.n_res; r++) {
+            uint32_t key;
+            deny_st[(n_dn + n_fe + c) * B.n_res + r] = (uint8_t)kv_fe_chain(ft, (uint32_t)c, B.n_res, r, acc.data(), &key);
+          }
       }
       B.deny_st = deny_st.data();
     }
