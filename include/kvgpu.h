@@ -90,7 +90,20 @@ enum {
    * the {{element...}} variables of a later entry's preconditions, deny conditions and message read
    * the element merged over the last elements of the lists before it (maps merge key by key,
    * anything else replaces); an entry's pattern sees the raw element. */
-  KV_COMPILE_FOREACH_ENTRIES = 16
+  KV_COMPILE_FOREACH_ENTRIES = 16,
+  /* also evaluate validate.foreach entries that carry an `anyPattern` on the device (opt-in; needs
+   * KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN, else kv_compile returns KV_E_INVALID;
+   * composes with KV_COMPILE_FOREACH_ENTRIES; without it such a rule is KV_ROUTE_CPU, reason
+   * "foreach"). In scope: an entry {list, preconditions?, anyPattern}, anyPattern a list of 1 to 8
+   * maps, each within the limits of a pattern entry, no $() reference anywhere in the list (the
+   * reference resolves those against the list as a whole). Per element the alternatives are tried in
+   * order as MatchPattern(element, alternative): the first that matches makes the element PASS,
+   * none makes it FAIL (never SKIP or ERROR); the rule verdict is the foreach reduction. For the
+   * deciding element of a FAIL pair every alternative's outcome is kept
+   * (kv_result_foreach_alt). An element is CPU where an alternative up to and including the
+   * first that passes meets the typing guard of pattern entries or a record that does not fit
+   * 8 bytes. */
+  KV_COMPILE_FOREACH_ANYPATTERN = 32
 };
 
 /* kv_validate modes (bit set). KV_MODE_SCOPES adds per-scope counts
@@ -342,6 +355,28 @@ int kv_result_foreach_entry(const kv_result* r, uint32_t rule, uint64_t res, uin
 int kv_result_foreach_path(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
 int kv_result_foreach_error_message(const kv_result* r, uint32_t rule, uint64_t res, const char* element_json, size_t len,
                                     char* buf, size_t cap);
+/* anyPattern entries (KV_COMPILE_FOREACH_ANYPATTERN). kv_rule_foreach_anypattern: *n_alts = the
+ * alternative count of a device foreach rule whose one entry carries an anyPattern, 0 for every
+ * other rule (kv_rule_foreach_pattern is 0 for it). kv_foreach_set_alternatives: the same for
+ * foreach set `set` (0-based; the entries of a chain), 0 for a set that is no any set. A result
+ * fetched with statuses carries, per (any set, resource), the reduction key, a code word (4 bits
+ * per alternative: its status on the deciding element) and one 8-byte record per alternative.
+ * kv_result_foreach_alt: for a FAIL pair decided by an anyPattern entry, *status = the status of
+ * alternative `alt` on the deciding element (the FAIL, ERROR or SKIP status code) and, for FAIL, its
+ * failing path relative to the element in buf; returns the path's length (0 without one),
+ * KV_E_INVALID for any other pair, KV_E_RANGE for an alternative the set does not have.
+ * kv_result_foreach_alt_error_message: err.Error() of that alternative's PatternError, formatted
+ * from `element_json` with float64 typing as kv_result_foreach_error_message. The caller composes
+ * buildAnyPatternErrorMessage: per alternative "Rule <name>[<alt>] failed at path <path>." where
+ * the path is not empty, else "Rule <name>[<alt>] failed: <error>." (INTEGRATION.md).
+ * kv_result_foreach_path and kv_result_foreach_error_message are KV_E_INVALID for such a pair, and
+ * kv_result_failures keeps KV_PATH_NONE. */
+int kv_rule_foreach_anypattern(const kv_policyset* ps, uint32_t rule, uint32_t* n_alts);
+int kv_foreach_set_alternatives(const kv_policyset* ps, uint32_t set, uint32_t* n);
+int kv_result_foreach_alt(const kv_result* r, uint32_t rule, uint64_t res, uint32_t alt, uint32_t* status, char* buf,
+                          size_t cap);
+int kv_result_foreach_alt_error_message(const kv_result* r, uint32_t rule, uint64_t res, uint32_t alt,
+                                        const char* element_json, size_t len, char* buf, size_t cap);
 double kv_result_kernel_ms(const kv_result* r);
 
 /* Bulk export of the failing pairs (KV_MODE_ERRORS): every FAIL / ERROR / SKIP pair,

@@ -44,6 +44,7 @@ STATUS_NAMES = ["pass", "fail", "warn", "error", "skip", "nomatch", "cpu"]
 MODE_STATUS, MODE_ERRORS, MODE_COUNTS, MODE_SCOPES = 1, 2, 4, 8
 COMPILE_SPECIALIZE, COMPILE_DENY, COMPILE_FOREACH, COMPILE_FOREACH_PATTERN = 1, 2, 4, 8
 COMPILE_FOREACH_ENTRIES = 16
+COMPILE_FOREACH_ANYPATTERN = 32
 ROUTE_GPU, ROUTE_CPU, ROUTE_NORESPONSE, ROUTE_CONSTANT = range(4)
 
 
@@ -83,6 +84,7 @@ class Rule:
     foreach: bool = False  # a validate.foreach rule evaluated on the device (PolicySet(foreach=True))
     foreach_pattern: bool = False  # ... whose entry carries a pattern (PolicySet(foreach_pattern=True))
     foreach_entries: int = 0  # ... of several entries: their number (PolicySet(foreach_entries=True)), else 0
+    foreach_anypattern: int = 0  # ... whose one entry carries an anyPattern: its alternatives (PolicySet(foreach_anypattern=True))
 
 
 class PolicySet:
@@ -111,17 +113,24 @@ class PolicySet:
     rules of 2 to 16 entries, each of the forms above, to the GPU. As in the reference, the
     ``{{element...}}`` variables of a later entry read the element merged over the last elements of
     the lists before it. Without it such a rule stays CPU-routed, reason ``"foreach"``.
+
+    ``foreach_anypattern=True`` (``KV_COMPILE_FOREACH_ANYPATTERN``, opt-in, needs ``foreach`` and
+    ``foreach_pattern``) also routes entries ``{list, preconditions?, anyPattern}`` to the GPU:
+    ``anyPattern`` a list of 1 to 8 maps, each within the limits of a pattern entry. An element
+    passes when one alternative matches; ``Result.foreach_alt`` gives every alternative's outcome on
+    the deciding element of a FAIL pair. Without it such a rule stays CPU-routed, reason ``"foreach"``.
     """
 
     def __init__(self, policies, specialize: bool = False, deny: bool = False, foreach: bool = False,
-                 foreach_pattern: bool = False, foreach_entries: bool = False):
+                 foreach_pattern: bool = False, foreach_entries: bool = False, foreach_anypattern: bool = False):
         L = lib()
         data = _dumps(policies)
         h = ctypes.c_void_p()
         err = new_err()
         flags = ((COMPILE_SPECIALIZE if specialize else 0) | (COMPILE_DENY if deny else 0)
                  | (COMPILE_FOREACH if foreach else 0) | (COMPILE_FOREACH_PATTERN if foreach_pattern else 0)
-                 | (COMPILE_FOREACH_ENTRIES if foreach_entries else 0))
+                 | (COMPILE_FOREACH_ENTRIES if foreach_entries else 0)
+                 | (COMPILE_FOREACH_ANYPATTERN if foreach_anypattern else 0))
         check(L.kv_compile(data, len(data), flags, ctypes.byref(h), ctypes.byref(err)), err)
         self._h = h
         self.specialize = specialize
@@ -129,6 +138,7 @@ class PolicySet:
         self.foreach = foreach
         self.foreach_pattern = foreach_pattern
         self.foreach_entries = foreach_entries
+        self.foreach_anypattern = foreach_anypattern
         np_, nr = ctypes.c_uint32(), ctypes.c_uint32()
         L.kv_policyset_info(h, ctypes.byref(np_), ctypes.byref(nr))
         self.n_policies, self.n_rules = np_.value, nr.value
@@ -146,6 +156,8 @@ class PolicySet:
             on = ctypes.c_uint32()
             L.kv_rule_foreach_pattern(h, i, ctypes.byref(on))
             self.rules[-1].foreach_pattern = on.value != 0
+            L.kv_rule_foreach_anypattern(h, i, ctypes.byref(on))
+            self.rules[-1].foreach_anypattern = on.value
             ch, ne = ctypes.c_uint32(), ctypes.c_uint32()
             L.kv_rule_foreach_chain(h, i, ctypes.byref(ch), ctypes.byref(ne))
             if ch.value:  # (kv_rule_info.foreach_set stays 0 for a rule of several entries)
@@ -233,7 +245,9 @@ class PolicySet:
         for s in range(n_sets):
             on = ctypes.c_uint32()
             lib().kv_foreach_set_pattern(self._h, s, ctypes.byref(on))
-            if on.value:  # (a pattern set, of a rule of one entry or of several)
+            na = ctypes.c_uint32()
+            lib().kv_foreach_set_alternatives(self._h, s, ctypes.byref(na))
+            if on.value or na.value:  # (a pattern set or any set, of a rule of one entry or of several)
                 st[s] = 255
                 continue
             rc = lib().kv_batch_foreach_fold(self._h, b._h, s, st[s].ctypes.data, el[s].ctypes.data, b.n_res)
@@ -499,6 +513,31 @@ class Result:
             doc = doc.encode("utf-8")
         return self._text(lib().kv_result_foreach_error_message, rule, res, doc, len(doc), errors="replace",
                           empty_ok=True)
+
+    def foreach_alt(self, rule: int, res: int, alt: int) -> tuple[int, str | None] | None:
+        """Alternative ``alt`` of the anyPattern entry that decided a FAIL pair of a device foreach
+        rule, on the deciding element (``kv_result_foreach_alt``): (its status FAIL / ERROR / SKIP,
+        the failing path relative to the element for FAIL, else None); None for any other pair."""
+        st = ctypes.c_uint32()
+        cap = 256
+        while True:
+            buf = ctypes.create_string_buffer(cap)
+            n = lib().kv_result_foreach_alt(self._h, rule, res, alt, ctypes.byref(st), buf, cap)
+            if n < 0:
+                return None
+            if n < cap:
+                return st.value, (buf.raw[:n].decode("utf-8") if st.value == FAIL else None)
+            cap = n + 1
+
+    def foreach_alt_error_message(self, rule: int, res: int, alt: int, element) -> str | None:
+        """err.Error() of the PatternError of alternative ``alt`` (``foreach_alt``) on the deciding
+        element (``kv_result_foreach_alt_error_message``), else None. ``element`` as for
+        ``foreach_error_message``."""
+        doc = element if isinstance(element, (bytes, str)) else _dumps(element)
+        if isinstance(doc, str):
+            doc = doc.encode("utf-8")
+        return self._text(lambda h, ru, re_, *a: lib().kv_result_foreach_alt_error_message(h, ru, re_, alt, *a), rule, res,
+                          doc, len(doc), errors="replace", empty_ok=True)
 
     def subst_error(self, rule: int, res: int) -> str | None:
         """The RuleResponse message of an ERROR pair caused by the pattern's variables failing to

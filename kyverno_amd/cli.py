@@ -29,10 +29,12 @@ whose conditions are of those forms on the device, with the messages of ``valida
 ``--device-foreach-pattern`` (``evaluate(foreach_pattern=True)``, ``KV_COMPILE_FOREACH_PATTERN``; implies
 ``--device-foreach``) also for entries that carry a ``pattern``; ``--device-foreach-entries``
 (``evaluate(foreach_entries=True)``, ``KV_COMPILE_FOREACH_ENTRIES``; implies ``--device-foreach``) also for
-rules of several entries.
+rules of several entries; ``--device-foreach-anypattern`` (``evaluate(foreach_anypattern=True)``,
+``KV_COMPILE_FOREACH_ANYPATTERN``; implies ``--device-foreach-pattern`` and ``--device-foreach``) also for
+entries that carry an ``anyPattern``, with the message of ``buildAnyPatternErrorMessage``.
 
     python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N] [--device-deny] [--device-foreach]
-        [--device-foreach-pattern] [--device-foreach-entries]
+        [--device-foreach-pattern] [--device-foreach-entries] [--device-foreach-anypattern]
     python -m kyverno_amd test test/cli/test/simple
 """
 from __future__ import annotations
@@ -118,6 +120,7 @@ class Evaluation:
     foreach_entry: dict = field(default_factory=dict)  # (rule, res) -> the deciding entry (rules of several entries)
     foreach_path: dict = field(default_factory=dict)  # (rule, res) -> failing path in the deciding element (pattern entries)
     foreach_err: dict = field(default_factory=dict)   # (rule, res) -> pattern error of the deciding element (pattern entries, ERROR)
+    foreach_alts: dict = field(default_factory=dict)  # (rule, res) -> [(status, path, error text)] per alternative (anyPattern entries, FAIL)
     anypattern: dict = field(default_factory=dict)  # (rule, res) -> [(status, path)] per pattern
     warnings: list = field(default_factory=list)    # host-side limits met while rendering messages
 
@@ -128,7 +131,7 @@ class Evaluation:
 def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messages: bool = True,
              namespace_labels: dict | None = None, specialize: bool = False, gpus: int = 1,
              deny: bool = False, foreach: bool = False, foreach_pattern: bool = False,
-             foreach_entries: bool = False) -> Evaluation:
+             foreach_entries: bool = False, foreach_anypattern: bool = False) -> Evaluation:
     """All (rule, resource) pairs on the GPU (``kv_compile`` → ``kv_ingest`` → ``kv_validate``).
     ``specialize`` selects the per-policy-set specialized kernels (worth their hiprtc compile on
     large batches) over the bytecode interpreter; both write the same statuses and error records.
@@ -138,12 +141,15 @@ def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messa
     ``validate.foreach`` rules (``KV_COMPILE_FOREACH``), ``foreach_pattern`` (which implies
     ``foreach``) also for entries that carry a ``pattern`` (``KV_COMPILE_FOREACH_PATTERN``),
     ``foreach_entries`` (which implies ``foreach`` too) also for rules of several entries
-    (``KV_COMPILE_FOREACH_ENTRIES``)."""
+    (``KV_COMPILE_FOREACH_ENTRIES``), ``foreach_anypattern`` (which implies ``foreach_pattern`` and
+    ``foreach``) also for entries that carry an ``anyPattern`` (``KV_COMPILE_FOREACH_ANYPATTERN``)."""
     from . import batch
 
+    foreach_pattern = foreach_pattern or foreach_anypattern
     ps = batch.PolicySet(policies, specialize=specialize, deny=deny,
                          foreach=foreach or foreach_pattern or foreach_entries,
-                         foreach_pattern=foreach_pattern, foreach_entries=foreach_entries)
+                         foreach_pattern=foreach_pattern, foreach_entries=foreach_entries,
+                         foreach_anypattern=foreach_anypattern)
     b = batch.Batch(ps, resources, namespace_labels)
     mask = ((1 << gpus) - 1) << device if gpus > 1 else None
     r = batch.validate(ps, b, device=device, device_mask=mask)
@@ -156,6 +162,8 @@ def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messa
                     ev.foreach_entry[(int(ri), int(res))] = r.foreach_entry(int(ri), int(res))
                 if _pattern_entry(ev, ps.rules[ri], int(res)):  # (a pattern entry: the path inside that element)
                     ev.foreach_path[(int(ri), int(res))] = r.foreach_path(int(ri), int(res))
+                if _any_entry(ev, ps.rules[ri], int(res)):  # (an anyPattern entry: every alternative's outcome on it)
+                    ev.foreach_alts[(int(ri), int(res))] = _foreach_alts(ev, ps.rules[ri], r, int(res))
             elif not ps.rules[ri].any_pattern and not ps.rules[ri].deny:  # (a deny FAIL has no failing path)
                 ev.paths[(int(ri), int(res))] = r.path(int(ri), int(res))
         collect_errors(ev, ps, r, resources)
@@ -290,6 +298,36 @@ def _pattern_entry(ev: Evaluation, rule, res: int) -> bool:
     return k is not None and "pattern" in _foreach_entries(ev, rule)[k]
 
 
+def _any_entry(ev: Evaluation, rule, res: int) -> bool:
+    """The pair of a device foreach rule was decided by an entry that carries an anyPattern."""
+    if getattr(rule, "foreach_anypattern", 0):
+        return True
+    if not getattr(rule, "foreach_entries", 0):
+        return False
+    k = _deciding_entry(ev, rule, res)
+    return k is not None and "anyPattern" in _foreach_entries(ev, rule)[k]
+
+
+def _foreach_alts(ev: Evaluation, rule, r, res: int) -> list:
+    """Per alternative of the deciding anyPattern entry of a FAIL pair, on the deciding element:
+    (status, failing path, err.Error() where the path is empty); None for one the device did not
+    report."""
+    k = _deciding_entry(ev, rule, res)
+    el = _foreach_element(ev, rule, res)
+    outs = []
+    for a in range(len(_foreach_entries(ev, rule)[k]["anyPattern"])):
+        o = r.foreach_alt(rule.index, res, a)
+        if o is None:
+            outs.append(None)
+            continue
+        st, path = o
+        text = None
+        if not path and el is not None:
+            text = r.foreach_alt_error_message(rule.index, res, a, el)
+        outs.append((st, path, text))
+    return outs
+
+
 def _entry_list(entry: dict, resource) -> list | None:
     """evaluateList of one entry: None where the query fails, a map is a one-element list."""
     try:
@@ -364,6 +402,21 @@ def rule_message(ev: Evaluation, rule, res: int) -> str:
                 return head + f"validation error: rule {rule.name} {tail}"
             msg = _message(ev, rule, res, _foreach_element(ev, rule, res, merged=True))
             return head + f"validation error: {_with_dot(msg)} Rule {rule.name} {tail}"
+        if st == FAIL and _any_entry(ev, rule, res):
+            # the element's buildAnyPatternErrorMessage (validation.go:447-489,536-547): one part per
+            # alternative, behind the rule's message as written (it is not substituted)
+            parts = []
+            for j, o in enumerate(ev.foreach_alts.get((rule.index, res), [])):
+                if o is None:
+                    continue
+                _, path, text = o
+                parts.append(f"Rule {rule.name}[{j}] failed at path {path}." if path else
+                             f"Rule {rule.name}[{j}] failed: {text}.")
+            es = " ".join(parts)
+            head = "validation failed in foreach rule for "
+            if not rule.message:
+                return head + f"validation error: {es}"
+            return head + f"validation error: {_with_dot(rule.message)} {es}"
         if st == FAIL:  # the element's validateDeny message, in the element's context
             head = "validation failed in foreach rule for "
             if not rule.message:
@@ -497,19 +550,21 @@ def policy_has_validate(policy: dict) -> bool:
 
 def apply(policy_paths: list[str], resource_paths: list[str], policy_report: bool = False, device: int = 0,
           out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
-          foreach: bool = False, foreach_pattern: bool = False, foreach_entries: bool = False) -> tuple[ResultCounts, list]:
+          foreach: bool = False, foreach_pattern: bool = False, foreach_entries: bool = False,
+          foreach_anypattern: bool = False) -> tuple[ResultCounts, list]:
     """applyCommandHelper (apply_command.go:147-310) for resource files. Returns counts and the
     policyreport infos. ``evaluation_fn(policies, resources) -> Evaluation`` replaces the device
     evaluation (tests of the host logic)."""
     policies = load_policies(policy_paths)
     resources = load_resources(resource_paths)
     return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny, foreach, foreach_pattern,
-                      foreach_entries)
+                      foreach_entries, foreach_anypattern)
 
 
 def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool = False, device: int = 0,
                out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
-          foreach: bool = False, foreach_pattern: bool = False, foreach_entries: bool = False) -> tuple[ResultCounts, list]:
+          foreach: bool = False, foreach_pattern: bool = False, foreach_entries: bool = False,
+          foreach_anypattern: bool = False) -> tuple[ResultCounts, list]:
     mutated = autogen.mutate_policies(policies)
     if len(mutated) > 0 and len(resources) > 0:
         msg_p = "1 policy" if len(mutated) <= 1 else f"{len(policies)} policies"
@@ -523,7 +578,8 @@ def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool 
     if active and resources:
         ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus, deny=deny, foreach=foreach,
                                                           foreach_pattern=foreach_pattern,
-                                                          foreach_entries=foreach_entries)))(active, resources)
+                                                          foreach_entries=foreach_entries,
+                                                          foreach_anypattern=foreach_anypattern)))(active, resources)
         for pi, pol in enumerate(active):
             if not policy_has_validate(pol):
                 continue
@@ -637,6 +693,9 @@ def main(argv: list[str] | None = None) -> int:
     a.add_argument("--device-foreach-entries", action="store_true",
                    help="also evaluate validate.foreach rules of several entries on the GPU "
                         "(KV_COMPILE_FOREACH_ENTRIES; implies --device-foreach)")
+    a.add_argument("--device-foreach-anypattern", action="store_true",
+                   help="also evaluate validate.foreach entries that carry an anyPattern on the GPU "
+                        "(KV_COMPILE_FOREACH_ANYPATTERN; implies --device-foreach-pattern and --device-foreach)")
     t = sub.add_parser("test", help="run tests from a directory holding test.yaml")
     t.add_argument("dir")
     t.add_argument("--device", type=int, default=0)
@@ -644,8 +703,10 @@ def main(argv: list[str] | None = None) -> int:
     if args.cmd == "apply":
         try:
             rc, _ = apply(args.policies, args.resource, args.policy_report, args.device, gpus=args.gpus, deny=args.device_deny,
-                          foreach=args.device_foreach or args.device_foreach_pattern or args.device_foreach_entries,
-                          foreach_pattern=args.device_foreach_pattern, foreach_entries=args.device_foreach_entries)
+                          foreach=(args.device_foreach or args.device_foreach_pattern or args.device_foreach_entries
+                                   or args.device_foreach_anypattern),
+                          foreach_pattern=args.device_foreach_pattern or args.device_foreach_anypattern,
+                          foreach_entries=args.device_foreach_entries, foreach_anypattern=args.device_foreach_anypattern)
         except msgvars.MessageVariableError as e:
             # the Go CLI dies in buildErrorMessage (msgRaw.(string), validation.go:519-524): a
             # panic, exit status 2

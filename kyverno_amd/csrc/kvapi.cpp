@@ -72,6 +72,9 @@ struct DevBatchRes {
   DevBuf pre[5], dn[7], feg[2], fed[7], fe[5], fep[3], feacc, ferec, prest, dnst;
   // rules of several entries (KV_COMPILE_FOREACH_ENTRIES): the chain tables and fe_ckey[chain][res]
   DevBuf fec[2], feckey;
+  // any sets (KV_COMPILE_FOREACH_ANYPATTERN): their two tables (the list paths and `first` are the
+  // pattern sets' buffers), fe_acode[any set][res] and fe_arec[alternative][res]
+  DevBuf fea[2], feacode, fearec;
   double pre_ms = 0, deny_ms = 0, fe_ms = 0;
   DevBatch view{};
 };
@@ -199,7 +202,7 @@ DevPolicySet& dev_ps(kv_policyset* s, int device) {
       d->ptab_rows = (uint32_t)((J.memo_preds.size() + J.ptab_row - 1) / J.ptab_row);
     }
   }
-  if (!ps.fpats.empty()) d->view_dev.upload_raw(&d->view, sizeof(DevPS), device);
+  if (!ps.fpats.empty() || !ps.fanys.empty()) d->view_dev.upload_raw(&d->view, sizeof(DevPS), device);
   auto& ref = *d;
   s->dev[device] = std::move(d);
   return ref;
@@ -401,8 +404,11 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
   FeTables ft{};
   FePatTables qt{};
   DevBuf erec;  // the pattern sets' per-element records: needed until the fold's kernels are done
+  FeAnyTables at{};
+  DevBuf acode, arec;  // the any sets' per-element code words and records: likewise
   const uint32_t n_sets = (uint32_t)ps.csets.size(), n_dsets = (uint32_t)ps.dsets.size(),
                  n_fsets = (uint32_t)ps.fsets.size(), n_pats = (uint32_t)ps.fpats.size(),
+                 n_anys = (uint32_t)ps.fanys.size(),
                  n_chains = (uint32_t)ps.fe_chains.size();
   if (n_sets && !b.res.empty()) {
     build_pre(ps, b, &pre);
@@ -426,12 +432,24 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
     up(d->fe + 2, {&fh.el_res, &fh.el_ord, &fh.lstate}, dp + 2);
     ft.sets = dp[0]; ft.lists = dp[1]; ft.el_res = dp[2]; ft.el_ord = dp[3]; ft.lstate = dp[4];
     d->feacc.alloc((size_t)n_fsets * b.res.size() * sizeof(uint32_t), device);
-    if (n_pats) {
+    if (n_pats || n_anys) {
       const uint32_t* qp[3];
       up(d->fep, {&fh.pats, &fh.chain, &fh.first}, qp);
       qt = FePatTables{qp[0], qp[1], qp[2], n_pats};
+    }
+    if (n_pats) {
       erec.alloc(std::max<size_t>((size_t)n_pats * fh.max_el * sizeof(ErrRec8), 16), device);
       d->ferec.alloc((size_t)n_pats * b.res.size() * sizeof(ErrRec8), device);
+    }
+    if (n_anys) {
+      const uint32_t* ap[2];
+      up(d->fea, {&fh.anys, &fh.any_alts}, ap);
+      const size_t n_alts = fh.any_alts.size();
+      at = FeAnyTables{ap[0], ap[1], qt.chain, qt.first, n_anys, (uint32_t)n_alts};
+      acode.alloc(std::max<size_t>((size_t)n_anys * fh.max_el * sizeof(uint32_t), 16), device);
+      arec.alloc(std::max<size_t>(n_alts * fh.max_el * sizeof(ErrRec8), 16), device);
+      d->feacode.alloc((size_t)n_anys * b.res.size() * sizeof(uint32_t), device);
+      d->fearec.alloc(n_alts * b.res.size() * sizeof(ErrRec8), device);
     }
     if (n_chains) {
       const uint32_t* cp[2];
@@ -453,7 +471,8 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
       return launch_foreach(ft, v.n_res, (uint32_t*)d->feacc.p, (uint8_t*)d->dnst.p + (size_t)n_dsets * v.n_res, us,
                             n_pats ? &qt : nullptr, pdev, (const DevBatch*)d->view_dev.p, (uint2*)erec.p,
                             (uint2*)d->ferec.p, (uint8_t*)d->dnst.p + (size_t)(n_dsets + n_fsets) * v.n_res,
-                            (uint32_t*)d->feckey.p);
+                            (uint32_t*)d->feckey.p, n_anys ? &at : nullptr, (uint32_t*)acode.p, (uint2*)arec.p,
+                            (uint32_t*)d->feacode.p, (uint2*)d->fearec.p);
     });
   HIPCHK(hipStreamSynchronize(us));
   for (const Timed& t : timed) {
@@ -1188,6 +1207,24 @@ struct DevSession {
                             hipMemcpyDeviceToHost, stream));
       lap("foreach_rows_d2h");
     }
+    // any sets of foreach rules: per (any set, resource) the reduction key and the deciding
+    // element's code word, per (alternative, resource) that element's record (kvforeach.h)
+    if (want_st && !ps->ps.fanys.empty() && batch_ref && batch_ref->fearec.p) {
+      const std::vector<uint32_t>& fa = ps->ps.fanys;
+      size_t n_alts = 0;
+      for (uint32_t fs : fa) n_alts += ps->ps.fsets[fs].alt_prog.size();
+      part->fe_akey.alloc(fa.size() * nres);
+      part->fe_acode.alloc(fa.size() * nres);
+      part->fe_arec.alloc(n_alts * nres);
+      for (size_t k = 0; k < fa.size(); k++)
+        HIPCHK(hipMemcpyAsync(part->fe_akey.data() + k * nres, (const uint32_t*)batch_ref->feacc.p + (size_t)fa[k] * nres,
+                              nres * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(part->fe_acode.data(), batch_ref->feacode.p, fa.size() * nres * sizeof(uint32_t),
+                            hipMemcpyDeviceToHost, stream));
+      HIPCHK(hipMemcpyAsync(part->fe_arec.data(), batch_ref->fearec.p, n_alts * nres * sizeof(ErrRec8),
+                            hipMemcpyDeviceToHost, stream));
+      lap("foreach_any_rows_d2h");
+    }
     // rules of several entries: the chain key per (chain, resource) (kvforeach.h kv_fe_chain)
     if (want_st && !ps->ps.fe_chains.empty() && batch_ref && batch_ref->feckey.p) {
       part->fe_ckey.alloc(ps->ps.fe_chains.size() * nres);
@@ -1547,10 +1584,14 @@ int kv_compile(const char* policies_json, size_t len, uint32_t flags, kv_policys
     return fail(err, KV_E_INVALID, "KV_COMPILE_FOREACH_PATTERN needs KV_COMPILE_FOREACH");
   if ((flags & KV_COMPILE_FOREACH_ENTRIES) && !(flags & KV_COMPILE_FOREACH))
     return fail(err, KV_E_INVALID, "KV_COMPILE_FOREACH_ENTRIES needs KV_COMPILE_FOREACH");
+  if ((flags & KV_COMPILE_FOREACH_ANYPATTERN) &&
+      (flags & (KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN)) != (KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN))
+    return fail(err, KV_E_INVALID, "KV_COMPILE_FOREACH_ANYPATTERN needs KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN");
   return guarded(KV_E_PARSE, err, [&]() -> int {
     auto s = std::make_unique<kv_policyset>();
     compile_policies(policies_json, len, &s->ps,
-                     flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN | KV_COMPILE_FOREACH_ENTRIES));
+                     flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN | KV_COMPILE_FOREACH_ENTRIES |
+                              KV_COMPILE_FOREACH_ANYPATTERN));
     if (flags & KV_COMPILE_SPECIALIZE) {
       s->jit = std::make_unique<JitImage>();
       jit_build(s->ps, s->jit.get());  // (kvjitbuild.cpp: generate, plan, compile, variants)

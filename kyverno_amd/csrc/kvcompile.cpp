@@ -1582,7 +1582,8 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
         uint32_t fe_chain = 0;
         uint32_t* fe_chainp = (flags & 16u /* KV_COMPILE_FOREACH_ENTRIES */) ? &fe_chain : nullptr;
         if (!has_validate) { rr.route = 2; rh.route_reason = "no validate"; }
-        else if (feP && (!feD || ((rh.foreach_set = compile_foreach(*ps, d, (uint32_t)fen, fe_patp, fe_chainp)) == 0 &&
+        else if (feP && (!feD || ((rh.foreach_set = compile_foreach(*ps, d, (uint32_t)fen, fe_patp, fe_chainp,
+                                                                            (flags & 32u /* KV_COMPILE_FOREACH_ANYPATTERN */) != 0)) == 0 &&
                                   (rh.foreach_chain = fe_chain) == 0))) {
           rr.route = 1;
           rh.route_reason = "foreach";

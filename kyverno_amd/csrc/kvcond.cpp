@@ -632,31 +632,57 @@ bool may_read_element(const JDoc& d, uint32_t node) {
   return false;
 }
 
+// a key or string below `node` that holds a `$(` reference
+bool has_reference(const JDoc& d, uint32_t node) {
+  const JNode& n = d.at(node);
+  if (n.t == J_STR) return d.sval(n).find("$(") != std::string_view::npos;
+  if (n.t == J_MAP || n.t == J_ARR)
+    for (uint32_t c = n.first; c < n.first + n.count; c++) {
+      if (n.t == J_MAP && d.key(d.at(c)).find("$(") != std::string_view::npos) return true;
+      if (has_reference(d, c)) return true;
+    }
+  return false;
+}
+
 // One entry {list, preconditions?, deny | pattern} of validate.foreach, its element strings in
 // the leak context `before` (the lists of the entries in front of it; empty for the first): 1 +
 // its foreach set, 0 outside the scope (nothing is left behind)
 uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const FePatternCompiler* pattern,
-                               const std::vector<uint32_t>& before) {
+                               const std::vector<uint32_t>& before, bool anypattern = false) {
   if (d.at(en).t != J_MAP) return 0;
-  int64_t ln = -1, pn = -1, dn = -1, tn = -1;
+  int64_t ln = -1, pn = -1, dn = -1, tn = -1, an = -1;
   for (uint32_t c = d.at(en).first; c < d.at(en).first + d.at(en).count; c++) {
     const std::string_view k = d.key(d.at(c));
     if (k == "list") ln = c;
     else if (k == "preconditions") pn = c;
     else if (k == "deny") dn = c;
     else if (k == "pattern" && pattern) tn = c;
-    else return 0;  // anyPattern, context, ... (and pattern without KV_COMPILE_FOREACH_PATTERN)
+    else if (k == "anyPattern" && pattern && anypattern) an = c;
+    else return 0;  // context, ... (and pattern / anyPattern without their flags)
+  }
+  // an anyPattern entry (KV_COMPILE_FOREACH_ANYPATTERN): a list of 1 to 8 maps, nothing beside it
+  // (an empty list passes with the rule message in the reference: left to it)
+  if (an >= 0) {
+    const JNode& al = d.at((uint32_t)an);
+    if (tn >= 0 || dn >= 0 || al.t != J_ARR || al.count == 0 || al.count > FE_MAX_ALTS) return 0;
+    for (uint32_t c = al.first; c < al.first + al.count; c++)
+      if (d.at(c).t != J_MAP) return 0;
+    // The reference substitutes the anyPattern list as one document (validation.go:560-567), so a
+    // `$()` reference resolves against the list, alternative k at /k/...: an absolute one, or a
+    // relative one that climbs above its alternative, does not resolve and every element is an
+    // ERROR. The alternatives are compiled one by one here: a reference anywhere stays routed.
+    if (has_reference(d, (uint32_t)an)) return 0;
   }
   // a pattern entry: the pattern a map, no deny beside it
   if (tn >= 0 && (dn >= 0 || d.at((uint32_t)tn).t != J_MAP)) return 0;
-  if (ln < 0 || (dn < 0 && tn < 0) || d.at((uint32_t)ln).t != J_STR) return 0;
+  if (ln < 0 || (dn < 0 && tn < 0 && an < 0) || d.at((uint32_t)ln).t != J_STR) return 0;
   const std::string list(d.sval(d.at((uint32_t)ln)));
   if (!list_query_in_scope(list)) return 0;
   if (pn >= 0 && d.at((uint32_t)pn).t == J_NULL) pn = -1;
   // the old list form of an entry's preconditions fails common.ToMap and is dropped by the
   // reference (validation.go:260-266): left to it
   if (pn >= 0 && d.at((uint32_t)pn).t != J_MAP) return 0;
-  const int64_t cn = tn >= 0 ? 0 : deny_conditions(d, (uint32_t)dn);
+  const int64_t cn = tn >= 0 || an >= 0 ? 0 : deny_conditions(d, (uint32_t)dn);
   if (cn < 0) return 0;
   // checkpoint: an entry outside the scope leaves nothing behind
   const size_t l0 = ps.flists.size(), k0 = ps.elem.keys.size(), c0 = ps.elem.conds.size();
@@ -716,6 +742,9 @@ uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const 
   if (tn >= 0) {
     did = "P";
     pattern_text(to_pv(d, (uint32_t)tn), &did);
+  } else if (an >= 0) {  // (an any set is interned by its alternatives' texts, in order)
+    did = "A";
+    pattern_text(to_pv(d, (uint32_t)an), &did);
   } else if (!compile_deny_block(sp, d, (uint32_t)cn, &s.deny, &did)) {
     return rollback();
   }
@@ -733,6 +762,21 @@ uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const 
     s.pattern = true;
     s.pat = (uint32_t)ps.fpats.size();
     ps.fpats.push_back((uint32_t)ps.fsets.size());
+  }
+  // an anyPattern entry met for the first time: one plain pattern program per alternative, each
+  // with a root pattern node of its own (the caller's checkpoint takes back what the earlier
+  // alternatives of a refused entry left)
+  if (an >= 0 && it == ps.fset_id.end()) {
+    const JNode& al = d.at((uint32_t)an);
+    for (uint32_t c = al.first; c < al.first + al.count; c++) {
+      FeSet alt;
+      if (!(*pattern)(c, list, s.list, &alt)) return rollback();
+      s.alt_prog.push_back(alt.prog);
+      s.alt_root.push_back(alt.root_pnode);
+    }
+    s.any = true;
+    s.anyi = (uint32_t)ps.fanys.size();
+    ps.fanys.push_back((uint32_t)ps.fsets.size());
   }
   // the strings this entry added: their list, resolver mode and column in the list's element rows
   for (size_t i = ps.fkeys.size(); i < ps.elem.keys.size(); i++) {
@@ -757,14 +801,14 @@ uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const 
 // the sizes every table a foreach rule compiles into had before it, and the way back
 struct FeCheckpoint {
   PolicySet& ps;
-  size_t prog, fix, pnodes, lists, keys, conds, fkeys, sets, pats, ctxs, paths;
+  size_t prog, fix, pnodes, lists, keys, conds, fkeys, sets, pats, anys, ctxs, paths;
   size_t preds, alts, conjs, atoms, gsegs, gwords, strs;  // (what the programs' leaf predicates interned)
   std::vector<size_t> list_keys;
   std::vector<bool> path_set;
   explicit FeCheckpoint(PolicySet& p)
       : ps(p), prog(p.prog.size()), fix(p.slot_fix.size()), pnodes(p.pnodes.size()), lists(p.flists.size()),
         keys(p.elem.keys.size()), conds(p.elem.conds.size()), fkeys(p.fkeys.size()), sets(p.fsets.size()),
-        pats(p.fpats.size()), ctxs(p.fctx.size()), paths(p.fchains.size()), preds(p.preds.size()), alts(p.alts.size()),
+        pats(p.fpats.size()), anys(p.fanys.size()), ctxs(p.fctx.size()), paths(p.fchains.size()), preds(p.preds.size()), alts(p.alts.size()),
         conjs(p.conjs.size()), atoms(p.atoms.size()), gsegs(p.gsegs.size()), gwords(p.gwords.size()), strs(p.strs.size()) {
     for (const auto& k : p.flist_keys) list_keys.push_back(k.size());
     for (const FeChain& c : p.fchains) path_set.push_back(!c.steps.empty());
@@ -794,6 +838,7 @@ struct FeCheckpoint {
     ps.fsets.resize(sets);
     drop_from(ps.fset_id, sets);
     ps.fpats.resize(pats);
+    ps.fanys.resize(anys);
     ps.fctx.resize(ctxs);
     drop_from(ps.fctx_id, ctxs);
     ps.fchains.resize(paths);
@@ -803,20 +848,28 @@ struct FeCheckpoint {
 };
 }  // namespace
 
-uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern, uint32_t* chain) {
+uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern, uint32_t* chain,
+                         bool anypattern) {
   // validate.foreach: a list of one entry, or (chain: KV_COMPILE_FOREACH_ENTRIES) of 2 to 16, each
   // what a single entry may be. With several, keys of entry k-1's last element leak into entry
   // k's `element` (kvcond.h): entry k's strings are compiled in the context of the lists before it
   if (chain) *chain = 0;
   if (d.at(node).t != J_ARR) return 0;
   const uint32_t count = d.at(node).count, first = d.at(node).first;
-  if (count == 1) return compile_foreach_entry(ps, d, first, pattern, {});
+  if (count == 1 && !(anypattern && d.at(first).t == J_MAP && d.get(first, "anyPattern") >= 0))
+    return compile_foreach_entry(ps, d, first, pattern, {});
+  if (count == 1) {  // (an anyPattern entry refused at a later alternative: the earlier ones' programs go)
+    FeCheckpoint ck(ps);
+    const uint32_t s = compile_foreach_entry(ps, d, first, pattern, {}, true);
+    if (!s) ck.rollback();
+    return s;
+  }
   if (!chain || count < 2 || count > FE_MAX_ENTRIES) return 0;
   FeCheckpoint ck(ps);
   std::vector<uint32_t> sets, before;
   std::string id;
   for (uint32_t en = first; en < first + count; en++) {
-    const uint32_t s = compile_foreach_entry(ps, d, en, pattern, before);
+    const uint32_t s = compile_foreach_entry(ps, d, en, pattern, before, anypattern);
     if (!s) {
       ck.rollback();
       return 0;
@@ -1044,7 +1097,8 @@ void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out) {
   std::vector<BlockRef> gate, deny;
   for (const FeSet& s : ps.fsets) {
     // (a pattern set: an empty deny row, never folded; word 2 names its pattern set)
-    h.sets.insert(h.sets.end(), {s.list, s.has_pre ? 1u : 0u, s.pattern ? 1u + s.pat : 0u, 0u});
+    // (an any set likewise; word 3 names it)
+    h.sets.insert(h.sets.end(), {s.list, s.has_pre ? 1u : 0u, s.pattern ? 1u + s.pat : 0u, s.any ? 1u + s.anyi : 0u});
     gate.push_back({&s.pre, nullptr});
     deny.push_back({&s.deny.fold, &s.deny.strs});
   }
@@ -1060,6 +1114,15 @@ void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out) {
     const FeSet& s = ps.fsets[fs];
     const FeChain& c = ps.fchains.at(s.list);
     h.pats.insert(h.pats.end(), {fs, s.prog, (uint32_t)(h.chain.size() / 2), (uint32_t)(c.words.size() / 2)});
+    h.chain.insert(h.chain.end(), c.words.begin(), c.words.end());
+  }
+  // the any sets: their alternatives' programs and the path to their list's elements
+  for (uint32_t fs : ps.fanys) {
+    const FeSet& s = ps.fsets[fs];
+    const FeChain& c = ps.fchains.at(s.list);
+    h.anys.insert(h.anys.end(), {fs, (uint32_t)h.any_alts.size(), (uint32_t)s.alt_prog.size(), (uint32_t)(h.chain.size() / 2),
+                                 (uint32_t)(c.words.size() / 2), 0u, 0u, 0u});
+    h.any_alts.insert(h.any_alts.end(), s.alt_prog.begin(), s.alt_prog.end());
     h.chain.insert(h.chain.end(), c.words.begin(), c.words.end());
   }
 }
@@ -1084,9 +1147,15 @@ FePatTables FeHost::pat_view() const {
   return FePatTables{pats.data(), chain.data(), first.data(), (uint32_t)(pats.size() / 4)};
 }
 
+FeAnyTables FeHost::any_view() const {
+  return FeAnyTables{anys.data(), any_alts.data(), chain.data(), first.data(), (uint32_t)(anys.size() / 8),
+                     (uint32_t)any_alts.size()};
+}
+
 uint8_t foreach_fold_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_t r, uint32_t* elem) {
   // (a pattern set's elements are walked on the device only: no host evaluator)
-  if (h.sets[4 * set + 2]) throw std::runtime_error("foreach_fold_host: a pattern set has no host fold");
+  if (h.sets[4 * set + 2] || h.sets[4 * set + 3])
+    throw std::runtime_error("foreach_fold_host: a pattern set or any set has no host fold");
   const FeTables t = h.view();
   const uint32_t list = h.sets[4 * set];
   const uint32_t n_el = h.lists[4 * list + 1], el0 = h.lists[4 * list + 3];

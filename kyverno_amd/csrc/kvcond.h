@@ -30,6 +30,7 @@ namespace kv {
 struct CondBlocks;  // kvblocks.h
 struct FeTables;    // kvforeach.h
 struct FePatTables;
+struct FeAnyTables;
 }
 
 namespace kvh {
@@ -147,8 +148,13 @@ using FePatternCompiler = std::function<bool(uint32_t pattern_node, const std::s
 // merged in when entry k + 1 starts (DESIGN.md §3 *Several entries*), so the element strings of an
 // entry behind the first are interned per *leak context*, the lists of the entries before it
 // (PolicySet::fctx), and resolve at ingest against the element over those lists' last elements.
+// `anypattern` (KV_COMPILE_FOREACH_ANYPATTERN, with `pattern`; validation.go:175-202,447-489): an
+// entry {list, preconditions?, anyPattern} of 1 to 8 map alternatives compiles to an *any set*, a
+// foreach set with one plain pattern program per alternative (each compiled by `pattern`, with a
+// root pattern node of its own), interned by the alternatives' texts. Per element the device
+// tries them in order (kv_foreach_any_kernel): the first that matches is PASS, none is FAIL.
 uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern = nullptr,
-                         uint32_t* chain = nullptr);
+                         uint32_t* chain = nullptr, bool anypattern = false);
 
 struct FeHost {
   // row s of gate / deny: the entry preconditions / the deny block of foreach set s. deny holds the
@@ -159,9 +165,11 @@ struct FeHost {
                                 // accessors; on the device only kv_foreach_rec_kernel reads it)
   std::vector<uint32_t> pats, chain;  // kvforeach.h FePatTables: the pattern sets and their lists' paths
   std::vector<uint32_t> chains, chain_ents;  // kvforeach.h FeTables: the rules of several entries
+  std::vector<uint32_t> anys, any_alts;      // kvforeach.h FeAnyTables: the any sets and their alternatives' programs
   uint32_t max_el = 0;
   kv::FeTables view() const;
   kv::FePatTables pat_view() const;
+  kv::FeAnyTables any_view() const;
 };
 void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out);
 // one (foreach set, store resource) on the host, as the two kernels: ST_PASS, ST_FAIL, ST_ERROR,

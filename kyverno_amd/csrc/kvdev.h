@@ -31,12 +31,18 @@ hipError_t launch_cond(bool strict, const CondBlocks& T, uint32_t n_res, uint32_
 // element's into fe_rec[pattern set][res]. With chains (T.n_chains, KV_COMPILE_FOREACH_ENTRIES):
 // kv_foreach_chain_kernel then folds each chain's entry rows into chain_st[chain][res] (the rows of
 // the deny plane after the foreach sets') and the chain keys fe_ckey[chain][res].
+// With any sets (A, kvforeach.h FeAnyTables; KV_COMPILE_FOREACH_ANYPATTERN): their elements go
+// through kv_foreach_any_kernel, the per-element code words into the transient acode[any set]
+// [T.max_el] and the alternatives' records into arec[alternative][T.max_el]; the deciding
+// element's into fe_acode[any set][res] and fe_arec[alternative][res].
 struct FeTables;
 struct FePatTables;
+struct FeAnyTables;
 hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream,
                           const FePatTables* Q = nullptr, const DevPS* P = nullptr, const DevBatch* B = nullptr,
                           uint2* erec = nullptr, uint2* fe_rec = nullptr, uint8_t* chain_st = nullptr,
-                          uint32_t* fe_ckey = nullptr);
+                          uint32_t* fe_ckey = nullptr, const FeAnyTables* A = nullptr, uint32_t* acode = nullptr,
+                          uint2* arec = nullptr, uint32_t* fe_acode = nullptr, uint2* fe_arec = nullptr);
 
 // Match tables of a pass (DevPS::mt_*): `words` = mt_ns_words + mt_ann_words +
 // mt_sel_words rows, max_entities = max(n_nsm, n_asets, n_lsets).

@@ -1,6 +1,6 @@
 // validate.foreach on the device (kvcond.h): the list states, the per-element verdict and the
-// reduction keys, shared by kv_foreach_elem_kernel / kv_foreach_pat_kernel / kv_foreach_fin_kernel /
-// kv_foreach_chain_kernel (kvkernel.hip) and the host fold (kvcond.cpp foreach_fold_host). Plain code over the tables of
+// reduction keys, shared by kv_foreach_elem_kernel / kv_foreach_pat_kernel / kv_foreach_any_kernel /
+// kv_foreach_fin_kernel / kv_foreach_chain_kernel (kvkernel.hip) and the host fold (kvcond.cpp foreach_fold_host). Plain code over the tables of
 // kvcond.h FeHost; needs kv_layout.h and kvblocks.h.
 #pragma once
 
@@ -12,6 +12,7 @@ constexpr uint8_t FE_LIST_OK = 1;     // a list of maps (or one map), no null in
 constexpr uint8_t FE_LIST_OOS = 2;    // anything else: the pair is ST_CPU
 constexpr uint32_t FE_MAX_ELEMS = 0x10000u;
 constexpr uint32_t FE_MAX_ENTRIES = 16u;  // entries of one rule (KV_COMPILE_FOREACH_ENTRIES)
+constexpr uint32_t FE_MAX_ALTS = 8u;      // alternatives of one anyPattern entry (KV_COMPILE_FOREACH_ANYPATTERN)
 
 // Reduction keys of fe_acc[set][res] (atomicMin): the first decisive element of the resource's
 // list, (index in the list << 3 | its ST_ code), below the key of "some element passed", below
@@ -22,7 +23,7 @@ constexpr uint32_t FE_KEY_NONE = 0xFFFFFFFFu;
 // The device view of FeHost (32-bit words throughout). Row s of gate / deny is foreach set s; the
 // two share outc and the truth / unknown planes, and their string rows are columns of the set's list.
 struct FeTables {
-  const uint32_t* sets;    // 4 words per foreach set: list, has_pre, 1 + pattern set (0: a deny block), 0
+  const uint32_t* sets;    // 4 words per foreach set: list, has_pre, 1 + pattern set, 1 + any set (both 0: a deny block)
   const uint32_t* lists;   // 4 words per list: first word of its outc block, elements, first plane row, first element
   CondBlocks gate;         // the entry preconditions of every set (preconditions resolver: no err / oos)
   CondBlocks deny;         // the deny block of every set; outc: per list a block [string of the list][element
@@ -48,6 +49,19 @@ struct FePatTables {
   const uint32_t* chain;  // 2 words per step of a list path: FE_STEP_*, slot | index | key id
   const uint32_t* first;  // [list][res]: the resource's first element in the list's block
   uint32_t n_pats;
+};
+
+// Any sets (KV_COMPILE_FOREACH_ANYPATTERN): the foreach sets whose entry carries an `anyPattern`,
+// the alternatives plain pattern programs tried in order per element (kv_foreach_any_kernel).
+// The code word of an element: 4 bits per alternative, alternative k's ST_ status (FAIL, ERROR or
+// SKIP) in bits [4k, 4k + 4), 0 for one that was not evaluated or passed. The record alone cannot
+// tell ERROR from FAIL, so the status is kept beside it.
+struct FeAnyTables {
+  const uint32_t* anys;   // 8 words per any set: foreach set, first alternative, alternatives, first step, steps, 0, 0, 0
+  const uint32_t* alts;   // per alternative: the first instruction of its program
+  const uint32_t* chain;  // FePatTables::chain
+  const uint32_t* first;  // FePatTables::first
+  uint32_t n_anys, n_alts;
 };
 
 // One element of foreach set `set`: element e of the set's list (e < its element count).

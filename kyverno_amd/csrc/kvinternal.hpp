@@ -119,6 +119,12 @@ struct FeSet {
   DenySet deny;
   bool pattern = false;
   uint32_t prog = 0, root_pnode = 0, pat = 0;
+  // An any set (KV_COMPILE_FOREACH_ANYPATTERN): the entry's `anyPattern` instead, one plain pattern
+  // program and root pattern node per alternative, in order, and its index among the any sets
+  // (`anyi`, PolicySet::fanys)
+  bool any = false;
+  uint32_t anyi = 0;
+  std::vector<uint32_t> alt_prog, alt_root;
 };
 // One step of a foreach list path (kvvars.cpp list_query_steps): a field or an index
 struct ListStep {
@@ -287,6 +293,9 @@ struct PolicySet {
   // no pattern set reads the list)
   std::vector<uint32_t> fpats;
   std::vector<FeChain> fchains;
+  // anyPattern entries (KV_COMPILE_FOREACH_ANYPATTERN): the foreach sets that carry an anyPattern,
+  // in order (FeSet::anyi indexes it); their lists' paths are in fchains too
+  std::vector<uint32_t> fanys;
   // rules of several entries (KV_COMPILE_FOREACH_ENTRIES): a *chain* is the ordered list of the
   // entries' foreach sets, interned by that list (fe_chains). The reference's JSON context keeps
   // the last element of entry k merged in when entry k + 1 starts, so an entry's `element` strings
@@ -301,7 +310,7 @@ struct PolicySet {
 
 // Compiles a JSON list of (already autogen-expanded) ClusterPolicy/Policy
 // objects (flags: kv_compile's KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN |
-// KV_COMPILE_FOREACH_ENTRIES). Throws
+// KV_COMPILE_FOREACH_ENTRIES | KV_COMPILE_FOREACH_ANYPATTERN). Throws
 // std::runtime_error on malformed input.
 void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flags = 0);
 

@@ -225,7 +225,7 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_elem_kernel(FeTab
   const uint32_t e = blockIdx.x * KV_WG + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63u;
   for (uint32_t s = blockIdx.y; s < T.n_sets; s += gridDim.y) {
-    if (T.sets[4u * s + 2u]) continue;  // (a pattern set: kv_foreach_pat_kernel's)
+    if (T.sets[4u * s + 2u] | T.sets[4u * s + 3u]) continue;  // (a pattern set or any set: their own kernels')
     const uint32_t* L = T.lists + 4u * T.sets[4u * s];
     const uint32_t n_el = L[1], el0 = L[3];
     if (blockIdx.x * KV_WG >= n_el) continue;  // (workgroup-uniform)
@@ -281,6 +281,43 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_pat_kernel(FeTabl
   }
 }
 
+// kv_foreach_any_kernel (KV_COMPILE_FOREACH_ANYPATTERN, kvwalk.h kv_fe_any_lane): the elements of
+// the any sets. The launch shape of kv_foreach_pat_kernel with grid.y = any sets; the gate and the
+// element-node lookup are the same code. A lane then tries its set's alternatives in order, the
+// loop bound uniform for the launch row and no lane leaving or skipping a walk; the first that
+// matches makes the element ST_PASS, none ST_FAIL. For the alternatives that did not match, the
+// 8-byte record goes to the transient arec[alternative][element] (alternatives numbered through
+// all any sets) and the status into the element's code word, acode[any set][element] (written for
+// every element of the list: 0 unless the element is ST_FAIL). The code feeds kv_fe_reduce.
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_any_kernel(FeTables T, FeAnyTables A,
+                                                                           const DevPS* __restrict__ Pp,
+                                                                           const DevBatch* __restrict__ Bp,
+                                                                           uint32_t n_res, uint32_t* __restrict__ fe_acc,
+                                                                           uint32_t* __restrict__ acode,
+                                                                           uint2* __restrict__ arec) {
+  __shared__ uint32_t s_cur[KV_MAXD][KV_WG];
+  __shared__ uint32_t s_lfirst[KV_MAXL][KV_WG];
+  __shared__ uint32_t s_llen[KV_MAXL][KV_WG];
+  __shared__ uint32_t s_li[KV_WG / 64][KV_MAXL];
+  const DevPS& P = *Pp;
+  const DevBatch& B = *Bp;
+  const Node* __restrict__ N = B.nodes;
+  const uint32_t e = blockIdx.x * KV_WG + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint32_t a = blockIdx.y; a < A.n_anys; a += gridDim.y) {
+    const uint32_t* AT = A.anys + 8u * a;
+    const uint32_t s = uni(AT[0]), a0 = uni(AT[1]);
+    const uint32_t n_el = T.lists[4u * T.sets[4u * s] + 1u];
+    if (blockIdx.x * KV_WG >= n_el) continue;  // (workgroup-uniform)
+    const bool valid = e < n_el;  // (n_el <= T.max_el: a valid lane's slots are inside acode and arec)
+    uint32_t res, ord, cw;
+    const uint32_t code = kv_fe_any_lane(T, A, P, B, N, a, e, valid, n_res, s_cur, s_lfirst, s_llen, s_li, &res, &ord, &cw,
+                                         arec + ((size_t)a0 * T.max_el + e), T.max_el);
+    if (valid) acode[(size_t)a * T.max_el + e] = cw;
+    kv_fe_reduce(lane, valid, res, ord, code, n_res, fe_acc + (size_t)s * n_res);
+  }
+}
+
 // kv_foreach_fin_kernel: one lane per resource, grid.y = foreach sets; the list state and the
 // reduced key into the status byte of row `set` of fe_st (the rows of DevBatch::deny_st after the
 // deny sets'): ST_CPU, ST_SKIP, ST_PASS, or the code of the first decisive element.
@@ -315,6 +352,33 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_rec_kernel(FeTabl
   }
 }
 
+// kv_foreach_anyrec_kernel: one lane per resource, grid.y = any sets; where the reduced key is
+// FAIL, the deciding element's code word into fe_acode[any set][res] and, per alternative whose
+// field of it is set, its record into fe_arec[alternative][res]; zeros everywhere else.
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_anyrec_kernel(FeTables T, FeAnyTables A, uint32_t n_res,
+                                                                              const uint32_t* __restrict__ fe_acc,
+                                                                              const uint32_t* __restrict__ acode,
+                                                                              const uint2* __restrict__ arec,
+                                                                              uint32_t* __restrict__ fe_acode,
+                                                                              uint2* __restrict__ fe_arec) {
+  const uint64_t r = (uint64_t)blockIdx.x * KV_WG + threadIdx.x;
+  if (r >= n_res) return;
+  for (uint32_t a = blockIdx.y; a < A.n_anys; a += gridDim.y) {
+    const uint32_t s = A.anys[8u * a], a0 = A.anys[8u * a + 1u], na = A.anys[8u * a + 2u], list = T.sets[4u * s];
+    const uint32_t key = fe_acc[(size_t)s * n_res + r];
+    uint64_t e = 0;
+    uint32_t cw = 0;
+    if (key < FE_KEY_PASS && (key & 7u) == ST_FAIL) {
+      e = (uint64_t)A.first[(size_t)list * n_res + r] + (key >> 3);
+      if (e < T.lists[4u * list + 1u]) cw = acode[(size_t)a * T.max_el + e];
+    }
+    fe_acode[(size_t)a * n_res + r] = cw;
+    for (uint32_t k = 0; k < na; k++)
+      fe_arec[(size_t)(a0 + k) * n_res + r] =
+          (cw >> (4u * k)) & 15u ? arec[(size_t)(a0 + k) * T.max_el + e] : make_uint2(0u, 0u);
+  }
+}
+
 // kv_foreach_chain_kernel (KV_COMPILE_FOREACH_ENTRIES): one lane per resource, grid.y = chains,
 // after kv_foreach_fin_kernel on the same stream. A lane walks its chain's entries in order
 // (kv_fe_chain: one coalesced word of lstate and one of fe_acc per entry; the chain's words are
@@ -337,23 +401,31 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_chain_kernel(FeTa
 namespace kv {
 hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream,
                           const FePatTables* Q, const DevPS* P, const DevBatch* B, uint2* erec, uint2* fe_rec,
-                          uint8_t* chain_st, uint32_t* fe_ckey) {
+                          uint8_t* chain_st, uint32_t* fe_ckey, const FeAnyTables* A, uint32_t* acode, uint2* arec,
+                          uint32_t* fe_acode, uint2* fe_arec) {
   if (n_res == 0 || T.n_sets == 0) return hipSuccess;
   const hipError_t e = hipMemsetAsync(fe_acc, 0xFF, (size_t)T.n_sets * n_res * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
   const uint32_t gy = T.n_sets < KV_PRE_YMAX ? T.n_sets : KV_PRE_YMAX;
   const uint32_t n_pats = Q ? Q->n_pats : 0u, py = n_pats < KV_PRE_YMAX ? n_pats : KV_PRE_YMAX;
-  if (T.max_el && T.n_sets > n_pats)
+  const uint32_t n_anys = A ? A->n_anys : 0u, ay = n_anys < KV_PRE_YMAX ? n_anys : KV_PRE_YMAX;
+  if (T.max_el && T.n_sets > n_pats + n_anys)
     hipLaunchKernelGGL(kv_foreach_elem_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, gy), dim3(KV_WG), 0, stream, T, n_res,
                        fe_acc);
   if (T.max_el && n_pats)
     hipLaunchKernelGGL(kv_foreach_pat_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, py), dim3(KV_WG), 0, stream, T, *Q, P, B,
                        n_res, fe_acc, erec);
+  if (T.max_el && n_anys)
+    hipLaunchKernelGGL(kv_foreach_any_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, ay), dim3(KV_WG), 0, stream, T, *A, P, B,
+                       n_res, fe_acc, acode, arec);
   hipLaunchKernelGGL(kv_foreach_fin_kernel, dim3((n_res + KV_WG - 1) / KV_WG, gy), dim3(KV_WG), 0, stream, T, n_res,
                      (const uint32_t*)fe_acc, fe_st);
   if (n_pats)
     hipLaunchKernelGGL(kv_foreach_rec_kernel, dim3((n_res + KV_WG - 1) / KV_WG, py), dim3(KV_WG), 0, stream, T, *Q, n_res,
                        (const uint32_t*)fe_acc, (const uint2*)erec, fe_rec);
+  if (n_anys)
+    hipLaunchKernelGGL(kv_foreach_anyrec_kernel, dim3((n_res + KV_WG - 1) / KV_WG, ay), dim3(KV_WG), 0, stream, T, *A, n_res,
+                       (const uint32_t*)fe_acc, (const uint32_t*)acode, (const uint2*)arec, fe_acode, fe_arec);
   if (T.n_chains && chain_st && fe_ckey)
     hipLaunchKernelGGL(kv_foreach_chain_kernel,
                        dim3((n_res + KV_WG - 1) / KV_WG, T.n_chains < KV_PRE_YMAX ? T.n_chains : KV_PRE_YMAX), dim3(KV_WG), 0,

@@ -416,6 +416,41 @@ bool pattern_pair(const Pair& q, uint32_t* key, ErrRec8* rec) {
   return true;
 }
 
+// A FAIL pair of a device foreach rule that an anyPattern entry decided
+// (KV_COMPILE_FOREACH_ANYPATTERN): the fetched reduction key, the deciding element's code word, the
+// deciding set and the row of its first alternative in fe_arec. False for every other pair.
+bool any_pair(const Pair& q, uint32_t* key, uint32_t* cw, uint32_t* set_o, size_t* alt0) {
+  if (!q.part || q.part->fe_akey.empty()) return false;
+  const RuleHost& rh = q.ps().rhost[q.rule];
+  if (!rh.foreach_set && !rh.foreach_chain) return false;
+  const uint8_t st = q.status();
+  if (st != ST_FAIL) return false;
+  uint32_t set, entry, elem;
+  if (!deciding_entry(q, st, &set, &entry, &elem) || !q.ps().fsets[set].any) return false;
+  const size_t at = (size_t)q.ps().fsets[set].anyi * q.part->n + q.local;
+  const uint32_t k = q.part->fe_akey[at];
+  if (k >= FE_KEY_PASS || (k & 7u) != st) return false;
+  if (rh.foreach_chain && (k >> 3) != elem) return false;
+  *key = k;
+  *cw = q.part->fe_acode[at];
+  *set_o = set;
+  *alt0 = 0;
+  for (uint32_t i = 0; i < q.ps().fsets[set].anyi; i++) *alt0 += q.ps().fsets[q.ps().fanys[i]].alt_prog.size();
+  return true;
+}
+
+// alternative `alt` of an any_pair: its status on the deciding element and its record
+int any_alt(const Pair& q, uint32_t alt, uint32_t* status, ErrRec8* rec) {
+  uint32_t key, cw, set;
+  size_t alt0;
+  if (!any_pair(q, &key, &cw, &set, &alt0)) return KV_E_INVALID;
+  if (alt >= q.ps().fsets[set].alt_prog.size()) return KV_E_RANGE;
+  *status = (cw >> (4u * alt)) & 15u;
+  if (*status != ST_FAIL && *status != ST_ERROR && *status != ST_SKIP) return KV_E_INVALID;
+  *rec = q.part->fe_arec[(alt0 + alt) * q.part->n + q.local];
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -576,6 +611,12 @@ int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, u
       if (pattern_pair(q, &key, &rec)) *index = key >> 3;
       return 0;
     }
+    if (q.ps().fsets[set - 1].any) {  // an anyPattern entry likewise
+      uint32_t key, cw, s;
+      size_t a0;
+      if (any_pair(q, &key, &cw, &s, &a0)) *index = key >> 3;
+      return 0;
+    }
     uint32_t e = 0xFFFFFFFFu;
     if (foreach_fold_host(q.kb->fe_host(q.ps()), set - 1, q.n_local(), q.local, &e) == st) *index = e;
     return 0;
@@ -622,7 +663,7 @@ int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, c
         return key == FE_KEY_NONE ? put_message("rule skipped", buf, cap) : 0;
       }
       uint32_t s, entry, e;
-      if (!deciding_entry(q, cst, &s, &entry, &e) || ps.fsets[s].pattern) return 0;
+      if (!deciding_entry(q, cst, &s, &entry, &e) || ps.fsets[s].pattern || ps.fsets[s].any) return 0;
       const std::string err = foreach_error_host(ps, q.kb->b, q.kb->fe_host(ps), s, q.local, e);
       if (err.empty()) return 0;
       return put_message("validation failed in foreach rule for failed to substitute variables in deny conditions: " + err,
@@ -639,6 +680,13 @@ int kv_result_foreach_message(const kv_result* r, uint32_t rule, uint64_t res, c
       const RuleRec& rr = ps.rules[rule];
       if (rr.pre && pre_status_host(q.kb->pre_host(ps), rr.pre - 1, q.n_local(), q.local) == ST_SKIP) return 0;
       if (q.part->fe_key[(size_t)ps.fsets[fs - 1].pat * q.part->n + q.local] != FE_KEY_NONE) return 0;
+      return put_message("rule skipped", buf, cap);
+    }
+    if (ps.fsets[fs - 1].any) {  // an anyPattern entry likewise (it has no ERROR of its own)
+      if (st != ST_SKIP || q.part->fe_akey.empty()) return 0;
+      const RuleRec& rr = ps.rules[rule];
+      if (rr.pre && pre_status_host(q.kb->pre_host(ps), rr.pre - 1, q.n_local(), q.local) == ST_SKIP) return 0;
+      if (q.part->fe_akey[(size_t)ps.fsets[fs - 1].anyi * q.part->n + q.local] != FE_KEY_NONE) return 0;
       return put_message("rule skipped", buf, cap);
     }
     const FeHost& h = q.kb->fe_host(ps);
@@ -682,6 +730,39 @@ int kv_result_foreach_error_message(const kv_result* r, uint32_t rule, uint64_t 
     // the element comes out of the JSON context: every number of it is float64 ('%v' 8.08e+06,
     // %T float64)
     JDoc doc;
+    parse_json(element_json, len, NUM_FLOAT, &doc);
+    const std::string m = error_message(q.ps(), q.r->batch_of(*q.part), kv_result::decode(rec), doc);
+    if (m.empty()) return KV_E_INVALID;
+    return put_message(m, buf, cap);
+  });
+}
+
+int kv_result_foreach_alt(const kv_result* r, uint32_t rule, uint64_t res, uint32_t alt, uint32_t* status, char* buf,
+                          size_t cap) {
+  if (!status) return KV_E_INVALID;
+  return guarded(KV_E_INVALID, nullptr, [&]() -> int {
+    const Pair q = pair_of(r, rule, res, false);
+    if (q.code) return q.code;
+    ErrRec8 rec;
+    const int rc = any_alt(q, alt, status, &rec);
+    if (rc) return rc;
+    if (*status != ST_FAIL) return put_message(std::string(), buf, cap);
+    // (the alternative's pattern nodes start at its own root: the path is relative to the element)
+    return put_message(render_path(q.ps(), q.r->batch_of(*q.part), kv_result::decode(rec)), buf, cap);
+  });
+}
+
+int kv_result_foreach_alt_error_message(const kv_result* r, uint32_t rule, uint64_t res, uint32_t alt,
+                                        const char* element_json, size_t len, char* buf, size_t cap) {
+  if (!element_json) return KV_E_INVALID;
+  return guarded(KV_E_PARSE, nullptr, [&]() -> int {
+    const Pair q = pair_of(r, rule, res, false);
+    if (q.code) return q.code;
+    uint32_t status;
+    ErrRec8 rec;
+    const int rc = any_alt(q, alt, &status, &rec);
+    if (rc) return rc;
+    JDoc doc;  // (every number of the element float64, as kv_result_foreach_error_message)
     parse_json(element_json, len, NUM_FLOAT, &doc);
     const std::string m = error_message(q.ps(), q.r->batch_of(*q.part), kv_result::decode(rec), doc);
     if (m.empty()) return KV_E_INVALID;
@@ -746,7 +827,7 @@ int kv_batch_foreach_fold(const kv_policyset* ps, const kv_batch* b, uint32_t se
                           uint64_t n) {
   if (!ps || !b || !status) return KV_E_INVALID;
   if (set >= ps->ps.fsets.size() || n != b->b.res.size()) return KV_E_RANGE;
-  if (ps->ps.fsets[set].pattern) return KV_E_INVALID;  // (a pattern set has no host evaluator)
+  if (ps->ps.fsets[set].pattern || ps->ps.fsets[set].any) return KV_E_INVALID;  // (no host evaluator)
   return guarded(KV_E_INVALID, nullptr, [&]() -> int {
     FeHost h;
     build_foreach(ps->ps, b->b, &h);
@@ -788,7 +869,7 @@ int kv_batch_foreach_chain_fold(const kv_policyset* ps, const kv_batch* b, uint3
   if (!ps || !b || !status) return KV_E_INVALID;
   if (chain >= ps->ps.fe_chains.size() || n != b->b.res.size()) return KV_E_RANGE;
   for (uint32_t s : ps->ps.fe_chains[chain])
-    if (ps->ps.fsets[s].pattern) return KV_E_INVALID;  // (a pattern set has no host evaluator)
+    if (ps->ps.fsets[s].pattern || ps->ps.fsets[s].any) return KV_E_INVALID;  // (no host evaluator)
   return guarded(KV_E_INVALID, nullptr, [&]() -> int {
     FeHost h;
     build_foreach(ps->ps, b->b, &h);
@@ -810,7 +891,7 @@ int kv_batch_foreach_chain_message(const kv_policyset* ps, const kv_batch* b, ui
   if (!ps || !b) return KV_E_INVALID;
   if (chain >= ps->ps.fe_chains.size() || res >= b->b.res.size()) return KV_E_RANGE;
   for (uint32_t s : ps->ps.fe_chains[chain])
-    if (ps->ps.fsets[s].pattern) return KV_E_INVALID;
+    if (ps->ps.fsets[s].pattern || ps->ps.fsets[s].any) return KV_E_INVALID;
   return guarded(KV_E_INVALID, nullptr, [&]() -> int {
     const FeHost& h = const_cast<kv_batch*>(b)->fe_host(ps->ps);
     const std::vector<uint32_t>& order = b->b.order;  // store index -> caller index (empty: identity)
@@ -840,6 +921,7 @@ int kv_batch_foreach_tables(const kv_policyset* ps, const kv_batch* b, char** ou
     };
     for (const std::vector<uint32_t>* v :
          {&h.sets, &h.lists, &h.el_res, &h.el_ord, &h.lstate, &h.first, &h.pats, &h.chain, &h.chains, &h.chain_ents,
+          &h.anys, &h.any_alts,
           &h.gate.sets, &h.gate.ents, &h.deny.sets, &h.deny.ents, &h.deny.outc, &h.deny.truth, &h.deny.unk, &h.deny.err,
           &h.deny.oos})
       put(*v);
@@ -851,6 +933,21 @@ int kv_batch_foreach_tables(const kv_policyset* ps, const kv_batch* b, char** ou
     *len = o.size();
     return 0;
   });
+}
+
+int kv_rule_foreach_anypattern(const kv_policyset* ps, uint32_t rule, uint32_t* n_alts) {
+  if (!ps || !n_alts) return KV_E_INVALID;
+  if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
+  const uint32_t fs = ps->ps.rhost[rule].foreach_set;
+  *n_alts = fs && ps->ps.fsets[fs - 1].any ? (uint32_t)ps->ps.fsets[fs - 1].alt_prog.size() : 0u;
+  return 0;
+}
+
+int kv_foreach_set_alternatives(const kv_policyset* ps, uint32_t set, uint32_t* n) {
+  if (!ps || !n) return KV_E_INVALID;
+  if (set >= ps->ps.fsets.size()) return KV_E_RANGE;
+  *n = ps->ps.fsets[set].any ? (uint32_t)ps->ps.fsets[set].alt_prog.size() : 0u;
+  return 0;
 }
 
 int kv_foreach_set_pattern(const kv_policyset* ps, uint32_t set, uint32_t* on) {

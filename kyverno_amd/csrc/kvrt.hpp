@@ -179,6 +179,12 @@ struct ResultPart {
   // Rules of several entries (KV_COMPILE_FOREACH_ENTRIES; fetched with the statuses), in store
   // order: [chain][n] the chain key (kvforeach.h kv_fe_chain: the deciding entry, element and code)
   HostArray<uint32_t> fe_ckey;
+  // Any sets of foreach rules (KV_COMPILE_FOREACH_ANYPATTERN; fetched with the statuses), in store
+  // order: [any set][n] the reduction key and the deciding element's code word (kvforeach.h: 4
+  // bits per alternative), [alternative][n] that element's record per alternative (alternatives
+  // numbered through the any sets in order)
+  HostArray<uint32_t> fe_akey, fe_acode;
+  HostArray<ErrRec8> fe_arec;
   // statuses [lo, lo + n) of rule `rule` from the transfer form into dst[0, n)
   void unpack_row(uint32_t rule, uint8_t* dst) const;
   uint64_t n_rec() const { return base.empty() ? 0 : base.back(); }

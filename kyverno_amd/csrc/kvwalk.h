@@ -3,7 +3,8 @@
 //   kv_validate_kernel (ELEM = false): a lane is a resource, the root its root node;
 //   kv_foreach_pat_kernel (ELEM = true, KV_COMPILE_FOREACH_PATTERN): a lane is an element of a
 //   foreach list, the root that element's node (MatchPattern(element, pattern): the element map
-//   as the whole resource), and the host harness tools/kvemu (a one-lane wave).
+//   as the whole resource), kv_foreach_any_kernel (KV_COMPILE_FOREACH_ANYPATTERN: the same, once per
+//   alternative of an anyPattern entry), and the host harness tools/kvemu (a one-lane wave).
 // Lanes that skip a subtree (absent anchored key) or raise an error park on a wake-up pc (the scope
 // end / catch point) instead of branching, so the wave never diverges in program position; loops
 // over resource arrays run max(len) uniform iterations with the counter in LDS per wave.
@@ -299,27 +300,22 @@ __device__ __forceinline__ void kv_walk(const DevPS& P, const DevBatch& B, const
   }
 }
 
-// One lane of kv_foreach_pat_kernel (shared with the host harness): element e of the list of
-// pattern set p (valid: e is below the list's element count; the other lanes go through the walk
-// parked). Returns the element's code and, for ST_FAIL / ST_ERROR, the 8-byte record words in *w;
-// *res / *ord: the element's store resource and its index in its list (0xFFFFFFFF / 0 for a lane
-// that is not valid). Needs kvblocks.h and kvforeach.h.
+// The gate and the element's node of element e of foreach set s, whose list's path is steps
+// [c0, c0 + cn) of `chain` (FePatTables::chain): one copy for kv_fe_pat_lane and kv_fe_any_lane.
+// valid: e is below the list's element count. Returns 0 with *run set where the walk may start
+// at *root, else the element's code with *run clear (the lane goes through the walk parked):
 //  1. the entry gate (kv_cond_fold<false>): not met ST_SKIP, undecided ST_CPU;
-//  2. the element's node: from the resource's root along the list's path (FePatTables::chain: a
-//     slot or key-id lookup per field, child k per index); the node the path ends in is the list
-//     and the element its child `ord`, or a single map, the one element itself (the one-element
-//     rule of evaluateList; behind a field step its trie node carries the element node's keys,
-//     kvcompile.cpp). Anything else, a list behind an index step included, is ST_CPU;
-//  3. the pattern walk with that node as the root; ST_CPU when the int64 / float64 typing of a
-//     number could change the verdict (above) or the record does not fit 8 bytes (which includes
-//     the stale counter of a finished loop, below).
-__device__ __forceinline__ uint32_t kv_fe_pat_lane(const FeTables& T, const FePatTables& Q, const DevPS& P,
-                                                   const DevBatch& B, const Node* __restrict__ N, uint32_t p, uint32_t e,
-                                                   bool valid, uint32_t n_res, uint32_t (*s_cur)[KV_WG],
-                                                   uint32_t (*s_lfirst)[KV_WG], uint32_t (*s_llen)[KV_WG],
-                                                   uint32_t (*s_li)[KV_MAXL], uint32_t* res_o, uint32_t* ord_o, uint2* w) {
-  const uint32_t* PT = Q.pats + 4u * p;
-  const uint32_t s = uni(PT[0]);
+//  2. the element's node: from the resource's root along the list's path (a slot or key-id lookup
+//     per field, child k per index); the node the path ends in is the list and the element its
+//     child `ord`, or a single map, the one element itself (the one-element rule of evaluateList;
+//     behind a field step its trie node carries the element node's keys, kvcompile.cpp). Anything
+//     else, a list behind an index step included, is ST_CPU.
+// *res / *ord: the element's store resource and its index in its list (0xFFFFFFFF / 0 for a lane
+// that is not valid); *rl: the resource's lane in its rows.
+__device__ __forceinline__ uint32_t kv_fe_elem_root(const FeTables& T, const uint32_t* __restrict__ chain, const DevBatch& B,
+                                                    const Node* __restrict__ N, uint32_t s, uint32_t c0, uint32_t cn,
+                                                    uint32_t e, bool valid, uint32_t n_res, uint32_t* res_o, uint32_t* ord_o,
+                                                    uint32_t* rl_o, uint32_t* root_o, bool* run_o) {
   const uint32_t* L = T.lists + 4u * T.sets[4u * s];
   const uint32_t n_el = L[1], el0 = L[3];
   uint32_t res = 0xFFFFFFFFu, ord = 0, code = ST_SKIP, rl = 0, root = ABSENT;
@@ -336,10 +332,9 @@ __device__ __forceinline__ uint32_t kv_fe_pat_lane(const FeTables& T, const FePa
     if (!code) {
       rl = res & (KV_LANES - 1u);
       uint32_t node = B.res[res].root * KV_LANES + rl;
-      const uint32_t c0 = uni(PT[2]), cn = uni(PT[3]);
       uint32_t last = FE_STEP_SLOT;
       for (uint32_t k = 0; k < cn && node != ABSENT; k++) {
-        const uint32_t kind = Q.chain[2u * (c0 + k)], val = Q.chain[2u * (c0 + k) + 1u];
+        const uint32_t kind = chain[2u * (c0 + k)], val = chain[2u * (c0 + k) + 1u];
         last = kind;
         if (kind == FE_STEP_INDEX) {
           const Node n = N[node];
@@ -361,6 +356,33 @@ __device__ __forceinline__ uint32_t kv_fe_pat_lane(const FeTables& T, const FePa
       if (!run) code = ST_CPU;
     }
   }
+  *res_o = res;
+  *ord_o = ord;
+  *rl_o = rl;
+  *root_o = root;
+  *run_o = run;
+  return code;
+}
+
+// One lane of kv_foreach_pat_kernel (shared with the host harness): element e of the list of
+// pattern set p (valid: e is below the list's element count; the other lanes go through the walk
+// parked). Returns the element's code and, for ST_FAIL / ST_ERROR, the 8-byte record words in *w;
+// *res / *ord: the element's store resource and its index in its list (0xFFFFFFFF / 0 for a lane
+// that is not valid). Needs kvblocks.h and kvforeach.h.
+//  1. 2. the entry gate and the element's node (kv_fe_elem_root);
+//  3. the pattern walk with that node as the root; ST_CPU when the int64 / float64 typing of a
+//     number could change the verdict (above) or the record does not fit 8 bytes (which includes
+//     the stale counter of a finished loop, below).
+__device__ __forceinline__ uint32_t kv_fe_pat_lane(const FeTables& T, const FePatTables& Q, const DevPS& P,
+                                                   const DevBatch& B, const Node* __restrict__ N, uint32_t p, uint32_t e,
+                                                   bool valid, uint32_t n_res, uint32_t (*s_cur)[KV_WG],
+                                                   uint32_t (*s_lfirst)[KV_WG], uint32_t (*s_llen)[KV_WG],
+                                                   uint32_t (*s_li)[KV_MAXL], uint32_t* res_o, uint32_t* ord_o, uint2* w) {
+  const uint32_t* PT = Q.pats + 4u * p;
+  const uint32_t s = uni(PT[0]);
+  uint32_t res, ord, rl, root;
+  bool run;
+  uint32_t code = kv_fe_elem_root(T, Q.chain, B, N, s, uni(PT[2]), uni(PT[3]), e, valid, n_res, &res, &ord, &rl, &root, &run);
   // the wave's loop counters start at zero: an error raised outside a loop records them, and
   // what an earlier program (or kernel) left there must not make the record look too wide.
   // Within one program a finished loop leaves its last index in its counter, and a later error
@@ -381,5 +403,65 @@ __device__ __forceinline__ uint32_t kv_fe_pat_lane(const FeTables& T, const FePa
   }
   *res_o = res;
   *ord_o = ord;
+  return code;
+}
+
+// One lane of kv_foreach_any_kernel (KV_COMPILE_FOREACH_ANYPATTERN; shared with the host harness):
+// element e of the list of any set a, after the gate and the node lookup of kv_fe_elem_root. The
+// set's alternatives are tried in order as validate() does (validation.go:447-489): each is a
+// plain pattern program walked with the element as the root, for the lanes still undecided. The
+// alternative count is the same for the whole launch row, and the walk holds wave operations, so
+// every lane goes through every call: decided lanes, lanes past the list's end and lanes without
+// an element node go parked, and a parked lane's `cpu` and `st` are not read. Per alternative of
+// a running lane: the typing guard or ST_CPU makes the element ST_CPU; ST_PASS makes it ST_PASS
+// (the later alternatives are not evaluated, so their guard does not count); otherwise (FAIL /
+// ERROR / SKIP of that alternative: each is a PatternError the message names) its 8-byte record
+// goes to rec[k * stride] and its status into bits [4k, 4k + 4) of the code word; a record that
+// does not fit 8 bytes makes the element ST_CPU. A lane undecided after the last alternative is
+// ST_FAIL. The wave's loop counters are cleared before every alternative: a finished loop of
+// alternative k leaves its last index there, and an error of alternative k + 1 outside any loop
+// would record it (a wrong path, or a record that looks wide).
+__device__ __forceinline__ uint32_t kv_fe_any_lane(const FeTables& T, const FeAnyTables& A, const DevPS& P,
+                                                   const DevBatch& B, const Node* __restrict__ N, uint32_t a, uint32_t e,
+                                                   bool valid, uint32_t n_res, uint32_t (*s_cur)[KV_WG],
+                                                   uint32_t (*s_lfirst)[KV_WG], uint32_t (*s_llen)[KV_WG],
+                                                   uint32_t (*s_li)[KV_MAXL], uint32_t* res_o, uint32_t* ord_o, uint32_t* cw_o,
+                                                   uint2* __restrict__ rec, size_t stride) {
+  const uint32_t* AT = A.anys + 8u * a;
+  const uint32_t s = uni(AT[0]), a0 = uni(AT[1]), na = uni(AT[2]);
+  uint32_t res, ord, rl, root;
+  bool open;  // the lane is still undecided
+  uint32_t code = kv_fe_elem_root(T, A.chain, B, N, s, uni(AT[3]), uni(AT[4]), e, valid, n_res, &res, &ord, &rl, &root, &open);
+  uint32_t cw = 0;
+  for (uint32_t k = 0; k < na; k++) {
+    if ((threadIdx.x & 63u) == 0u)
+      for (uint32_t j = 0; j < KV_MAXL; j++) s_li[threadIdx.x >> 6][j] = 0u;
+    uint32_t st = ST_CPU;
+    EState es{0, 0, 0, ABSENT, ABSENT, 0, 0, 0, 0};
+    bool cpu = false;
+    kv_walk<true>(P, B, N, A.alts + a0 + k, root, open, res, n_res, rl, s_cur, s_lfirst, s_llen, s_li, st, es, cpu);
+    if (open) {
+      if (cpu || st == ST_CPU) {
+        code = ST_CPU;
+        open = false;
+      } else if (st == ST_PASS) {
+        code = ST_PASS;
+        open = false;
+      } else {
+        const uint2 w = err8_pack(es.kind, es.flags, es.pn, es.key, es.i0, es.i1, es.i2, es.i3, rl);
+        if (w.x & ERR8_WIDE) {
+          code = ST_CPU;
+          open = false;
+        } else {
+          rec[k * stride] = w;
+          cw |= st << (4u * k);
+        }
+      }
+    }
+  }
+  if (open) code = ST_FAIL;
+  *res_o = res;
+  *ord_o = ord;
+  *cw_o = code == ST_FAIL ? cw : 0u;
   return code;
 }

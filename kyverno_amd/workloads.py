@@ -223,6 +223,24 @@ def c2_foreach_pattern_policies() -> list[dict]:
     return pols
 
 
+def c2_foreach_anypattern_policies() -> list[dict]:
+    """The any twin of ``c2_foreach_pattern_policies``: the same 100 rules with rule i's entry turned
+    into ``anyPattern: [pattern i mod 8, pattern (i + 1) mod 8]``, to be compiled with
+    ``PolicySet(..., foreach=True, foreach_pattern=True, foreach_anypattern=True)``: 8 any sets of 2
+    alternatives, the workload of the any sets' measurement (DESIGN.md §3 *anyPattern entries*)."""
+    import copy
+
+    n = len(C2_FOREACH_PATTERNS)
+    pols = c2_policies()
+    for i, r in enumerate(pols[0]["spec"]["rules"]):
+        r["validate"] = {"message": r["validate"].get("message", ""),
+                         "foreach": [{"list": "request.object.spec.containers",
+                                      "anyPattern": [copy.deepcopy(C2_FOREACH_PATTERNS[i % n]),
+                                                     copy.deepcopy(C2_FOREACH_PATTERNS[(i + 1) % n])]}]}
+    pols[0]["metadata"]["name"] = "c2-pod-rules-foreach-anypattern"
+    return pols
+
+
 def c2_foreach_chain_policies() -> list[dict]:
     """The chain twin of ``c2_foreach_policies``: the same 100 rules with each rule's entry doubled
     into a ``containers`` entry and an ``initContainers`` entry with the same ``deny`` block (rule i:

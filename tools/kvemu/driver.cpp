@@ -51,6 +51,9 @@ extern "C" void kvemu_mfac(const DevPS* P, const DevBatch* B, uint32_t* mtup);
 // the pattern sets' rows of the foreach plane (fepat.cpp: kvwalk.h as a one-lane wave)
 extern "C" void kvemu_foreach_pat(const FeTables* T, const FePatTables* Q, const DevPS* P, const DevBatch* B,
                                   uint32_t n_res, uint8_t* fe_st);
+// ... and the any sets' (KV_COMPILE_FOREACH_ANYPATTERN)
+extern "C" void kvemu_foreach_any(const FeTables* T, const FeAnyTables* A, const DevPS* P, const DevBatch* B,
+                                  uint32_t n_res, uint8_t* fe_st);
 typedef void (*chunk_fn)(const DevPS*, const DevBatch*, const Node*, const Val*, const uint8_t*, DevOut, uint32_t);
 
 static std::string slurp(const char* p) {
@@ -251,12 +254,17 @@ int main(int argc, char** argv) {
       for (size_t s = 0; s < n_dn; s++)
         for (uint32_t r = 0; r < B.n_res; r++) deny_st[s * B.n_res + r] = deny_status_host(dn, (uint32_t)s, B.n_res, r);
       for (size_t s = 0; s < n_fe; s++)
-        for (uint32_t r = 0; r < B.n_res && !ps.fsets[s].pattern; r++)
+        for (uint32_t r = 0; r < B.n_res && !ps.fsets[s].pattern && !ps.fsets[s].any; r++)
           deny_st[(n_dn + s) * B.n_res + r] = foreach_fold_host(fe, (uint32_t)s, B.n_res, r, nullptr);
       if (!ps.fpats.empty()) {  // (as launch_foreach: the pattern sets' elements through the pattern walk)
         const FeTables ft = fe.view();
         const FePatTables qt = fe.pat_view();
         kvemu_foreach_pat(&ft, &qt, &P, &B, B.n_res, deny_st.data() + n_dn * B.n_res);
+      }
+      if (!ps.fanys.empty()) {  // (as launch_foreach: the any sets' elements through their alternatives)
+        const FeTables ft = fe.view();
+        const FeAnyTables at = fe.any_view();
+        kvemu_foreach_any(&ft, &at, &P, &B, B.n_res, deny_st.data() + n_dn * B.n_res);
       }
       if (n_ch) {  // (as kv_foreach_chain_kernel, after the set rows: a key per status byte, the element left out)
         std::vector<uint32_t> acc(n_fe * B.n_res);

@@ -1,5 +1,5 @@
 // kvemu: host build of the pattern walk (kvwalk.h: the interpreter loop of kv_validate_kernel and
-// the per-lane body of kv_foreach_pat_kernel) as a one-lane wave, with the prelude the specialized
+// the per-lane bodies of kv_foreach_pat_kernel and kv_foreach_any_kernel) as a one-lane wave, with the prelude the specialized
 // kernels see: the pattern sets' rows of the deny plane (KV_COMPILE_FOREACH_PATTERN), element by
 // element, reduced as kv_foreach_elem_kernel's keys are and finished as kv_foreach_fin_kernel does.
 #include "shim.h"
@@ -27,6 +27,30 @@ extern "C" void kvemu_foreach_pat(const FeTables* T, const FePatTables* Q, const
       uint2 w{0u, 0u};
       const uint32_t code = kv_fe_pat_lane(*T, *Q, *P, *B, B->nodes, p, e, true, n_res, s_cur, s_lfirst, s_llen, s_li, &res,
                                            &ord, &w);
+      if (res < n_res) key[res] = std::min(key[res], kv_fe_key(code, ord));
+    }
+    for (uint32_t r = 0; r < n_res; r++)
+      fe_st[(size_t)s * n_res + r] = (uint8_t)kv_fe_final(T->lstate[(size_t)list * n_res + r], key[r]);
+  }
+}
+
+// fe_st[set][res] of every any set of A (KV_COMPILE_FOREACH_ANYPATTERN): the lane body of
+// kv_foreach_any_kernel per element, the records of one element at a time
+extern "C" void kvemu_foreach_any(const FeTables* T, const FeAnyTables* A, const DevPS* P, const DevBatch* B,
+                                  uint32_t n_res, uint8_t* fe_st) {
+  static thread_local uint32_t s_cur[KV_MAXD][KV_WG], s_lfirst[KV_MAXL][KV_WG], s_llen[KV_MAXL][KV_WG],
+      s_li[KV_WG / 64][KV_MAXL];
+  threadIdx.x = 0;
+  std::vector<uint32_t> key(n_res);
+  for (uint32_t a = 0; a < A->n_anys; a++) {
+    const uint32_t s = A->anys[8u * a], list = T->sets[4u * s];
+    const uint32_t n_el = T->lists[4u * list + 1u];
+    std::fill(key.begin(), key.end(), FE_KEY_NONE);
+    for (uint32_t e = 0; e < n_el; e++) {
+      uint32_t res, ord, cw;
+      uint2 rec[FE_MAX_ALTS];
+      const uint32_t code = kv_fe_any_lane(*T, *A, *P, *B, B->nodes, a, e, true, n_res, s_cur, s_lfirst, s_llen, s_li, &res,
+                                           &ord, &cw, rec, 1);
       if (res < n_res) key[res] = std::min(key[res], kv_fe_key(code, ord));
     }
     for (uint32_t r = 0; r < n_res; r++)
