@@ -68,7 +68,8 @@ enum {
   /* also evaluate validate.foreach entries that carry a `pattern` on the device (opt-in; needs
    * KV_COMPILE_FOREACH, else kv_compile returns KV_E_INVALID; without it such a rule is
    * KV_ROUTE_CPU, reason "foreach"). In scope: one entry {list, preconditions?, pattern}, the
-   * pattern a map without {{ }} variables and without a `metadata` key, inside what the pattern
+   * pattern a map without {{ }} variables (KV_COMPILE_FOREACH_PATVARS lifts that) and without a
+   * `metadata` key, inside what the pattern
    * compiler accepts for a rule's pattern. Per element the pattern is matched with the element as
    * the whole resource (validate.MatchPattern): no error is PASS, a conditional / global anchor
    * skip is SKIP (ignored by foreach), an error without a path ERROR, any other FAIL with a path
@@ -103,7 +104,23 @@ enum {
    * (kv_result_foreach_alt). An element is CPU where an alternative up to and including the
    * first that passes meets the typing guard of pattern entries or a record that does not fit
    * 8 bytes. */
-  KV_COMPILE_FOREACH_ANYPATTERN = 32
+  KV_COMPILE_FOREACH_ANYPATTERN = 32,
+  /* also evaluate validate.foreach entries whose `pattern` (or, with KV_COMPILE_FOREACH_ANYPATTERN,
+   * `anyPattern`) holds {{ }} variables on the device (opt-in; needs KV_COMPILE_FOREACH |
+   * KV_COMPILE_FOREACH_PATTERN, else kv_compile returns KV_E_INVALID; composes with the anyPattern
+   * and entries flags; without it such a rule is KV_ROUTE_CPU, reason "foreach"). In scope: string
+   * values holding {{element<field / quoted-field / index chain>}} and {{request.object<chain>}},
+   * as the whole string (the value keeps its JSON type, numbers float64) or inside one (spliced
+   * text), several per string. Outside it: a variable in a map key, {{element}} alone, {{@}},
+   * functions, nested variables, \{{ escapes, a $() reference that brings a variable in. Per
+   * element, after the entry's preconditions, the whole pattern (every alternative of an
+   * anyPattern, alternative 0's strings first) is substituted in the element's context (in a rule
+   * of several entries: the element over the last elements of the lists before it): the first
+   * string in traversal order that does not resolve makes the element ERROR "variable substitution
+   * failed: <err>" (kv_result_foreach_subst_error), one outside the resolver's scope CPU, else a
+   * map or an array in a leaf's place CPU; then the substituted pattern is matched against the
+   * element. The typing guard of pattern entries is decided per substituted value. */
+  KV_COMPILE_FOREACH_PATVARS = 64
 };
 
 /* kv_validate modes (bit set). KV_MODE_SCOPES adds per-scope counts
@@ -377,6 +394,24 @@ int kv_result_foreach_alt(const kv_result* r, uint32_t rule, uint64_t res, uint3
                           size_t cap);
 int kv_result_foreach_alt_error_message(const kv_result* r, uint32_t rule, uint64_t res, uint32_t alt,
                                         const char* element_json, size_t len, char* buf, size_t cap);
+/* Pattern variables in entries (KV_COMPILE_FOREACH_PATVARS). kv_rule_foreach_patvars: *on = 1
+ * for a device foreach rule with an entry whose pattern or alternatives hold variable strings,
+ * else 0. kv_result_foreach_subst_error: for an ERROR pair whose deciding element failed the
+ * substitution of its entry's pattern, "validation failed in foreach rule for variable
+ * substitution failed: <err>" (the RuleResponse message), recomputed on the host from that
+ * element's outcome row; returns its length, 0 for every other pair (an ERROR the pattern walk
+ * gave is kv_result_foreach_error_message's). kv_result_foreach_error_message and
+ * kv_result_foreach_alt_error_message render the deciding element's substituted value at a
+ * dynamic leaf. kv_batch_foreach_subst (diagnostics and tests, as kv_batch_foreach_fold and
+ * kv_batch_foreach_chain_fold: not part of the evaluation path): the substitution verdict of element `elem` of caller
+ * resource `res` under the pattern strings of foreach set `set` on the host (no GPU; the function
+ * the kernels run): *code = 0, the ERROR or the CPU status code, and for ERROR the <err> text in
+ * buf; returns its length, KV_E_INVALID for a set without variable strings, KV_E_RANGE for an
+ * element the resource's list does not have. */
+int kv_rule_foreach_patvars(const kv_policyset* ps, uint32_t rule, uint32_t* on);
+int kv_result_foreach_subst_error(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap);
+int kv_batch_foreach_subst(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint64_t res, uint32_t elem,
+                           uint32_t* code, char* buf, size_t cap);
 double kv_result_kernel_ms(const kv_result* r);
 
 /* Bulk export of the failing pairs (KV_MODE_ERRORS): every FAIL / ERROR / SKIP pair,

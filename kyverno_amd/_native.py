@@ -110,6 +110,9 @@ def lib():
         L.kv_foreach_set_alternatives.argtypes = [vp, u32, ctypes.POINTER(u32)]
         L.kv_result_foreach_alt.argtypes = [vp, u32, u64, u32, ctypes.POINTER(u32), ctypes.c_char_p, sz]
         L.kv_result_foreach_alt_error_message.argtypes = [vp, u32, u64, u32, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
+        L.kv_rule_foreach_patvars.argtypes = [vp, u32, ctypes.POINTER(u32)]
+        L.kv_result_foreach_subst_error.argtypes = [vp, u32, u64, ctypes.c_char_p, sz]
+        L.kv_batch_foreach_subst.argtypes = [vp, vp, u32, u64, u32, ctypes.POINTER(u32), ctypes.c_char_p, sz]
         L.kv_result_kernel_ms.argtypes = [vp]
         L.kv_result_kernel_ms.restype = ctypes.c_double
         L.kv_bench.argtypes = [vp, vp, ctypes.c_char_p, i32, u32, i32, i32, ctypes.POINTER(ctypes.c_double), errpp]
@@ -161,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "kv_batch_foreach_tables",
     "kv_rule_foreach_anypattern", "kv_foreach_set_alternatives", "kv_result_foreach_alt",
     "kv_result_foreach_alt_error_message",
+    "kv_rule_foreach_patvars", "kv_result_foreach_subst_error", "kv_batch_foreach_subst",
     "kv_bench", "kv_synth", "kv_synth_range", "kv_free_policyset", "kv_free_batch", "kv_free_result", "kv_free_error",
     "kv_free_buffer", "kv_session_create", "kv_session_run", "kv_session_counts", "kv_free_session",
     "kv_session_scope_counts", "kv_result_scope_counts", "kv_batch_namespaces", "kv_batch_namespace",

@@ -45,6 +45,7 @@ MODE_STATUS, MODE_ERRORS, MODE_COUNTS, MODE_SCOPES = 1, 2, 4, 8
 COMPILE_SPECIALIZE, COMPILE_DENY, COMPILE_FOREACH, COMPILE_FOREACH_PATTERN = 1, 2, 4, 8
 COMPILE_FOREACH_ENTRIES = 16
 COMPILE_FOREACH_ANYPATTERN = 32
+COMPILE_FOREACH_PATVARS = 64
 ROUTE_GPU, ROUTE_CPU, ROUTE_NORESPONSE, ROUTE_CONSTANT = range(4)
 
 
@@ -85,6 +86,7 @@ class Rule:
     foreach_pattern: bool = False  # ... whose entry carries a pattern (PolicySet(foreach_pattern=True))
     foreach_entries: int = 0  # ... of several entries: their number (PolicySet(foreach_entries=True)), else 0
     foreach_anypattern: int = 0  # ... whose one entry carries an anyPattern: its alternatives (PolicySet(foreach_anypattern=True))
+    foreach_patvars: bool = False  # ... with variable strings in an entry's pattern (PolicySet(foreach_patvars=True))
 
 
 class PolicySet:
@@ -119,10 +121,18 @@ class PolicySet:
     ``anyPattern`` a list of 1 to 8 maps, each within the limits of a pattern entry. An element
     passes when one alternative matches; ``Result.foreach_alt`` gives every alternative's outcome on
     the deciding element of a FAIL pair. Without it such a rule stays CPU-routed, reason ``"foreach"``.
+
+    ``foreach_patvars=True`` (``KV_COMPILE_FOREACH_PATVARS``, opt-in, needs ``foreach`` and
+    ``foreach_pattern``; composes with the other two) also routes entries whose ``pattern`` (or
+    ``anyPattern``) holds ``{{element...}}`` / ``{{request.object...}}`` variables in its string
+    values. Per element the pattern is substituted first: an unresolved variable makes the element
+    ``ERROR`` (``Result.foreach_subst_error``), then the substituted pattern is matched against the
+    element. Without it such a rule stays CPU-routed, reason ``"foreach"``.
     """
 
     def __init__(self, policies, specialize: bool = False, deny: bool = False, foreach: bool = False,
-                 foreach_pattern: bool = False, foreach_entries: bool = False, foreach_anypattern: bool = False):
+                 foreach_pattern: bool = False, foreach_entries: bool = False, foreach_anypattern: bool = False,
+                 foreach_patvars: bool = False):
         L = lib()
         data = _dumps(policies)
         h = ctypes.c_void_p()
@@ -130,7 +140,8 @@ class PolicySet:
         flags = ((COMPILE_SPECIALIZE if specialize else 0) | (COMPILE_DENY if deny else 0)
                  | (COMPILE_FOREACH if foreach else 0) | (COMPILE_FOREACH_PATTERN if foreach_pattern else 0)
                  | (COMPILE_FOREACH_ENTRIES if foreach_entries else 0)
-                 | (COMPILE_FOREACH_ANYPATTERN if foreach_anypattern else 0))
+                 | (COMPILE_FOREACH_ANYPATTERN if foreach_anypattern else 0)
+                 | (COMPILE_FOREACH_PATVARS if foreach_patvars else 0))
         check(L.kv_compile(data, len(data), flags, ctypes.byref(h), ctypes.byref(err)), err)
         self._h = h
         self.specialize = specialize
@@ -139,6 +150,7 @@ class PolicySet:
         self.foreach_pattern = foreach_pattern
         self.foreach_entries = foreach_entries
         self.foreach_anypattern = foreach_anypattern
+        self.foreach_patvars = foreach_patvars
         np_, nr = ctypes.c_uint32(), ctypes.c_uint32()
         L.kv_policyset_info(h, ctypes.byref(np_), ctypes.byref(nr))
         self.n_policies, self.n_rules = np_.value, nr.value
@@ -158,6 +170,8 @@ class PolicySet:
             self.rules[-1].foreach_pattern = on.value != 0
             L.kv_rule_foreach_anypattern(h, i, ctypes.byref(on))
             self.rules[-1].foreach_anypattern = on.value
+            L.kv_rule_foreach_patvars(h, i, ctypes.byref(on))
+            self.rules[-1].foreach_patvars = on.value != 0
             ch, ne = ctypes.c_uint32(), ctypes.c_uint32()
             L.kv_rule_foreach_chain(h, i, ctypes.byref(ch), ctypes.byref(ne))
             if ch.value:  # (kv_rule_info.foreach_set stays 0 for a rule of several entries)
@@ -299,6 +313,21 @@ class PolicySet:
             elif rc != 0:
                 raise RuntimeError(f"kv_batch_foreach_chain_fold: code {rc}")
         return st, en, el
+
+    def foreach_subst(self, b: "Batch", fset: int, res: int, elem: int) -> tuple[int, str | None]:
+        """Diagnostics: the substitution verdict of element ``elem`` of resource ``res`` under the pattern strings of
+        foreach set ``fset`` (``foreach_patvars=True``) on the host (``kv_batch_foreach_subst``, no GPU;
+        the function the kernels run): (0 | ERROR | CPU, the error text of an ERROR)."""
+        code = ctypes.c_uint32()
+        cap = 1024
+        while True:
+            buf = ctypes.create_string_buffer(cap)
+            n = lib().kv_batch_foreach_subst(self._h, b._h, fset, res, elem, ctypes.byref(code), buf, cap)
+            if n < 0:
+                raise RuntimeError(f"kv_batch_foreach_subst: code {n}")
+            if n < cap:
+                return code.value, (buf.raw[:n].decode("utf-8", "replace") if code.value == ERROR else None)
+            cap = n + 1
 
     def foreach_tables(self, b: "Batch") -> bytes:
         """The per-batch foreach tables of ``b`` as the device receives them, as bytes
@@ -538,6 +567,13 @@ class Result:
             doc = doc.encode("utf-8")
         return self._text(lambda h, ru, re_, *a: lib().kv_result_foreach_alt_error_message(h, ru, re_, alt, *a), rule, res,
                           doc, len(doc), errors="replace", empty_ok=True)
+
+    def foreach_subst_error(self, rule: int, res: int) -> str | None:
+        """The RuleResponse message of an ERROR pair of a device foreach rule whose deciding element
+        failed the substitution of its entry's pattern (``foreach_patvars=True``): "validation failed
+        in foreach rule for variable substitution failed: ..." (``kv_result_foreach_subst_error``),
+        else None."""
+        return self._text(lib().kv_result_foreach_subst_error, rule, res, errors="replace")
 
     def subst_error(self, rule: int, res: int) -> str | None:
         """The RuleResponse message of an ERROR pair caused by the pattern's variables failing to

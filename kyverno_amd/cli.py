@@ -31,10 +31,13 @@ whose conditions are of those forms on the device, with the messages of ``valida
 (``evaluate(foreach_entries=True)``, ``KV_COMPILE_FOREACH_ENTRIES``; implies ``--device-foreach``) also for
 rules of several entries; ``--device-foreach-anypattern`` (``evaluate(foreach_anypattern=True)``,
 ``KV_COMPILE_FOREACH_ANYPATTERN``; implies ``--device-foreach-pattern`` and ``--device-foreach``) also for
-entries that carry an ``anyPattern``, with the message of ``buildAnyPatternErrorMessage``.
+entries that carry an ``anyPattern``, with the message of ``buildAnyPatternErrorMessage``;
+``--device-foreach-patvars`` (``evaluate(foreach_patvars=True)``, ``KV_COMPILE_FOREACH_PATVARS``; implies
+``--device-foreach-pattern`` and ``--device-foreach``) also for entries whose pattern or alternatives hold
+``{{element...}}`` / ``{{request.object...}}`` variables, with the element's "variable substitution failed" error.
 
     python -m kyverno_amd apply policy.yaml -r pods.yaml [--policy-report] [--device N] [--device-deny] [--device-foreach]
-        [--device-foreach-pattern] [--device-foreach-entries] [--device-foreach-anypattern]
+        [--device-foreach-pattern] [--device-foreach-entries] [--device-foreach-anypattern] [--device-foreach-patvars]
     python -m kyverno_amd test test/cli/test/simple
 """
 from __future__ import annotations
@@ -131,7 +134,8 @@ class Evaluation:
 def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messages: bool = True,
              namespace_labels: dict | None = None, specialize: bool = False, gpus: int = 1,
              deny: bool = False, foreach: bool = False, foreach_pattern: bool = False,
-             foreach_entries: bool = False, foreach_anypattern: bool = False) -> Evaluation:
+             foreach_entries: bool = False, foreach_anypattern: bool = False,
+             foreach_patvars: bool = False) -> Evaluation:
     """All (rule, resource) pairs on the GPU (``kv_compile`` → ``kv_ingest`` → ``kv_validate``).
     ``specialize`` selects the per-policy-set specialized kernels (worth their hiprtc compile on
     large batches) over the bytecode interpreter; both write the same statuses and error records.
@@ -142,14 +146,17 @@ def evaluate(policies: list[dict], resources: list[dict], device: int = 0, messa
     ``foreach``) also for entries that carry a ``pattern`` (``KV_COMPILE_FOREACH_PATTERN``),
     ``foreach_entries`` (which implies ``foreach`` too) also for rules of several entries
     (``KV_COMPILE_FOREACH_ENTRIES``), ``foreach_anypattern`` (which implies ``foreach_pattern`` and
-    ``foreach``) also for entries that carry an ``anyPattern`` (``KV_COMPILE_FOREACH_ANYPATTERN``)."""
+    ``foreach``) also for entries that carry an ``anyPattern`` (``KV_COMPILE_FOREACH_ANYPATTERN``),
+    ``foreach_patvars`` (which implies ``foreach_pattern`` and ``foreach``) also for entries whose
+    pattern or alternatives hold ``{{element...}}`` / ``{{request.object...}}`` variables
+    (``KV_COMPILE_FOREACH_PATVARS``)."""
     from . import batch
 
-    foreach_pattern = foreach_pattern or foreach_anypattern
+    foreach_pattern = foreach_pattern or foreach_anypattern or foreach_patvars
     ps = batch.PolicySet(policies, specialize=specialize, deny=deny,
                          foreach=foreach or foreach_pattern or foreach_entries,
                          foreach_pattern=foreach_pattern, foreach_entries=foreach_entries,
-                         foreach_anypattern=foreach_anypattern)
+                         foreach_anypattern=foreach_anypattern, foreach_patvars=foreach_patvars)
     b = batch.Batch(ps, resources, namespace_labels)
     mask = ((1 << gpus) - 1) << device if gpus > 1 else None
     r = batch.validate(ps, b, device=device, device_mask=mask)
@@ -185,6 +192,12 @@ def collect_errors(ev: Evaluation, ps, r, resources: list) -> None:
             if m is not None:
                 ev.deny[key] = m
                 continue
+            if getattr(ps.rules[ri], "foreach_patvars", False):
+                # the deciding element failed the substitution of its entry's pattern: the whole message
+                m = r.foreach_subst_error(*key)
+                if m is not None:
+                    ev.subst[key] = m
+                    continue
         else:
             m = r.precond_message(*key)
             if m is not None:
@@ -551,20 +564,20 @@ def policy_has_validate(policy: dict) -> bool:
 def apply(policy_paths: list[str], resource_paths: list[str], policy_report: bool = False, device: int = 0,
           out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
           foreach: bool = False, foreach_pattern: bool = False, foreach_entries: bool = False,
-          foreach_anypattern: bool = False) -> tuple[ResultCounts, list]:
+          foreach_anypattern: bool = False, foreach_patvars: bool = False) -> tuple[ResultCounts, list]:
     """applyCommandHelper (apply_command.go:147-310) for resource files. Returns counts and the
     policyreport infos. ``evaluation_fn(policies, resources) -> Evaluation`` replaces the device
     evaluation (tests of the host logic)."""
     policies = load_policies(policy_paths)
     resources = load_resources(resource_paths)
     return apply_docs(policies, resources, policy_report, device, out, evaluation_fn, gpus, deny, foreach, foreach_pattern,
-                      foreach_entries, foreach_anypattern)
+                      foreach_entries, foreach_anypattern, foreach_patvars)
 
 
 def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool = False, device: int = 0,
                out=sys.stdout, evaluation_fn=None, gpus: int = 1, deny: bool = False,
           foreach: bool = False, foreach_pattern: bool = False, foreach_entries: bool = False,
-          foreach_anypattern: bool = False) -> tuple[ResultCounts, list]:
+          foreach_anypattern: bool = False, foreach_patvars: bool = False) -> tuple[ResultCounts, list]:
     mutated = autogen.mutate_policies(policies)
     if len(mutated) > 0 and len(resources) > 0:
         msg_p = "1 policy" if len(mutated) <= 1 else f"{len(policies)} policies"
@@ -579,7 +592,8 @@ def apply_docs(policies: list[dict], resources: list[dict], policy_report: bool 
         ev = (evaluation_fn or (lambda p, r: evaluate(p, r, device=device, gpus=gpus, deny=deny, foreach=foreach,
                                                           foreach_pattern=foreach_pattern,
                                                           foreach_entries=foreach_entries,
-                                                          foreach_anypattern=foreach_anypattern)))(active, resources)
+                                                          foreach_anypattern=foreach_anypattern,
+                                                          foreach_patvars=foreach_patvars)))(active, resources)
         for pi, pol in enumerate(active):
             if not policy_has_validate(pol):
                 continue
@@ -696,6 +710,10 @@ def main(argv: list[str] | None = None) -> int:
     a.add_argument("--device-foreach-anypattern", action="store_true",
                    help="also evaluate validate.foreach entries that carry an anyPattern on the GPU "
                         "(KV_COMPILE_FOREACH_ANYPATTERN; implies --device-foreach-pattern and --device-foreach)")
+    a.add_argument("--device-foreach-patvars", action="store_true",
+                   help="also evaluate validate.foreach entries whose pattern holds {{element...}} / {{request.object...}} "
+                        "variables on the GPU (KV_COMPILE_FOREACH_PATVARS; implies --device-foreach-pattern and "
+                        "--device-foreach)")
     t = sub.add_parser("test", help="run tests from a directory holding test.yaml")
     t.add_argument("dir")
     t.add_argument("--device", type=int, default=0)
@@ -704,9 +722,11 @@ def main(argv: list[str] | None = None) -> int:
         try:
             rc, _ = apply(args.policies, args.resource, args.policy_report, args.device, gpus=args.gpus, deny=args.device_deny,
                           foreach=(args.device_foreach or args.device_foreach_pattern or args.device_foreach_entries
-                                   or args.device_foreach_anypattern),
-                          foreach_pattern=args.device_foreach_pattern or args.device_foreach_anypattern,
-                          foreach_entries=args.device_foreach_entries, foreach_anypattern=args.device_foreach_anypattern)
+                                   or args.device_foreach_anypattern or args.device_foreach_patvars),
+                          foreach_pattern=(args.device_foreach_pattern or args.device_foreach_anypattern
+                                           or args.device_foreach_patvars),
+                          foreach_entries=args.device_foreach_entries, foreach_anypattern=args.device_foreach_anypattern,
+                          foreach_patvars=args.device_foreach_patvars)
         except msgvars.MessageVariableError as e:
             # the Go CLI dies in buildErrorMessage (msgRaw.(string), validation.go:519-524): a
             # panic, exit status 2

@@ -75,6 +75,9 @@ struct DevBatchRes {
   // any sets (KV_COMPILE_FOREACH_ANYPATTERN): their two tables (the list paths and `first` are the
   // pattern sets' buffers), fe_acode[any set][res] and fe_arec[alternative][res]
   DevBuf fea[2], feacode, fearec;
+  // variable strings in entries' patterns (KV_COMPILE_FOREACH_PATVARS): the runs, their rows, the M
+  // plane and the int-typing plane of the batch predicate table
+  DevBuf fev[4];
   double pre_ms = 0, deny_ms = 0, fe_ms = 0;
   DevBatch view{};
 };
@@ -406,6 +409,7 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
   DevBuf erec;  // the pattern sets' per-element records: needed until the fold's kernels are done
   FeAnyTables at{};
   DevBuf acode, arec;  // the any sets' per-element code words and records: likewise
+  FeVarTables vt{};
   const uint32_t n_sets = (uint32_t)ps.csets.size(), n_dsets = (uint32_t)ps.dsets.size(),
                  n_fsets = (uint32_t)ps.fsets.size(), n_pats = (uint32_t)ps.fpats.size(),
                  n_anys = (uint32_t)ps.fanys.size(),
@@ -451,6 +455,15 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
       d->feacode.alloc((size_t)n_anys * b.res.size() * sizeof(uint32_t), device);
       d->fearec.alloc(n_alts * b.res.size() * sizeof(ErrRec8), device);
     }
+    // (one source of truth for the launch split: the policy set's counts; tables that disagree
+    // would send sets with variables through the kernels without them)
+    if ((ps.n_vpats || ps.n_vanys) != fh.has_vars())
+      throw std::runtime_error("foreach tables: variable-string runs do not match the policy set");
+    if (ps.n_vpats || ps.n_vanys) {
+      const uint32_t* vp[4];
+      up(d->fev, {&fh.vruns, &fh.vrows, &fh.mpl, &bt->dyn_host(ps).ityp}, vp);
+      vt = FeVarTables{vp[0], vp[1], vp[2], vp[3]};
+    }
     if (n_chains) {
       const uint32_t* cp[2];
       up(d->fec, {&fh.chains, &fh.chain_ents}, cp);
@@ -472,7 +485,8 @@ std::shared_ptr<DevBatchRes> dev_batch(kv_batch* bt, const PolicySet& ps, int de
                             n_pats ? &qt : nullptr, pdev, (const DevBatch*)d->view_dev.p, (uint2*)erec.p,
                             (uint2*)d->ferec.p, (uint8_t*)d->dnst.p + (size_t)(n_dsets + n_fsets) * v.n_res,
                             (uint32_t*)d->feckey.p, n_anys ? &at : nullptr, (uint32_t*)acode.p, (uint2*)arec.p,
-                            (uint32_t*)d->feacode.p, (uint2*)d->fearec.p);
+                            (uint32_t*)d->feacode.p, (uint2*)d->fearec.p, ps.n_vpats || ps.n_vanys ? &vt : nullptr,
+                            ps.n_vpats, ps.n_vanys);
     });
   HIPCHK(hipStreamSynchronize(us));
   for (const Timed& t : timed) {
@@ -1587,11 +1601,14 @@ int kv_compile(const char* policies_json, size_t len, uint32_t flags, kv_policys
   if ((flags & KV_COMPILE_FOREACH_ANYPATTERN) &&
       (flags & (KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN)) != (KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN))
     return fail(err, KV_E_INVALID, "KV_COMPILE_FOREACH_ANYPATTERN needs KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN");
+  if ((flags & KV_COMPILE_FOREACH_PATVARS) &&
+      (flags & (KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN)) != (KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN))
+    return fail(err, KV_E_INVALID, "KV_COMPILE_FOREACH_PATVARS needs KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN");
   return guarded(KV_E_PARSE, err, [&]() -> int {
     auto s = std::make_unique<kv_policyset>();
     compile_policies(policies_json, len, &s->ps,
                      flags & (KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN | KV_COMPILE_FOREACH_ENTRIES |
-                              KV_COMPILE_FOREACH_ANYPATTERN));
+                              KV_COMPILE_FOREACH_ANYPATTERN | KV_COMPILE_FOREACH_PATVARS));
     if (flags & KV_COMPILE_SPECIALIZE) {
       s->jit = std::make_unique<JitImage>();
       jit_build(s->ps, s->jit.get());  // (kvjitbuild.cpp: generate, plan, compile, variants)

@@ -571,6 +571,21 @@ std::vector<std::string> split(const std::string& s, const std::string& sep) {
 
 }  // namespace
 
+bool leaf_pred_type_agnostic(const PolicySet& ps, uint32_t pi) {
+  const Pred& pr = ps.preds[pi];
+  if (pr.kind != PK_STRING) return true;
+  for (uint32_t a = pr.first; a < pr.first + pr.count; a++)
+    for (uint32_t c = ps.alts[a].first; c < ps.alts[a].first + ps.alts[a].count; c++) {
+      const Conj& cj = ps.conjs[c];
+      for (uint32_t k = 0; k < (cj.kind == CJ_ATOM ? 1u : 2u); k++) {  // (a range has two atoms)
+        const Atom& at = ps.atoms[k ? cj.a1 : cj.a0];
+        const bool glob = at.kind == AT_GLOB_E || at.kind == AT_GLOB_N;
+        if (glob && !(at.gflags & G_ALL)) return false;
+      }
+    }
+  return true;
+}
+
 struct Compiler {
   PolicySet& ps;
   explicit Compiler(PolicySet& p) : ps(p) {}
@@ -890,6 +905,13 @@ struct Compiler {
   // scalar pattern leaf: a compiled predicate, or (a string holding variables) a dynamic
   // leaf whose predicate is the resource's substituted value (kvvars.cpp)
   void leaf(const PV& P, uint32_t d, uint32_t pn, uint32_t cs) {
+    if (P.t == J_STR && P.vstr >= 0 && fe_pattern) {
+      // a foreach entry's pattern (KV_COMPILE_FOREACH_PATVARS): the string is an element string of
+      // the entry's list, and the leaf names its row there (kvwalk.h: the predicate is per element)
+      ps.pnodes[pn].fe_key = P.vstr;
+      emit(OP_VLEAF, d, 0, fe_row((uint32_t)P.vstr), pn, cs);
+      return;
+    }
     if (P.t == J_STR && P.vstr >= 0) {
       const uint32_t dl = (uint32_t)ps.dleaf_vstr.size();
       ps.dleaf_vstr.push_back((uint32_t)P.vstr);
@@ -910,19 +932,14 @@ struct Compiler {
   // forms are compared (validateString on FormatFloat 'E' against decimal, the wildcard branch of
   // validateNumberWithStr on %f against decimal).
   bool fe_pattern = false;
-  bool pred_type_agnostic(uint32_t pi) const {
-    const Pred& pr = ps.preds[pi];
-    if (pr.kind != PK_STRING) return true;
-    for (uint32_t a = pr.first; a < pr.first + pr.count; a++)
-      for (uint32_t c = ps.alts[a].first; c < ps.alts[a].first + ps.alts[a].count; c++) {
-        const Conj& cj = ps.conjs[c];
-        for (uint32_t k = 0; k < (cj.kind == CJ_ATOM ? 1u : 2u); k++) {  // (a range has two atoms)
-          const Atom& at = ps.atoms[k ? cj.a1 : cj.a0];
-          const bool glob = at.kind == AT_GLOB_E || at.kind == AT_GLOB_N;
-          if (glob && !(at.gflags & G_ALL)) return false;
-        }
-      }
-    return true;
+  bool pred_type_agnostic(uint32_t pi) const { return leaf_pred_type_agnostic(ps, pi); }
+  // The row in its list of element string k (PolicySet::elem.keys index) of the entry being
+  // compiled, whose list is fe_list: a string interned before this entry has its column; the ones
+  // this entry adds get theirs, in interning order, once the entry is accepted (kvcond.cpp
+  // compile_foreach_entry), and nothing else is interned in between.
+  uint32_t fe_list = 0;
+  uint32_t fe_row(uint32_t k) const {
+    return k < ps.fkeys.size() ? ps.fkeys[k].col : (uint32_t)(ps.flist_keys[fe_list].size() + (k - ps.fkeys.size()));
   }
 
   void children(const PV& P, uint32_t d, uint32_t pn, uint32_t cs, int meta_idx, int expand_tag, uint32_t t) {
@@ -1451,24 +1468,86 @@ static bool has_metadata_key(const PV& p) {
   return false;
 }
 
+// Pattern variables in an entry's pattern (KV_COMPILE_FOREACH_PATVARS). In scope: string values
+// whose variables are all `element` / `request.object` field, quoted-field and index chains (the
+// element strings' grammar, kvvars.cpp cond_string_in_scope), none in a map key, no `\{{` escape
+// anywhere, no `$(` beside a variable.
+static bool fe_pattern_vars_in_scope(const PV& v) {
+  if (v.t == J_STR) {
+    if (v.s.find("\\{{") != std::string::npos) return false;
+    if (!has_variable(v.s) && !var_string(v.s)) return true;
+    return var_string(v.s) && v.s.find("$(") == std::string::npos && cond_string_in_scope(v.s, true);
+  }
+  for (size_t i = 0; i < v.mk.size(); i++) {
+    const std::string& k = v.mk[i];
+    if (has_variable(k) || var_string(k) || k.find("\\{{") != std::string::npos) return false;
+    if (!fe_pattern_vars_in_scope(v.mv[i])) return false;
+  }
+  for (const PV& x : v.a)
+    if (!fe_pattern_vars_in_scope(x)) return false;
+  return true;
+}
+static size_t count_var_strings(const PV& v) {
+  size_t n = v.t == J_STR && (has_variable(v.s) || var_string(v.s)) ? 1 : 0;
+  for (const PV& x : v.mv) n += count_var_strings(x);
+  for (const PV& x : v.a) n += count_var_strings(x);
+  return n;
+}
+// The variable strings of an entry's pattern in the substitution's traversal order (keys in
+// canonical byte order, arrays in order: collect_var_strings), each interned as a strict element
+// string of the entry's list in its leak context (the key space of the deny strings: an equal text
+// in a deny block of the same list shares the row) and marked with that string (PV::vstr).
+static void collect_elem_strings(PolicySet& ps, PV& v, const std::string& tag, std::vector<uint32_t>* order) {
+  if (v.t == J_STR) {
+    if (!var_string(v.s)) return;
+    const std::string text = tag + v.s;
+    auto it = ps.elem.key_id.find(text);
+    if (it == ps.elem.key_id.end()) {
+      it = ps.elem.key_id.emplace(text, (uint32_t)ps.elem.keys.size()).first;
+      ps.elem.keys.push_back(text);
+    }
+    v.vstr = (int32_t)it->second;
+    order->push_back(it->second);
+    return;
+  }
+  if (v.t == J_MAP) {
+    std::vector<size_t> idx(v.mk.size());
+    for (size_t i = 0; i < idx.size(); i++) idx[i] = i;
+    std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return v.mk[a] < v.mk[b]; });
+    for (size_t i : idx) collect_elem_strings(ps, v.mv[i], tag, order);
+    return;
+  }
+  for (PV& x : v.a) collect_elem_strings(ps, x, tag, order);
+}
+
 // The `pattern` of a validate.foreach entry (kvcond.h FePatternCompiler): the pattern program of
 // MatchPattern(element, pattern), rooted at the projection-trie node of the elements of `list`.
-// Outside the scope (false): {{ }} variables, an anchor-error phrase, a failing $() reference, a
+// Outside the scope (false): {{ }} variables (without `patvars`, or outside its forms:
+// fe_pattern_vars_in_scope), an anchor-error phrase, a failing $() reference, a
 // `metadata` key (MatchPattern runs ExpandInMetadata on the element at the top; below it the
 // pattern compiler's metadata sites read the resource's flags, which say nothing about an element)
 // and whatever the pattern compiler refuses. A refused pattern leaves no instruction, slot fix-up
 // or foreach set behind; the trie nodes of the list path and of the pattern's keys, interned
 // keys, predicates and (where the pattern compiler itself refused) pattern nodes stay, as they do
 // for a refused rule pattern: they only widen the projection.
-static bool compile_foreach_pattern(Compiler& C, const JDoc& d, uint32_t pn, const std::string& list, uint32_t li, FeSet* s) {
+static bool compile_foreach_pattern(Compiler& C, const JDoc& d, uint32_t pn, const std::string& list, uint32_t li, FeSet* s,
+                                    bool patvars) {
   PolicySet& ps = C.ps;
   PV doc = to_pv(d, pn);
-  if (doc.t != J_MAP || doc_has_variable(doc) || doc_has_magic(doc) || has_metadata_key(doc)) return false;
+  if (doc.t != J_MAP || doc_has_magic(doc) || has_metadata_key(doc)) return false;
+  const bool vars = doc_has_variable(doc);
+  if (vars && (!patvars || !fe_pattern_vars_in_scope(doc))) return false;
+  const size_t n_vars = vars ? count_var_strings(doc) : 0;
   PV orig = doc;
   std::string err;
   if (!subst_tree(orig, doc, "", &err)) return false;
-  unescape_vars(doc);
-  if (has_metadata_key(doc) || doc_has_variable(doc)) return false;  // (a $() reference may have brought one in)
+  if (!vars) {
+    unescape_vars(doc);
+    if (doc_has_variable(doc)) return false;  // (a $() reference may have brought one in)
+  } else if (!fe_pattern_vars_in_scope(doc) || count_var_strings(doc) != n_vars) {
+    return false;  // (likewise)
+  }
+  if (has_metadata_key(doc)) return false;
   // the list's path in the projection trie: fields are children, arrays transparent (the element
   // trie). The elements of a list a field step ends in stand at that field's element node; an
   // index step ends in the one element itself.
@@ -1484,7 +1563,13 @@ static bool compile_foreach_pattern(Compiler& C, const JDoc& d, uint32_t pn, con
   RuleRec rr{};
   RuleHost rh;
   const size_t fix0 = ps.slot_fix.size(), pn0 = ps.pnodes.size();
+  // (the strings stay interned where the program is refused below: the caller's rollback takes them)
+  std::vector<uint32_t> vorder;
+  if (vars)
+    collect_elem_strings(ps, doc, "d" + std::to_string(li) + (s->ctx ? "@" + std::to_string(s->ctx) : std::string()) + ":",
+                         &vorder);
   C.fe_pattern = true;
+  C.fe_list = li;
   const bool ok = compile_pattern_program(C, {doc}, false, rr, rh, ch.elem_trie);
   C.fe_pattern = false;
   if (!ok) return false;
@@ -1499,6 +1584,7 @@ static bool compile_foreach_pattern(Compiler& C, const JDoc& d, uint32_t pn, con
   }
   s->prog = rr.prog;
   s->root_pnode = rh.root_pnode;
+  s->vorder = std::move(vorder);
   if (ps.fchains.size() <= li) ps.fchains.resize(li + 1);
   if (ps.fchains[li].steps.empty()) ps.fchains[li] = std::move(ch);
   return true;
@@ -1573,7 +1659,7 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
         // the list's elements. A rule whose name holds an anchor-error phrase stays on the CPU, as
         // for rule patterns: it gets no pattern compiler, whether or not its set is interned already
         const FePatternCompiler fe_pat = [&](uint32_t pnode, const std::string& list, uint32_t li, FeSet* s) {
-          return compile_foreach_pattern(C, d, pnode, list, li, s);
+          return compile_foreach_pattern(C, d, pnode, list, li, s, (flags & 64u /* KV_COMPILE_FOREACH_PATVARS */) != 0);
         };
         const FePatternCompiler* fe_patp =
             (flags & 8u /* KV_COMPILE_FOREACH_PATTERN */) && !has_magic(rh.name) ? &fe_pat : nullptr;
@@ -1583,7 +1669,8 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
         uint32_t* fe_chainp = (flags & 16u /* KV_COMPILE_FOREACH_ENTRIES */) ? &fe_chain : nullptr;
         if (!has_validate) { rr.route = 2; rh.route_reason = "no validate"; }
         else if (feP && (!feD || ((rh.foreach_set = compile_foreach(*ps, d, (uint32_t)fen, fe_patp, fe_chainp,
-                                                                            (flags & 32u /* KV_COMPILE_FOREACH_ANYPATTERN */) != 0)) == 0 &&
+                                                                            (flags & 32u /* KV_COMPILE_FOREACH_ANYPATTERN */) != 0,
+                                                                            (flags & 64u /* KV_COMPILE_FOREACH_PATVARS */) != 0)) == 0 &&
                                   (rh.foreach_chain = fe_chain) == 0))) {
           rr.route = 1;
           rh.route_reason = "foreach";
@@ -1675,6 +1762,19 @@ void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flag
       }
     }
     ps->policy_rule_count.push_back(nrules);
+  }
+  // Pattern variables in entries (KV_COMPILE_FOREACH_PATVARS): the pattern sets and the any sets
+  // with variable strings go behind the others, in order, so the device runs each kind as a range
+  // (the sets without variables in the kernels they ran before). Nothing moves without such a set.
+  for (std::vector<uint32_t>* v : {&ps->fpats, &ps->fanys})
+    std::stable_partition(v->begin(), v->end(), [&](uint32_t fs) { return ps->fsets[fs].vorder.empty(); });
+  for (uint32_t i = 0; i < ps->fpats.size(); i++) {
+    ps->fsets[ps->fpats[i]].pat = i;
+    ps->n_vpats += !ps->fsets[ps->fpats[i]].vorder.empty();
+  }
+  for (uint32_t i = 0; i < ps->fanys.size(); i++) {
+    ps->fsets[ps->fanys[i]].anyi = i;
+    ps->n_vanys += !ps->fsets[ps->fanys[i]].vorder.empty();
   }
   // foreach rules read their status from the rows of the deny plane after the deny sets'
   for (size_t i = 0; i < ps->rules.size(); i++)

@@ -648,7 +648,7 @@ bool has_reference(const JDoc& d, uint32_t node) {
 // the leak context `before` (the lists of the entries in front of it; empty for the first): 1 +
 // its foreach set, 0 outside the scope (nothing is left behind)
 uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const FePatternCompiler* pattern,
-                               const std::vector<uint32_t>& before, bool anypattern = false) {
+                               const std::vector<uint32_t>& before, bool anypattern = false, bool patvars = false) {
   if (d.at(en).t != J_MAP) return 0;
   int64_t ln = -1, pn = -1, dn = -1, tn = -1, an = -1;
   for (uint32_t c = d.at(en).first; c < d.at(en).first + d.at(en).count; c++) {
@@ -713,7 +713,10 @@ uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const 
   FeSet s;
   s.list = li->second;
   // the leak context: that of the first entry unless a string of this one may read `element`
-  if (!before.empty() && ((pn >= 0 && may_read_element(d, (uint32_t)pn)) || (dn >= 0 && may_read_element(d, (uint32_t)dn)))) {
+  // (KV_COMPILE_FOREACH_PATVARS: the strings of its pattern or alternatives are strings of the entry too)
+  const bool pat_reads = patvars && ((tn >= 0 && may_read_element(d, (uint32_t)tn)) || (an >= 0 && may_read_element(d, (uint32_t)an)));
+  if (!before.empty() &&
+      ((pn >= 0 && may_read_element(d, (uint32_t)pn)) || (dn >= 0 && may_read_element(d, (uint32_t)dn)) || pat_reads)) {
     if (ps.fctx.empty()) {
       ps.fctx.emplace_back();
       ps.fctx_id.emplace(std::string(), 0u);
@@ -749,7 +752,7 @@ uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const 
     return rollback();
   }
   // (a set that kept no string of its context reads nothing the entries before it left: the first entry's set)
-  if (s.ctx && !s.has_pre && s.deny.strs.empty()) {
+  if (s.ctx && !s.has_pre && s.deny.strs.empty() && !pat_reads) {
     s.ctx = 0;
     if (ps.elem.keys.size() == k0) drop_contexts();  // (no string names the context either)
   }
@@ -770,9 +773,12 @@ uint32_t compile_foreach_entry(PolicySet& ps, const JDoc& d, uint32_t en, const 
     const JNode& al = d.at((uint32_t)an);
     for (uint32_t c = al.first; c < al.first + al.count; c++) {
       FeSet alt;
+      alt.list = s.list;
+      alt.ctx = s.ctx;
       if (!(*pattern)(c, list, s.list, &alt)) return rollback();
       s.alt_prog.push_back(alt.prog);
       s.alt_root.push_back(alt.root_pnode);
+      s.vorder.insert(s.vorder.end(), alt.vorder.begin(), alt.vorder.end());
     }
     s.any = true;
     s.anyi = (uint32_t)ps.fanys.size();
@@ -849,7 +855,7 @@ struct FeCheckpoint {
 }  // namespace
 
 uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern, uint32_t* chain,
-                         bool anypattern) {
+                         bool anypattern, bool patvars) {
   // validate.foreach: a list of one entry, or (chain: KV_COMPILE_FOREACH_ENTRIES) of 2 to 16, each
   // what a single entry may be. With several, keys of entry k-1's last element leak into entry
   // k's `element` (kvcond.h): entry k's strings are compiled in the context of the lists before it
@@ -857,10 +863,10 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePa
   if (d.at(node).t != J_ARR) return 0;
   const uint32_t count = d.at(node).count, first = d.at(node).first;
   if (count == 1 && !(anypattern && d.at(first).t == J_MAP && d.get(first, "anyPattern") >= 0))
-    return compile_foreach_entry(ps, d, first, pattern, {});
+    return compile_foreach_entry(ps, d, first, pattern, {}, false, patvars);
   if (count == 1) {  // (an anyPattern entry refused at a later alternative: the earlier ones' programs go)
     FeCheckpoint ck(ps);
-    const uint32_t s = compile_foreach_entry(ps, d, first, pattern, {}, true);
+    const uint32_t s = compile_foreach_entry(ps, d, first, pattern, {}, true, patvars);
     if (!s) ck.rollback();
     return s;
   }
@@ -869,7 +875,7 @@ uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePa
   std::vector<uint32_t> sets, before;
   std::string id;
   for (uint32_t en = first; en < first + count; en++) {
-    const uint32_t s = compile_foreach_entry(ps, d, en, pattern, before, anypattern);
+    const uint32_t s = compile_foreach_entry(ps, d, en, pattern, before, anypattern, patvars);
     if (!s) {
       ck.rollback();
       return 0;
@@ -1125,6 +1131,51 @@ void build_foreach(const PolicySet& ps, const Batch& b, FeHost* out) {
     h.any_alts.insert(h.any_alts.end(), s.alt_prog.begin(), s.alt_prog.end());
     h.chain.insert(h.chain.end(), c.words.begin(), c.words.end());
   }
+  // pattern variables in entries (KV_COMPILE_FOREACH_PATVARS): per pattern set, then per any set,
+  // the run of its strings' rows in substitution order, and the plane of the outcomes that are a
+  // map or an array (beside err / oos, which fill_planes gave the strict rows)
+  if (ps.n_vpats || ps.n_vanys) {
+    for (const std::vector<uint32_t>* v : {&ps.fpats, &ps.fanys})
+      for (uint32_t fs : *v) {
+        const FeSet& s = ps.fsets[fs];
+        h.vruns.insert(h.vruns.end(), {(uint32_t)h.vrows.size(), (uint32_t)s.vorder.size()});
+        for (uint32_t k : s.vorder) h.vrows.push_back(ps.fkeys[k].col);
+      }
+    const uint32_t W = h.deny.words;
+    h.mpl.assign(rows.size() * W, 0);
+    for (size_t r = 0; r < rows.size(); r++)
+      for (size_t i = 0; i < rows[r].n && rows[r].strict; i++) {
+        const uint32_t o = h.deny.outc[rows[r].at + i];
+        if (!b.vout_tab[o].empty() && b.vout_tab[o][0] == 'M') h.mpl[r * W + o / 32] |= 1u << (o % 32);
+      }
+  }
+}
+
+FeVarTables FeHost::var_view(const uint32_t* ityp) const {
+  return FeVarTables{vruns.data(), vrows.data(), mpl.data(), ityp};
+}
+
+uint32_t foreach_subst_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_t r, uint32_t elem) {
+  const uint32_t pat = h.sets[4 * set + 2], any = h.sets[4 * set + 3];
+  if (!h.has_vars() || (!pat && !any)) return 0;
+  const size_t run = pat ? pat - 1 : h.pats.size() / 4 + (any - 1);
+  const FeTables t = h.view();
+  const FeVarTables v = h.var_view(nullptr);
+  const uint32_t list = h.sets[4 * set];
+  return kv_fe_subst(t, v, h.lists.data() + 4 * list, h.vruns[2 * run], h.vruns[2 * run + 1],
+                     h.first[(size_t)list * n_res + r] + elem);
+}
+
+uint32_t foreach_elem_outcome(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t key, uint64_t r, uint32_t elem) {
+  const FeKey& k = ps.fkeys[key];
+  const size_t K = ps.flist_keys[k.list].size();
+  const size_t e = (size_t)h.first[(size_t)k.list * b.res.size() + r] + elem;
+  return b.fout[k.list][e * K + k.col];
+}
+
+std::string foreach_subst_error_host(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t set, uint64_t r,
+                                     uint32_t elem) {
+  return first_error(b, ps.fsets[set].vorder, [&](uint32_t k) { return foreach_elem_outcome(ps, b, h, k, r, elem); });
 }
 
 FeTables FeHost::view() const {

@@ -31,6 +31,7 @@ struct CondBlocks;  // kvblocks.h
 struct FeTables;    // kvforeach.h
 struct FePatTables;
 struct FeAnyTables;
+struct FeVarTables;
 }
 
 namespace kvh {
@@ -153,8 +154,15 @@ using FePatternCompiler = std::function<bool(uint32_t pattern_node, const std::s
 // foreach set with one plain pattern program per alternative (each compiled by `pattern`, with a
 // root pattern node of its own), interned by the alternatives' texts. Per element the device
 // tries them in order (kv_foreach_any_kernel): the first that matches is PASS, none is FAIL.
+// `patvars` (KV_COMPILE_FOREACH_PATVARS, with `pattern`): a pattern or an alternative may hold
+// `{{element...}}` / `{{request.object...}}` variables in its string values. Each such string is a
+// strict element string of the entry's list in its leak context (FeSet::vorder: the substitution's
+// traversal order), a leaf on it a dynamic leaf that names the string's row (OP_VLEAF). Per element
+// the device takes the substitution verdict first (kvforeach.h kv_fe_subst: an unresolved variable
+// is ST_ERROR "variable substitution failed", validation.go:549-571), then walks the pattern with
+// the element's substituted values (kvwalk.h). `pattern` reads s->list and s->ctx.
 uint32_t compile_foreach(PolicySet& ps, const JDoc& d, uint32_t node, const FePatternCompiler* pattern = nullptr,
-                         uint32_t* chain = nullptr, bool anypattern = false);
+                         uint32_t* chain = nullptr, bool anypattern = false, bool patvars = false);
 
 struct FeHost {
   // row s of gate / deny: the entry preconditions / the deny block of foreach set s. deny holds the
@@ -166,6 +174,12 @@ struct FeHost {
   std::vector<uint32_t> pats, chain;  // kvforeach.h FePatTables: the pattern sets and their lists' paths
   std::vector<uint32_t> chains, chain_ents;  // kvforeach.h FeTables: the rules of several entries
   std::vector<uint32_t> anys, any_alts;      // kvforeach.h FeAnyTables: the any sets and their alternatives' programs
+  // kvforeach.h FeVarTables (KV_COMPILE_FOREACH_PATVARS; all empty without a set that has variable
+  // strings): a run per pattern set, then per any set; the runs' string rows; the M plane
+  std::vector<uint32_t> vruns, vrows, mpl;
+  bool has_vars() const { return !vrows.empty(); }
+  // (ityp: the int-typing plane of the batch predicate table, DynHost::ityp)
+  kv::FeVarTables var_view(const uint32_t* ityp) const;
   uint32_t max_el = 0;
   kv::FeTables view() const;
   kv::FePatTables pat_view() const;
@@ -189,5 +203,14 @@ uint8_t foreach_chain_fold_host(const FeHost& h, uint32_t chain, uint64_t n_res,
 // order of deny_error_host
 std::string foreach_error_host(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t set, uint64_t r,
                                uint32_t elem);
+// KV_COMPILE_FOREACH_PATVARS: the substitution verdict of element `elem` of store resource r under
+// the pattern strings of `set` (a pattern set or an any set), as the kernels take it
+// (kv_fe_subst): 0, ST_ERROR or ST_CPU ...
+uint32_t foreach_subst_host(const FeHost& h, uint32_t set, uint64_t n_res, uint64_t r, uint32_t elem);
+// ... and the error of the first unresolved pattern string in traversal order ("" without one)
+std::string foreach_subst_error_host(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t set, uint64_t r,
+                                     uint32_t elem);
+// the outcome (Batch::vout_tab index) of element string `key` (PolicySet::fkeys) on that element
+uint32_t foreach_elem_outcome(const PolicySet& ps, const Batch& b, const FeHost& h, uint32_t key, uint64_t r, uint32_t elem);
 
 }  // namespace kvh

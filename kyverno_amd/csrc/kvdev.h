@@ -35,14 +35,19 @@ hipError_t launch_cond(bool strict, const CondBlocks& T, uint32_t n_res, uint32_
 // through kv_foreach_any_kernel, the per-element code words into the transient acode[any set]
 // [T.max_el] and the alternatives' records into arec[alternative][T.max_el]; the deciding
 // element's into fe_acode[any set][res] and fe_arec[alternative][res].
+// With variable strings in entries' patterns (V, kvforeach.h FeVarTables; KV_COMPILE_FOREACH_PATVARS):
+// the last n_vpats pattern sets and the last n_vanys any sets go through kv_foreach_patv_kernel /
+// kv_foreach_anyv_kernel instead; V.runs holds a run per pattern set, then per any set.
 struct FeTables;
 struct FePatTables;
 struct FeAnyTables;
+struct FeVarTables;
 hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream,
                           const FePatTables* Q = nullptr, const DevPS* P = nullptr, const DevBatch* B = nullptr,
                           uint2* erec = nullptr, uint2* fe_rec = nullptr, uint8_t* chain_st = nullptr,
                           uint32_t* fe_ckey = nullptr, const FeAnyTables* A = nullptr, uint32_t* acode = nullptr,
-                          uint2* arec = nullptr, uint32_t* fe_acode = nullptr, uint2* fe_arec = nullptr);
+                          uint2* arec = nullptr, uint32_t* fe_acode = nullptr, uint2* fe_arec = nullptr,
+                          const FeVarTables* V = nullptr, uint32_t n_vpats = 0, uint32_t n_vanys = 0);
 
 // Match tables of a pass (DevPS::mt_*): `words` = mt_ns_words + mt_ann_words +
 // mt_sel_words rows, max_entities = max(n_nsm, n_asets, n_lsets).

@@ -64,6 +64,43 @@ struct FeAnyTables {
   uint32_t n_anys, n_alts;
 };
 
+// Pattern variables in entries (KV_COMPILE_FOREACH_PATVARS): the pattern sets and any sets whose
+// patterns hold `{{element...}}` / `{{request.object...}}` strings. The strings are strict string
+// rows of the set's list (FeTables::deny: outc, err, oos), resolved per element at ingest like the
+// deny strings; a dynamic leaf of the pattern program (OP_VLEAF) names its string's row in the
+// list, and the predicate it evaluates is the element's outcome id in the batch predicate table
+// (DevBatch::dps). Such sets stand behind the others in FePatTables::pats / FeAnyTables::anys and
+// run in kernels of their own (kv_foreach_patv_kernel, kv_foreach_anyv_kernel).
+struct FeVarTables {
+  const uint32_t* runs;  // 2 words per set (this launch's first set at 0): first row in `rows`, rows
+  const uint32_t* rows;  // the strings of a set in the substitution's traversal order (for an any set:
+                         // alternative 0's, then alternative 1's, ...): the string's row in its list
+  const uint32_t* mpl;   // [plane row of the list + string][words], beside err / oos: the outcome is a map or an array
+  const uint32_t* ityp;  // [words], by outcome id: the outcome's predicate compares a number's text form
+};
+
+// substitutePatterns() of one element (validation.go:549-571): element e of the list L (its 4
+// words of FeTables::lists) under the strings rows[r0, r0 + rn) of a set. 0: every string resolved
+// to a leaf value; ST_ERROR / ST_CPU: the first string in traversal order whose outcome is an
+// error / outside the resolver's scope decides; otherwise ST_CPU where a map or an array replaces
+// a leaf. The run is the same for every lane of a launch row; a lane loads outc[row][e], coalesced.
+KV_HD inline uint32_t kv_fe_subst(const FeTables& T, const FeVarTables& V, const uint32_t* L, uint32_t r0, uint32_t rn,
+                                  uint32_t e) {
+  const uint32_t* outc = T.deny.outc + L[0];
+  const uint32_t n_el = L[1], W = T.deny.words;
+  uint32_t structural = 0;
+  for (uint32_t k = 0; k < rn; k++) {
+    const uint32_t row = V.rows[r0 + k];
+    const uint32_t o = outc[(uint64_t)row * n_el + e];
+    const uint64_t w = (uint64_t)(L[2] + row) * W + (o >> 5);
+    const uint32_t bit = 1u << (o & 31u);
+    if (T.deny.err[w] & bit) return ST_ERROR;
+    if (T.deny.oos[w] & bit) return ST_CPU;
+    structural |= V.mpl[w] & bit;
+  }
+  return structural ? (uint32_t)ST_CPU : 0u;
+}
+
 // One element of foreach set `set`: element e of the set's list (e < its element count).
 // validate() on the element's context (validation.go:156-202): the entry's preconditions under
 // the preconditions resolver (not met: ST_SKIP, undecided: ST_CPU), then the deny block under the

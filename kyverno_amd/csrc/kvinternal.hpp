@@ -49,6 +49,8 @@ struct PNodeInfo {
   std::string pat_v;     // Go %v of the compared scalar (the value, or element 0 of a scalar list)
   uint32_t pat_len = 0;  // pattern array length (validate.go:172)
   int32_t dleaf = -1;    // a dynamic leaf (pattern variables) compares here: pat_v is per resource
+  int32_t fe_key = -1;   // ... of a foreach entry's pattern (KV_COMPILE_FOREACH_PATVARS): its element string
+                         // (PolicySet::fkeys), pat_v is per element
 };
 
 // A pattern string holding {{ }} variables (kvvars.cpp): `text` after $() references, `path`
@@ -125,6 +127,10 @@ struct FeSet {
   bool any = false;
   uint32_t anyi = 0;
   std::vector<uint32_t> alt_prog, alt_root;
+  // Pattern variables in entries (KV_COMPILE_FOREACH_PATVARS): the variable strings of the pattern
+  // (of every alternative, alternative 0's first) in the substitution's traversal order, repeats
+  // kept: PolicySet::fkeys indices, strict strings of the set's list in its leak context
+  std::vector<uint32_t> vorder;
 };
 // One step of a foreach list path (kvvars.cpp list_query_steps): a field or an index
 struct ListStep {
@@ -296,6 +302,10 @@ struct PolicySet {
   // anyPattern entries (KV_COMPILE_FOREACH_ANYPATTERN): the foreach sets that carry an anyPattern,
   // in order (FeSet::anyi indexes it); their lists' paths are in fchains too
   std::vector<uint32_t> fanys;
+  // pattern variables in entries (KV_COMPILE_FOREACH_PATVARS): the pattern sets / any sets with
+  // variable strings stand behind the others in fpats / fanys (compile_policies orders them), so
+  // the device runs them as ranges: how many of each there are
+  uint32_t n_vpats = 0, n_vanys = 0;
   // rules of several entries (KV_COMPILE_FOREACH_ENTRIES): a *chain* is the ordered list of the
   // entries' foreach sets, interned by that list (fe_chains). The reference's JSON context keeps
   // the last element of entry k merged in when entry k + 1 starts, so an entry's `element` strings
@@ -310,7 +320,7 @@ struct PolicySet {
 
 // Compiles a JSON list of (already autogen-expanded) ClusterPolicy/Policy
 // objects (flags: kv_compile's KV_COMPILE_DENY | KV_COMPILE_FOREACH | KV_COMPILE_FOREACH_PATTERN |
-// KV_COMPILE_FOREACH_ENTRIES | KV_COMPILE_FOREACH_ANYPATTERN). Throws
+// KV_COMPILE_FOREACH_ENTRIES | KV_COMPILE_FOREACH_ANYPATTERN | KV_COMPILE_FOREACH_PATVARS). Throws
 // std::runtime_error on malformed input.
 void compile_policies(const char* json, size_t len, PolicySet* ps, uint32_t flags = 0);
 
@@ -487,8 +497,13 @@ struct Batch {
 // distinct outcome (pred id == outcome id), the outcome of each dynamic leaf
 // [dleaf][res], and the status substitution decides per [dyn rule][res] (0 / ST_ERROR /
 // ST_CPU) with the ERROR's outcome id (its message) in dyn_msg.
+// With variable strings in foreach entries' patterns (PolicySet::n_vpats / n_vanys) the predicate
+// table is built whether or not the policy set has resource-level keys, and `ityp` holds a bit
+// per outcome id: set where the outcome's predicate is not type-agnostic (it compares a number's
+// text form: the int-typing guard of kvwalk.h, decided per substituted value).
 struct DynHost {
   PolicySet tbl;
+  std::vector<uint32_t> ityp;
   std::vector<uint32_t> dleaf;
   std::vector<uint8_t> dyn_st;
   std::vector<uint32_t> dyn_msg;
@@ -519,6 +534,8 @@ std::string resolve_elem_overlay(const std::string& tmpl, const JDoc& d, uint32_
                                  bool precond);
 PV outcome_value(const std::string& o);
 uint32_t compile_leaf_pred(PolicySet& tbl, const PV& value);  // kvcompile.cpp
+// the verdict of predicate `pred` of tbl on a number does not depend on its int64 / float64 typing
+bool leaf_pred_type_agnostic(const PolicySet& tbl, uint32_t pred);
 std::string pattern_go_v(const PV& p);                         // Go %v of a scalar pattern value
 
 void ingest_resources(const PolicySet& ps, const char* json, size_t len, const char* ns_labels_json, Batch* b);

@@ -252,11 +252,11 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_elem_kernel(FeTab
 // 8 bytes. The 8-byte record of a FAIL / ERROR element goes to erec[pattern set][element];
 // kv_foreach_rec_kernel picks the deciding element's. No lane leaves before the wave operations: lanes past the list's end and
 // lanes without an element node go through the walk parked.
-extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_pat_kernel(FeTables T, FePatTables Q,
-                                                                           const DevPS* __restrict__ Pp,
-                                                                           const DevBatch* __restrict__ Bp,
-                                                                           uint32_t n_res, uint32_t* __restrict__ fe_acc,
-                                                                           uint2* __restrict__ erec) {
+template <bool VARS>
+__device__ __forceinline__ void kv_foreach_pat_body(const FeTables& T, const FePatTables& Q, const DevPS* __restrict__ Pp,
+                                                    const DevBatch* __restrict__ Bp, uint32_t n_res,
+                                                    uint32_t* __restrict__ fe_acc, uint2* __restrict__ erec,
+                                                    const FeVarTables* V) {
   __shared__ uint32_t s_cur[KV_MAXD][KV_WG];
   __shared__ uint32_t s_lfirst[KV_MAXL][KV_WG];
   __shared__ uint32_t s_llen[KV_MAXL][KV_WG];
@@ -275,10 +275,31 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_pat_kernel(FeTabl
     const bool valid = e < n_el;
     uint32_t res, ord;
     uint2 w;
-    const uint32_t code = kv_fe_pat_lane(T, Q, P, B, N, p, e, valid, n_res, s_cur, s_lfirst, s_llen, s_li, &res, &ord, &w);
+    const uint32_t code =
+        kv_fe_pat_lane<VARS>(T, Q, P, B, N, p, e, valid, n_res, s_cur, s_lfirst, s_llen, s_li, &res, &ord, &w, V);
     if (valid && (code == ST_FAIL || code == ST_ERROR)) erec[(size_t)p * T.max_el + e] = w;
     kv_fe_reduce(lane, valid, res, ord, code, n_res, fe_acc + (size_t)s * n_res);
   }
+}
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_pat_kernel(FeTables T, FePatTables Q,
+                                                                           const DevPS* __restrict__ Pp,
+                                                                           const DevBatch* __restrict__ Bp,
+                                                                           uint32_t n_res, uint32_t* __restrict__ fe_acc,
+                                                                           uint2* __restrict__ erec) {
+  kv_foreach_pat_body<false>(T, Q, Pp, Bp, n_res, fe_acc, erec, nullptr);
+}
+// kv_foreach_patv_kernel (KV_COMPILE_FOREACH_PATVARS): the pattern sets whose patterns hold variable
+// strings, which stand behind the others: Q.pats, erec and V.runs start at the first of them. Between
+// the gate and the walk a lane takes the substitution verdict of its element (kv_fe_subst: one
+// coalesced outcome word and three plane words per string of the set; the run is wave-uniform); a
+// lane it decides goes through the walk parked and writes a zero record for ST_ERROR. A dynamic
+// leaf evaluates the element's outcome on the batch predicate table (kvwalk.h).
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_patv_kernel(FeTables T, FePatTables Q, FeVarTables V,
+                                                                            const DevPS* __restrict__ Pp,
+                                                                            const DevBatch* __restrict__ Bp,
+                                                                            uint32_t n_res, uint32_t* __restrict__ fe_acc,
+                                                                            uint2* __restrict__ erec) {
+  kv_foreach_pat_body<true>(T, Q, Pp, Bp, n_res, fe_acc, erec, &V);
 }
 
 // kv_foreach_any_kernel (KV_COMPILE_FOREACH_ANYPATTERN, kvwalk.h kv_fe_any_lane): the elements of
@@ -289,12 +310,11 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_pat_kernel(FeTabl
 // 8-byte record goes to the transient arec[alternative][element] (alternatives numbered through
 // all any sets) and the status into the element's code word, acode[any set][element] (written for
 // every element of the list: 0 unless the element is ST_FAIL). The code feeds kv_fe_reduce.
-extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_any_kernel(FeTables T, FeAnyTables A,
-                                                                           const DevPS* __restrict__ Pp,
-                                                                           const DevBatch* __restrict__ Bp,
-                                                                           uint32_t n_res, uint32_t* __restrict__ fe_acc,
-                                                                           uint32_t* __restrict__ acode,
-                                                                           uint2* __restrict__ arec) {
+template <bool VARS>
+__device__ __forceinline__ void kv_foreach_any_body(const FeTables& T, const FeAnyTables& A, const DevPS* __restrict__ Pp,
+                                                    const DevBatch* __restrict__ Bp, uint32_t n_res,
+                                                    uint32_t* __restrict__ fe_acc, uint32_t* __restrict__ acode,
+                                                    uint2* __restrict__ arec, const FeVarTables* V) {
   __shared__ uint32_t s_cur[KV_MAXD][KV_WG];
   __shared__ uint32_t s_lfirst[KV_MAXL][KV_WG];
   __shared__ uint32_t s_llen[KV_MAXL][KV_WG];
@@ -311,11 +331,32 @@ extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_any_kernel(FeTabl
     if (blockIdx.x * KV_WG >= n_el) continue;  // (workgroup-uniform)
     const bool valid = e < n_el;  // (n_el <= T.max_el: a valid lane's slots are inside acode and arec)
     uint32_t res, ord, cw;
-    const uint32_t code = kv_fe_any_lane(T, A, P, B, N, a, e, valid, n_res, s_cur, s_lfirst, s_llen, s_li, &res, &ord, &cw,
-                                         arec + ((size_t)a0 * T.max_el + e), T.max_el);
+    const uint32_t code = kv_fe_any_lane<VARS>(T, A, P, B, N, a, e, valid, n_res, s_cur, s_lfirst, s_llen, s_li, &res, &ord,
+                                               &cw, arec + ((size_t)a0 * T.max_el + e), T.max_el, V);
     if (valid) acode[(size_t)a * T.max_el + e] = cw;
     kv_fe_reduce(lane, valid, res, ord, code, n_res, fe_acc + (size_t)s * n_res);
   }
+}
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_any_kernel(FeTables T, FeAnyTables A,
+                                                                           const DevPS* __restrict__ Pp,
+                                                                           const DevBatch* __restrict__ Bp,
+                                                                           uint32_t n_res, uint32_t* __restrict__ fe_acc,
+                                                                           uint32_t* __restrict__ acode,
+                                                                           uint2* __restrict__ arec) {
+  kv_foreach_any_body<false>(T, A, Pp, Bp, n_res, fe_acc, acode, arec, nullptr);
+}
+// kv_foreach_anyv_kernel (KV_COMPILE_FOREACH_PATVARS): the any sets with variable strings in an
+// alternative, which stand behind the others: A.anys, acode and V.runs start at the first of them
+// (A.alts and arec do not: an any set names its alternatives by their number through all any sets).
+// The substitution verdict covers the strings of every alternative and comes before the first one
+// is tried (kvwalk.h kv_fe_any_lane).
+extern "C" __global__ __launch_bounds__(KV_WG) void kv_foreach_anyv_kernel(FeTables T, FeAnyTables A, FeVarTables V,
+                                                                            const DevPS* __restrict__ Pp,
+                                                                            const DevBatch* __restrict__ Bp,
+                                                                            uint32_t n_res, uint32_t* __restrict__ fe_acc,
+                                                                            uint32_t* __restrict__ acode,
+                                                                            uint2* __restrict__ arec) {
+  kv_foreach_any_body<true>(T, A, Pp, Bp, n_res, fe_acc, acode, arec, &V);
 }
 
 // kv_foreach_fin_kernel: one lane per resource, grid.y = foreach sets; the list state and the
@@ -402,7 +443,7 @@ namespace kv {
 hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, uint8_t* fe_st, hipStream_t stream,
                           const FePatTables* Q, const DevPS* P, const DevBatch* B, uint2* erec, uint2* fe_rec,
                           uint8_t* chain_st, uint32_t* fe_ckey, const FeAnyTables* A, uint32_t* acode, uint2* arec,
-                          uint32_t* fe_acode, uint2* fe_arec) {
+                          uint32_t* fe_acode, uint2* fe_arec, const FeVarTables* V, uint32_t n_vpats, uint32_t n_vanys) {
   if (n_res == 0 || T.n_sets == 0) return hipSuccess;
   const hipError_t e = hipMemsetAsync(fe_acc, 0xFF, (size_t)T.n_sets * n_res * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
@@ -412,12 +453,39 @@ hipError_t launch_foreach(const FeTables& T, uint32_t n_res, uint32_t* fe_acc, u
   if (T.max_el && T.n_sets > n_pats + n_anys)
     hipLaunchKernelGGL(kv_foreach_elem_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, gy), dim3(KV_WG), 0, stream, T, n_res,
                        fe_acc);
-  if (T.max_el && n_pats)
-    hipLaunchKernelGGL(kv_foreach_pat_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, py), dim3(KV_WG), 0, stream, T, *Q, P, B,
-                       n_res, fe_acc, erec);
-  if (T.max_el && n_anys)
-    hipLaunchKernelGGL(kv_foreach_any_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, ay), dim3(KV_WG), 0, stream, T, *A, P, B,
-                       n_res, fe_acc, acode, arec);
+  // (KV_COMPILE_FOREACH_PATVARS: the last n_vpats pattern sets and n_vanys any sets hold variable
+  // strings and run in the kernels that read them; the others run what they ran before)
+  const uint32_t n_ppats = n_pats - n_vpats, n_panys = n_anys - n_vanys;
+  if (T.max_el && n_ppats) {
+    FePatTables Q0 = *Q;
+    Q0.n_pats = n_ppats;
+    hipLaunchKernelGGL(kv_foreach_pat_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, n_ppats < KV_PRE_YMAX ? n_ppats : KV_PRE_YMAX),
+                       dim3(KV_WG), 0, stream, T, Q0, P, B, n_res, fe_acc, erec);
+  }
+  if (T.max_el && n_vpats) {
+    FePatTables Q1 = *Q;
+    Q1.pats += 4u * n_ppats;
+    Q1.n_pats = n_vpats;
+    FeVarTables V1 = *V;
+    V1.runs += 2u * n_ppats;
+    hipLaunchKernelGGL(kv_foreach_patv_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, n_vpats < KV_PRE_YMAX ? n_vpats : KV_PRE_YMAX),
+                       dim3(KV_WG), 0, stream, T, Q1, V1, P, B, n_res, fe_acc, erec + (size_t)n_ppats * T.max_el);
+  }
+  if (T.max_el && n_panys) {
+    FeAnyTables A0 = *A;
+    A0.n_anys = n_panys;
+    hipLaunchKernelGGL(kv_foreach_any_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, n_panys < KV_PRE_YMAX ? n_panys : KV_PRE_YMAX),
+                       dim3(KV_WG), 0, stream, T, A0, P, B, n_res, fe_acc, acode, arec);
+  }
+  if (T.max_el && n_vanys) {
+    FeAnyTables A1 = *A;
+    A1.anys += 8u * n_panys;
+    A1.n_anys = n_vanys;
+    FeVarTables V1 = *V;
+    V1.runs += 2u * (n_pats + n_panys);
+    hipLaunchKernelGGL(kv_foreach_anyv_kernel, dim3((T.max_el + KV_WG - 1) / KV_WG, n_vanys < KV_PRE_YMAX ? n_vanys : KV_PRE_YMAX),
+                       dim3(KV_WG), 0, stream, T, A1, V1, P, B, n_res, fe_acc, acode + (size_t)n_panys * T.max_el, arec);
+  }
   hipLaunchKernelGGL(kv_foreach_fin_kernel, dim3((n_res + KV_WG - 1) / KV_WG, gy), dim3(KV_WG), 0, stream, T, n_res,
                      (const uint32_t*)fe_acc, fe_st);
   if (n_pats)

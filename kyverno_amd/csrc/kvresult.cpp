@@ -262,7 +262,8 @@ std::string error_message(const PolicySet& ps, const Batch& b, const ErrRec& e, 
   const uint32_t kind = err_kind(e);
   if (e.pnode >= ps.pnodes.size()) return "";
   PNodeInfo P = ps.pnodes[e.pnode];
-  if (P.dleaf >= 0 && dyn_pat_v) P.pat_v = *dyn_pat_v;  // the resource's substituted pattern value
+  // the resource's (a foreach entry's pattern: the element's) substituted pattern value
+  if ((P.dleaf >= 0 || P.fe_key >= 0) && dyn_pat_v) P.pat_v = *dyn_pat_v;
   const std::vector<PathSeg> segs = path_segs(ps, b, e, e.pnode);
   const std::string path = join_path(segs);
   std::string m;
@@ -436,6 +437,37 @@ bool any_pair(const Pair& q, uint32_t* key, uint32_t* cw, uint32_t* set_o, size_
   *set_o = set;
   *alt0 = 0;
   for (uint32_t i = 0; i < q.ps().fsets[set].anyi; i++) *alt0 += q.ps().fsets[q.ps().fanys[i]].alt_prog.size();
+  return true;
+}
+
+// A FAIL / ERROR pair (status st) of a device foreach rule that a pattern entry or an anyPattern
+// entry decided: the deciding set and element, from the fetched reduction keys. Unlike any_pair it
+// knows the ERROR of an any set, which only the substitution gives (KV_COMPILE_FOREACH_PATVARS).
+bool walked_pair(const Pair& q, uint8_t st, uint32_t* set_o, uint32_t* elem_o) {
+  if (!q.part) return false;
+  const RuleHost& rh = q.ps().rhost[q.rule];
+  if (!rh.foreach_set && !rh.foreach_chain) return false;
+  uint32_t set, entry, elem;
+  if (!deciding_entry(q, st, &set, &entry, &elem)) return false;
+  const FeSet& s = q.ps().fsets[set];
+  uint32_t k;
+  if (s.pattern && !q.part->fe_key.empty()) k = q.part->fe_key[(size_t)s.pat * q.part->n + q.local];
+  else if (s.any && !q.part->fe_akey.empty()) k = q.part->fe_akey[(size_t)s.anyi * q.part->n + q.local];
+  else return false;
+  if (k >= FE_KEY_PASS || (k & 7u) != st) return false;
+  if (rh.foreach_chain && (k >> 3) != elem) return false;
+  *set_o = set;
+  *elem_o = k >> 3;
+  return true;
+}
+
+// Go %v of the substituted pattern value at the dynamic leaf of record e of a foreach entry's
+// pattern (KV_COMPILE_FOREACH_PATVARS), on element `elem` of the pair's resource; false: not such a leaf
+bool elem_pattern_value(const Pair& q, const ErrRec& e, uint32_t elem, std::string* pv) {
+  const PolicySet& ps = q.ps();
+  if (e.pnode >= ps.pnodes.size() || ps.pnodes[e.pnode].fe_key < 0) return false;
+  const uint32_t o = foreach_elem_outcome(ps, q.kb->b, q.kb->fe_host(ps), (uint32_t)ps.pnodes[e.pnode].fe_key, q.local, elem);
+  *pv = pattern_go_v(outcome_value(q.kb->b.vout_tab[o]));
   return true;
 }
 
@@ -615,6 +647,7 @@ int kv_result_foreach_element(const kv_result* r, uint32_t rule, uint64_t res, u
       uint32_t key, cw, s;
       size_t a0;
       if (any_pair(q, &key, &cw, &s, &a0)) *index = key >> 3;
+      else if (st == ST_ERROR && walked_pair(q, st, &s, &key)) *index = key;  // (a substitution error)
       return 0;
     }
     uint32_t e = 0xFFFFFFFFu;
@@ -731,9 +764,59 @@ int kv_result_foreach_error_message(const kv_result* r, uint32_t rule, uint64_t 
     // %T float64)
     JDoc doc;
     parse_json(element_json, len, NUM_FLOAT, &doc);
-    const std::string m = error_message(q.ps(), q.r->batch_of(*q.part), kv_result::decode(rec), doc);
+    const ErrRec e = kv_result::decode(rec);
+    std::string pv;  // (a dynamic leaf: the deciding element's substituted pattern value)
+    const bool dyn = elem_pattern_value(q, e, key >> 3, &pv);
+    const std::string m = error_message(q.ps(), q.r->batch_of(*q.part), e, doc, dyn ? &pv : nullptr);
     if (m.empty()) return KV_E_INVALID;
     return put_message(m, buf, cap);
+  });
+}
+
+int kv_result_foreach_subst_error(const kv_result* r, uint32_t rule, uint64_t res, char* buf, size_t cap) {
+  return guarded(KV_E_INVALID, nullptr, [&]() -> int {
+    const Pair q = pair_of(r, rule, res, false);
+    if (q.code) return q.code;
+    const PolicySet& ps = q.ps();
+    const RuleHost& rh = ps.rhost[rule];
+    if ((!rh.foreach_set && !rh.foreach_chain) || !(ps.n_vpats || ps.n_vanys) || !q.part) return 0;
+    if (q.status() != ST_ERROR) return 0;
+    uint32_t set, elem;
+    if (!walked_pair(q, ST_ERROR, &set, &elem) || ps.fsets[set].vorder.empty()) return 0;
+    // recomputed from the deciding element's outcome row, as kv_result_deny_message does
+    const FeHost& h = q.kb->fe_host(ps);
+    if (foreach_subst_host(h, set, q.n_local(), q.local, elem) != ST_ERROR) return 0;
+    const std::string err = foreach_subst_error_host(ps, q.kb->b, h, set, q.local, elem);
+    if (err.empty()) return 0;
+    // ruleError(rule, Validation, "variable substitution failed", err) of the element's validate()
+    // (validation.go:186-188), wrapped by the foreach loop (validation.go:248-252)
+    return put_message("validation failed in foreach rule for variable substitution failed: " + err, buf, cap);
+  });
+}
+
+int kv_rule_foreach_patvars(const kv_policyset* ps, uint32_t rule, uint32_t* on) {
+  if (!ps || !on) return KV_E_INVALID;
+  if (rule >= ps->ps.rules.size()) return KV_E_RANGE;
+  const RuleHost& rh = ps->ps.rhost[rule];
+  *on = 0;
+  if (rh.foreach_set) *on = ps->ps.fsets[rh.foreach_set - 1].vorder.empty() ? 0u : 1u;
+  if (rh.foreach_chain)
+    for (uint32_t s : ps->ps.fe_chains[rh.foreach_chain - 1]) *on |= ps->ps.fsets[s].vorder.empty() ? 0u : 1u;
+  return 0;
+}
+
+int kv_batch_foreach_subst(const kv_policyset* ps, const kv_batch* b, uint32_t set, uint64_t res, uint32_t elem,
+                           uint32_t* code, char* buf, size_t cap) {
+  if (!ps || !b || !code) return KV_E_INVALID;
+  if (set >= ps->ps.fsets.size() || res >= b->b.res.size()) return KV_E_RANGE;
+  if (ps->ps.fsets[set].vorder.empty()) return KV_E_INVALID;
+  return guarded(KV_E_INVALID, nullptr, [&]() -> int {
+    const FeHost& h = const_cast<kv_batch*>(b)->fe_host(ps->ps);
+    const uint32_t* inv = const_cast<kv_batch*>(b)->inverse();
+    const uint64_t s = inv ? inv[res] : res, n = b->b.res.size();
+    if (elem >= b->b.fcount[s * ps->ps.flists.size() + ps->ps.fsets[set].list]) return KV_E_RANGE;
+    *code = foreach_subst_host(h, set, n, s, elem);
+    return put_message(*code == ST_ERROR ? foreach_subst_error_host(ps->ps, b->b, h, set, s, elem) : std::string(), buf, cap);
   });
 }
 
@@ -764,7 +847,12 @@ int kv_result_foreach_alt_error_message(const kv_result* r, uint32_t rule, uint6
     if (rc) return rc;
     JDoc doc;  // (every number of the element float64, as kv_result_foreach_error_message)
     parse_json(element_json, len, NUM_FLOAT, &doc);
-    const std::string m = error_message(q.ps(), q.r->batch_of(*q.part), kv_result::decode(rec), doc);
+    const ErrRec e = kv_result::decode(rec);
+    std::string pv;  // (a dynamic leaf: the deciding element's substituted pattern value)
+    uint32_t key = 0, cw, set;
+    size_t alt0;
+    const bool dyn = any_pair(q, &key, &cw, &set, &alt0) && elem_pattern_value(q, e, key >> 3, &pv);
+    const std::string m = error_message(q.ps(), q.r->batch_of(*q.part), e, doc, dyn ? &pv : nullptr);
     if (m.empty()) return KV_E_INVALID;
     return put_message(m, buf, cap);
   });
@@ -926,6 +1014,8 @@ int kv_batch_foreach_tables(const kv_policyset* ps, const kv_batch* b, char** ou
           &h.deny.oos})
       put(*v);
     put({h.deny.words, h.max_el});
+    if (h.has_vars())  // (KV_COMPILE_FOREACH_PATVARS: nothing is added without a set with variable strings)
+      for (const std::vector<uint32_t>* v : {&h.vruns, &h.vrows, &h.mpl}) put(*v);
     char* p = (char*)malloc(std::max<size_t>(o.size(), 1));
     if (!p) return KV_E_NOMEM;
     memcpy(p, o.data(), o.size());

@@ -573,7 +573,10 @@ void build_dyn(const PolicySet& ps, const Batch& b, DynHost* out) {
   h = DynHost();
   const uint64_t n = b.res.size();
   const size_t K = ps.vout_width();
-  if (ps.vkeys.empty()) return;
+  // (pattern variables in foreach entries, KV_COMPILE_FOREACH_PATVARS: the element strings' outcomes
+  // are predicates of the same table, whether or not a rule pattern has variables)
+  const bool fe_vars = ps.n_vpats || ps.n_vanys;
+  if (ps.vkeys.empty() && !fe_vars) return;
   const std::vector<std::string>& tab = b.vout_tab;
   // batch predicate table: one predicate per distinct outcome (pred id == outcome id)
   for (size_t o = 0; o < tab.size(); o++) {
@@ -587,6 +590,11 @@ void build_dyn(const PolicySet& ps, const Batch& b, DynHost* out) {
   }
   if (h.tbl.preds.size() != tab.size()) throw std::runtime_error("build_dyn: predicate table misaligned");
   h.tbl.strs.append(16, '\0');
+  if (fe_vars) {
+    h.ityp.assign(std::max<size_t>((tab.size() + 31) / 32, 1), 0);
+    for (size_t o = 0; o < tab.size(); o++)
+      if (!leaf_pred_type_agnostic(h.tbl, (uint32_t)o)) h.ityp[o / 32] |= 1u << (o % 32);
+  }
   const size_t L = ps.dleaf_vstr.size(), R = ps.dyn_rules.size();
   h.dleaf.assign(L * n, 0);
   h.dyn_st.assign(R * n, 0);

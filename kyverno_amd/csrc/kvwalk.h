@@ -4,7 +4,10 @@
 //   kv_foreach_pat_kernel (ELEM = true, KV_COMPILE_FOREACH_PATTERN): a lane is an element of a
 //   foreach list, the root that element's node (MatchPattern(element, pattern): the element map
 //   as the whole resource), kv_foreach_any_kernel (KV_COMPILE_FOREACH_ANYPATTERN: the same, once per
-//   alternative of an anyPattern entry), and the host harness tools/kvemu (a one-lane wave).
+//   alternative of an anyPattern entry), kv_foreach_patv_kernel / kv_foreach_anyv_kernel (ELEM and
+//   VARS, KV_COMPILE_FOREACH_PATVARS: the two with `{{element...}}` strings in the patterns: a
+//   dynamic leaf reads the element's substituted value), and the host harness tools/kvemu (a
+//   one-lane wave).
 // Lanes that skip a subtree (absent anchored key) or raise an error park on a wake-up pc (the scope
 // end / catch point) instead of branching, so the wave never diverges in program position; loops
 // over resource arrays run max(len) uniform iterations with the counter in LDS per wave.
@@ -59,12 +62,18 @@ __device__ __forceinline__ bool kv_int_unsafe(const DevBatch& B, const Node& n, 
 // r: the lane's resource (the dynamic leaves' row); rl: see above (ELEM only). st and e: the
 // lane's status and error fields, written by the lanes that ran (MatchPattern's epilogue,
 // validate.go:29-50). cpu (ELEM only): see above.
-template <bool ELEM>
+// VARS (ELEM only; KV_COMPILE_FOREACH_PATVARS, kvforeach.h FeVarTables): a dynamic leaf's row is the
+// lane's *element*: the predicate id is vrow[a * vstride + ve], the outcome of string row a of the
+// element's list on element ve, evaluated on the batch predicate table as the resource arm does;
+// the int-typing guard is decided per substituted value, by the outcome's bit in `ityp`.
+template <bool ELEM, bool VARS = false>
 __device__ __forceinline__ void kv_walk(const DevPS& P, const DevBatch& B, const Node* __restrict__ N,
                                         const uint32_t* __restrict__ prog, uint32_t root, bool run, uint32_t r,
                                         uint32_t n_res, uint32_t rl, uint32_t (*s_cur)[KV_WG],
                                         uint32_t (*s_lfirst)[KV_WG], uint32_t (*s_llen)[KV_WG],
-                                        uint32_t (*s_li)[KV_MAXL], uint32_t& st, EState& e, bool& cpu) {
+                                        uint32_t (*s_li)[KV_MAXL], uint32_t& st, EState& e, bool& cpu,
+                                        const uint32_t* __restrict__ vrow = nullptr, uint32_t vstride = 0u,
+                                        uint32_t ve = 0u, const uint32_t* __restrict__ ityp = nullptr) {
   const uint32_t lane = threadIdx.x;
   const uint32_t wv = lane >> 6;
   if (__ballot(run)) {
@@ -186,7 +195,26 @@ __device__ __forceinline__ void kv_walk(const DevPS& P, const DevBatch& B, const
           break;
         case OP_VLEAF:  // the resource's substituted pattern value (kvvars.cpp): batch predicate table
           if (A) {
-            if constexpr (ELEM) {  // (no variables in an entry's pattern: the compiler refuses them)
+            if constexpr (ELEM && VARS) {  // the element's substituted pattern value
+              const uint32_t v = s_cur[d][lane];
+              const uint32_t dp = vrow[(size_t)ia * vstride + ve];
+              const bool sens = (ityp[dp >> 5] >> (dp & 31u)) & 1u;
+              Node vn{NT_NULL, 0, 0, 0};
+              if (v != ABSENT) vn = N[v];
+              const uint32_t vt = node_type(vn.kt);
+              bool ok;
+              if (vt == NT_ARR) {
+                ok = true;
+                for (uint32_t k = 0; k < vn.b && ok; k++) {
+                  cpu |= kv_int_unsafe(B, N[kv_nix<true>(vn.a + k, rl)], sens);
+                  ok = pred_node(*B.dps, B, N, dp, kv_nix<true>(vn.a + k, rl));
+                }
+              } else {
+                cpu |= kv_int_unsafe(B, vn, sens);
+                ok = pred_eval(*B.dps, B, dp, vt, vn);
+              }
+              if (!ok) raise(E_VALUE, ib, v, ic);
+            } else if constexpr (ELEM) {  // (no variables in this launch's patterns: kvforeach.h FeVarTables)
               cpu = true;
             } else {
               const uint32_t v = s_cur[d][lane];
@@ -373,16 +401,32 @@ __device__ __forceinline__ uint32_t kv_fe_elem_root(const FeTables& T, const uin
 //  3. the pattern walk with that node as the root; ST_CPU when the int64 / float64 typing of a
 //     number could change the verdict (above) or the record does not fit 8 bytes (which includes
 //     the stale counter of a finished loop, below).
+// VARS (V: the launch's FeVarTables): between 2. and 3. the substitution verdict of the set's
+// strings on the element (kv_fe_subst; the gate's SKIP wins): an element it decides is ST_ERROR
+// with a zero record, or ST_CPU, and goes through the walk parked.
+template <bool VARS = false>
 __device__ __forceinline__ uint32_t kv_fe_pat_lane(const FeTables& T, const FePatTables& Q, const DevPS& P,
                                                    const DevBatch& B, const Node* __restrict__ N, uint32_t p, uint32_t e,
                                                    bool valid, uint32_t n_res, uint32_t (*s_cur)[KV_WG],
                                                    uint32_t (*s_lfirst)[KV_WG], uint32_t (*s_llen)[KV_WG],
-                                                   uint32_t (*s_li)[KV_MAXL], uint32_t* res_o, uint32_t* ord_o, uint2* w) {
+                                                   uint32_t (*s_li)[KV_MAXL], uint32_t* res_o, uint32_t* ord_o, uint2* w,
+                                                   const FeVarTables* V = nullptr) {
   const uint32_t* PT = Q.pats + 4u * p;
   const uint32_t s = uni(PT[0]);
   uint32_t res, ord, rl, root;
   bool run;
   uint32_t code = kv_fe_elem_root(T, Q.chain, B, N, s, uni(PT[2]), uni(PT[3]), e, valid, n_res, &res, &ord, &rl, &root, &run);
+  if constexpr (VARS) {
+    const uint32_t* L = T.lists + 4u * T.sets[4u * s];
+    w->x = w->y = 0u;
+    if (run) {
+      const uint32_t sc = kv_fe_subst(T, *V, L, uni(V->runs[2u * p]), uni(V->runs[2u * p + 1u]), e);
+      if (sc) {
+        code = sc;
+        run = false;
+      }
+    }
+  }
   // the wave's loop counters start at zero: an error raised outside a loop records them, and
   // what an earlier program (or kernel) left there must not make the record look too wide.
   // Within one program a finished loop leaves its last index in its counter, and a later error
@@ -393,7 +437,12 @@ __device__ __forceinline__ uint32_t kv_fe_pat_lane(const FeTables& T, const FePa
   uint32_t st = ST_CPU;
   EState es{0, 0, 0, ABSENT, ABSENT, 0, 0, 0, 0};
   bool cpu = false;
-  kv_walk<true>(P, B, N, PT + 1, root, run, res, n_res, rl, s_cur, s_lfirst, s_llen, s_li, st, es, cpu);
+  if constexpr (VARS) {
+    const uint32_t* L = T.lists + 4u * T.sets[4u * s];
+    kv_walk<true, true>(P, B, N, PT + 1, root, run, res, n_res, rl, s_cur, s_lfirst, s_llen, s_li, st, es, cpu,
+                        T.deny.outc + L[0], L[1], e, V->ityp);
+  } else
+    kv_walk<true>(P, B, N, PT + 1, root, run, res, n_res, rl, s_cur, s_lfirst, s_llen, s_li, st, es, cpu);
   if (run) {
     code = cpu ? (uint32_t)ST_CPU : st;
     if (code == ST_FAIL || code == ST_ERROR) {
@@ -421,17 +470,33 @@ __device__ __forceinline__ uint32_t kv_fe_pat_lane(const FeTables& T, const FePa
 // ST_FAIL. The wave's loop counters are cleared before every alternative: a finished loop of
 // alternative k leaves its last index there, and an error of alternative k + 1 outside any loop
 // would record it (a wrong path, or a record that looks wide).
+// VARS (V: the launch's FeVarTables): the reference substitutes the whole anyPattern list before
+// the first alternative is tried, so the verdict of every alternative's strings (kv_fe_subst over
+// the set's run, alternative 0's strings first) comes after the gate and before the loop: an
+// element it decides is ST_ERROR or ST_CPU whatever alternative 0 would say.
+template <bool VARS = false>
 __device__ __forceinline__ uint32_t kv_fe_any_lane(const FeTables& T, const FeAnyTables& A, const DevPS& P,
                                                    const DevBatch& B, const Node* __restrict__ N, uint32_t a, uint32_t e,
                                                    bool valid, uint32_t n_res, uint32_t (*s_cur)[KV_WG],
                                                    uint32_t (*s_lfirst)[KV_WG], uint32_t (*s_llen)[KV_WG],
                                                    uint32_t (*s_li)[KV_MAXL], uint32_t* res_o, uint32_t* ord_o, uint32_t* cw_o,
-                                                   uint2* __restrict__ rec, size_t stride) {
+                                                   uint2* __restrict__ rec, size_t stride,
+                                                   const FeVarTables* V = nullptr) {
   const uint32_t* AT = A.anys + 8u * a;
   const uint32_t s = uni(AT[0]), a0 = uni(AT[1]), na = uni(AT[2]);
   uint32_t res, ord, rl, root;
   bool open;  // the lane is still undecided
   uint32_t code = kv_fe_elem_root(T, A.chain, B, N, s, uni(AT[3]), uni(AT[4]), e, valid, n_res, &res, &ord, &rl, &root, &open);
+  if constexpr (VARS) {
+    const uint32_t* L = T.lists + 4u * T.sets[4u * s];
+    if (open) {
+      const uint32_t sc = kv_fe_subst(T, *V, L, uni(V->runs[2u * a]), uni(V->runs[2u * a + 1u]), e);
+      if (sc) {
+        code = sc;
+        open = false;
+      }
+    }
+  }
   uint32_t cw = 0;
   for (uint32_t k = 0; k < na; k++) {
     if ((threadIdx.x & 63u) == 0u)
@@ -439,7 +504,12 @@ __device__ __forceinline__ uint32_t kv_fe_any_lane(const FeTables& T, const FeAn
     uint32_t st = ST_CPU;
     EState es{0, 0, 0, ABSENT, ABSENT, 0, 0, 0, 0};
     bool cpu = false;
-    kv_walk<true>(P, B, N, A.alts + a0 + k, root, open, res, n_res, rl, s_cur, s_lfirst, s_llen, s_li, st, es, cpu);
+    if constexpr (VARS) {
+      const uint32_t* L = T.lists + 4u * T.sets[4u * s];
+      kv_walk<true, true>(P, B, N, A.alts + a0 + k, root, open, res, n_res, rl, s_cur, s_lfirst, s_llen, s_li, st, es, cpu,
+                          T.deny.outc + L[0], L[1], e, V->ityp);
+    } else
+      kv_walk<true>(P, B, N, A.alts + a0 + k, root, open, res, n_res, rl, s_cur, s_lfirst, s_llen, s_li, st, es, cpu);
     if (open) {
       if (cpu || st == ST_CPU) {
         code = ST_CPU;

@@ -241,6 +241,39 @@ def c2_foreach_anypattern_policies() -> list[dict]:
     return pols
 
 
+# C2_FOREACH_PATTERNS with the `name` / `image` patterns restated over variables of the element and
+# of the resource (whole strings and parts of globs); the three others keep their text, so a policy
+# set built from these has pattern sets with and without variable strings.
+C2_FOREACH_PATVARS_PATTERNS = [
+    {"image": "!*:latest"},
+    {"name": "{{element.name}}"},
+    {"name": "!c2 & !c3", "image": "!docker.io/{{request.object.metadata.namespace}}*"},
+    {"name": "{{element.name}} | c1"},
+    {"(name)": "!c1", "image": "!*e*"},
+    {"imagePullPolicy": "Always"},
+    {"name": "!c3 & {{element.name}}"},
+    {"name": "!{{request.object.metadata.namespace}}"},
+]
+
+
+def c2_foreach_patvars_policies() -> list[dict]:
+    """The pattern twin (``c2_foreach_pattern_policies``) with rule i's pattern taken from
+    ``C2_FOREACH_PATVARS_PATTERNS`` (i mod 8), to be compiled with ``PolicySet(..., foreach=True,
+    foreach_pattern=True, foreach_patvars=True)``: 5 pattern sets with ``{{element.name}}`` /
+    ``{{request.object.metadata.namespace}}`` strings and 3 without, the workload of the measurement
+    of pattern variables in entries (DESIGN.md §3 *Pattern variables in entries*)."""
+    import copy
+
+    n = len(C2_FOREACH_PATVARS_PATTERNS)
+    pols = c2_policies()
+    for i, r in enumerate(pols[0]["spec"]["rules"]):
+        r["validate"] = {"message": r["validate"].get("message", ""),
+                         "foreach": [{"list": "request.object.spec.containers",
+                                      "pattern": copy.deepcopy(C2_FOREACH_PATVARS_PATTERNS[i % n])}]}
+    pols[0]["metadata"]["name"] = "c2-pod-rules-foreach-patvars"
+    return pols
+
+
 def c2_foreach_chain_policies() -> list[dict]:
     """The chain twin of ``c2_foreach_policies``: the same 100 rules with each rule's entry doubled
     into a ``containers`` entry and an ``initContainers`` entry with the same ``deny`` block (rule i:

@@ -50,10 +50,10 @@ typedef void (*ptab_fn)(const DevPS*, const Val*, const uint8_t*, uint32_t, uint
 extern "C" void kvemu_mfac(const DevPS* P, const DevBatch* B, uint32_t* mtup);
 // the pattern sets' rows of the foreach plane (fepat.cpp: kvwalk.h as a one-lane wave)
 extern "C" void kvemu_foreach_pat(const FeTables* T, const FePatTables* Q, const DevPS* P, const DevBatch* B,
-                                  uint32_t n_res, uint8_t* fe_st);
+                                  uint32_t n_res, uint8_t* fe_st, const FeVarTables* V, uint32_t n_vpats);
 // ... and the any sets' (KV_COMPILE_FOREACH_ANYPATTERN)
 extern "C" void kvemu_foreach_any(const FeTables* T, const FeAnyTables* A, const DevPS* P, const DevBatch* B,
-                                  uint32_t n_res, uint8_t* fe_st);
+                                  uint32_t n_res, uint8_t* fe_st, const FeVarTables* V, uint32_t n_vanys, uint32_t n_pats);
 typedef void (*chunk_fn)(const DevPS*, const DevBatch*, const Node*, const Val*, const uint8_t*, DevOut, uint32_t);
 
 static std::string slurp(const char* p) {
@@ -105,7 +105,8 @@ int main(int argc, char** argv) {
     std::string ctx = strcmp(argv[3], "-") ? slurp(argv[3]) : std::string();
     PolicySet ps;
     // KVEMU_COMPILE_FLAGS: kv_compile's flags (2: KV_COMPILE_DENY, 4: KV_COMPILE_FOREACH, 8:
-    // KV_COMPILE_FOREACH_PATTERN, 16: KV_COMPILE_FOREACH_ENTRIES), as the binary's source was generated
+    // KV_COMPILE_FOREACH_PATTERN, 16: KV_COMPILE_FOREACH_ENTRIES, 32: KV_COMPILE_FOREACH_ANYPATTERN,
+    // 64: KV_COMPILE_FOREACH_PATVARS), as the binary's source was generated
     compile_policies(pol.data(), pol.size(), &ps, getenv("KVEMU_COMPILE_FLAGS") ? (uint32_t)atoi(getenv("KVEMU_COMPILE_FLAGS")) : 0u);
     Batch whole;
     ingest_resources(ps, res.data(), res.size(), nullptr, &whole);
@@ -256,15 +257,18 @@ int main(int argc, char** argv) {
       for (size_t s = 0; s < n_fe; s++)
         for (uint32_t r = 0; r < B.n_res && !ps.fsets[s].pattern && !ps.fsets[s].any; r++)
           deny_st[(n_dn + s) * B.n_res + r] = foreach_fold_host(fe, (uint32_t)s, B.n_res, r, nullptr);
+      // (KV_COMPILE_FOREACH_PATVARS, flag 64: the sets with variable strings stand behind the others)
+      const FeVarTables vt = fe.var_view(dyn.ityp.data());
       if (!ps.fpats.empty()) {  // (as launch_foreach: the pattern sets' elements through the pattern walk)
         const FeTables ft = fe.view();
         const FePatTables qt = fe.pat_view();
-        kvemu_foreach_pat(&ft, &qt, &P, &B, B.n_res, deny_st.data() + n_dn * B.n_res);
+        kvemu_foreach_pat(&ft, &qt, &P, &B, B.n_res, deny_st.data() + n_dn * B.n_res, &vt, ps.n_vpats);
       }
       if (!ps.fanys.empty()) {  // (as launch_foreach: the any sets' elements through their alternatives)
         const FeTables ft = fe.view();
         const FeAnyTables at = fe.any_view();
-        kvemu_foreach_any(&ft, &at, &P, &B, B.n_res, deny_st.data() + n_dn * B.n_res);
+        kvemu_foreach_any(&ft, &at, &P, &B, B.n_res, deny_st.data() + n_dn * B.n_res, &vt, ps.n_vanys,
+                          (uint32_t)ps.fpats.size());
       }
       if (n_ch) {  // (as kv_foreach_chain_kernel, after the set rows: a key per status byte, the element left out)
         std::vector<uint32_t> acc(n_fe * B.n_res);
